@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: env-steps/sec of the fused TriFinger step (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, puts the env population into its steady state, warms up, times EXACTLY K steps and prints the result line
+(`value`, `ms_per_step`, the workload).  Everything else moves behind --full: the roofline (HIP event pairs around the timed launches,
+counters parsed from profiles/), the legs beside `value` (resident actions, torch-generated actions, the strong-scaling partition, the
+fast contact set) and the CPU baseline.  --dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy.
 
 N > 1 is launched by the driver as `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`:
 one process per GPU, envs sharded with no data-path collective; RNG is keyed by global env id.  RCCL is used only for the
@@ -18,7 +23,7 @@ Workload = BASELINE.json configs[2]: trifinger_difficulty_4, 65536 envs per GPU,
 defaults of scripts/rlg_hydra.py:58-118 + difficulty-4 reward schedule (:140-182), asymmetric obs on
 (the shipped resources/config/rlg/asymm.yaml default), episode_length 750.
 
-Rank 0 prints ONE JSON line with `roofline` (the fused step kernel vs the HBM roofline, as the north star asks;
+Rank 0 prints ONE JSON line; with --full it carries `roofline` (the fused step kernel vs the HBM roofline, as the north star asks;
 what binds it is the serial chain of the contact solve; HBM traffic and issue counters are parsed
 from the newest matching profiles/r*_pmc.txt, nothing is hard-coded) and `cpu_baseline` (this repo's CPU oracle on the
 host cores - the reference's IsaacGym CPU pipeline cannot be run).
@@ -234,6 +239,37 @@ def cpu_baseline(asym, budget_s=12.0):
                       f"available, baseline is this repo's CPU oracle (oracle/tf_oracle.c)"}
 
 
+DUMP_BUFFERS = ("obs", "states", "reward", "reset_buf", "goal_reset_buf", "successes", "dones", "action_buf", "steps")
+DUMP_MAX_BYTES = 64 << 20
+
+
+def snapshot_outputs(eng):
+    """Host copies of what one step hands its caller (the engine's output buffers), float32 (float64 for the int64 step counter).  When they
+    would exceed DUMP_MAX_BYTES, the same fixed, seeded sample of env rows is taken from every buffer and its env ids are kept beside them."""
+    import numpy as np
+    bufs = {k: getattr(eng, k) for k in DUMP_BUFFERS if getattr(eng, k).numel() > 0}
+    row_bytes = sum((8 if b.dtype == torch.int64 else 4) * (b.numel() // eng.num_envs) for b in bufs.values())
+    rows = None
+    if row_bytes * eng.num_envs > DUMP_MAX_BYTES:
+        keep = DUMP_MAX_BYTES // (row_bytes + 8) - 1
+        rows = np.sort(np.random.default_rng(0).choice(eng.num_envs, size=keep, replace=False))
+    out = {}
+    for k, b in bufs.items():
+        a = b.detach().cpu().numpy()
+        a = a.astype(np.float64 if b.dtype == torch.int64 else np.float32)
+        out[k] = a if rows is None else a[rows]
+    if rows is not None:
+        out["sampled_env_ids"] = rows.astype(np.float64)
+    return out
+
+
+def write_outputs(outputs, dump_dir):
+    import numpy as np
+    os.makedirs(dump_dir, exist_ok=True)
+    for k, a in outputs.items():
+        np.save(os.path.join(dump_dir, f"{k}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -266,7 +302,16 @@ def main():
     ap.add_argument("--time-window", type=int, default=8,
                     help="one HIP event pair per window of W consecutive k_step launches of the timed region (an event "
                          "pair costs ~3 us of stream time: per launch it would slow the region it measures and read "
-                         "2-3 us long; over 8 back-to-back launches it is amortised); 0: no kernel timing")
+                         "2-3 us long; over 8 back-to-back launches it is amortised); 0: no kernel timing.  --full only: a plain run "
+                         "puts no events into the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline figure as well: the roofline (kernel timing, profiles/ counters), the "
+                         "resident-action and torch-action legs, the strong-scaling leg, the fast-contact-set leg and the CPU baseline "
+                         "(--no-* switch single ones off); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to its caller (obs, states, reward, flags, drawn actions, step "
+                         "counters of rank 0's envs) as DIR/<name>.npy, float32 / float64, at most 64 MB (a fixed, seeded sample of env "
+                         "rows beyond that)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -304,6 +349,8 @@ def main():
                       **workload_kwargs(asym, args.difficulty, args.dr))
     eng = TrifingerEngine(cfg, device=dev, lib=lib)
     gen = torch.Generator(device=dev).manual_seed(7 + rank)
+    # the resident-action ring is only stepped with --full, but drawn in every run: its draws come before the prelude's, so that a plain and
+    # a --full run step the same env population
     ring = [(torch.rand(n, eng.action_dim, device=dev, generator=gen) * 2 - 1).contiguous() for _ in range(16)]
     eng.reset()
     # ---- steady state of the workload (untimed set-up, like generating the synthetic inputs) ----
@@ -350,7 +397,8 @@ def main():
         reducer = EpisodeStatsReducer(eng, world * n, every=args.stats_every)
     # ---- the timed region: EXACTLY --steps steps, actions 2*U-1 generated on the device in every step by the
     # step itself (tf_step_random: Philox draws inside the launch) ----
-    eng.enable_kernel_timing(8192 if args.time_window > 0 else 0, max(1, args.time_window))
+    time_window = args.time_window if args.full else 0          # the event pairs feed the roofline only: a plain run times the launches alone
+    eng.enable_kernel_timing(8192 if time_window > 0 else 0, max(1, time_window))
     # the driver's window is 20 steps = 1.4 ms: a cyclic-GC pass of the interpreter inside it (torch is loaded: a full collection takes milliseconds) would
     # be most of the measurement - collect now, keep the collector off while the timed regions run (the loop itself allocates nothing that needs it)
     import gc
@@ -364,33 +412,38 @@ def main():
             reducer.step()
     barrier()
     elapsed = time.perf_counter() - t0
+    # what the last timed step handed its caller, before any later leg steps this engine again
+    outputs = snapshot_outputs(eng) if args.dump_outputs and rank == 0 else None
+    # sanity on what was just timed: finite state, resets happened if steps crossed an episode boundary
+    assert torch.isfinite(eng.state).all(), "non-finite state after the timed region"
     kern_ms, kern_n = eng.kernel_time_ms()
     global_stats = reducer.result().cpu().tolist() if reducer is not None else None
     local_stats = eng.info.cpu().tolist() if reducer is not None else None
     eng.enable_kernel_timing(0)
-    # beside it, over the same number of steps: the step fed from a ring of 16 RESIDENT action tensors (what rounds 1-3 printed as
-    # `value`) ...
-    barrier()
-    t2 = time.perf_counter()
-    for k in range(args.steps):
-        eng.step(ring[k % len(ring)])
-    barrier()
-    elapsed_ring = time.perf_counter() - t2
-    # ... and with torch.rand(N, A)*2-1 generated inside the loop (three extra elementwise launches per step), a quarter of the steps
+    elapsed_ring = elapsed_gen = None
     gen_steps = max(1, args.steps // 4)
-    barrier()
-    t1 = time.perf_counter()
-    for k in range(gen_steps):
-        eng.step(torch.rand(n, eng.action_dim, device=dev, generator=gen) * 2 - 1)
-    barrier()
-    elapsed_gen = time.perf_counter() - t1
+    if args.full:
+        # beside it, over the same number of steps: the step fed from a ring of 16 RESIDENT action tensors (what rounds 1-3 printed as
+        # `value`) ...
+        barrier()
+        t2 = time.perf_counter()
+        for k in range(args.steps):
+            eng.step(ring[k % len(ring)])
+        barrier()
+        elapsed_ring = time.perf_counter() - t2
+        # ... and with torch.rand(N, A)*2-1 generated inside the loop (three extra elementwise launches per step), a quarter of the steps
+        barrier()
+        t1 = time.perf_counter()
+        for k in range(gen_steps):
+            eng.step(torch.rand(n, eng.action_dim, device=dev, generator=gen) * 2 - 1)
+        barrier()
+        elapsed_gen = time.perf_counter() - t1
     if distributed:
-        t = torch.tensor([elapsed, elapsed_gen, elapsed_ring], device=dev if not one_device else "cpu", dtype=torch.float64)
+        t = torch.tensor([elapsed, elapsed_gen or 0.0, elapsed_ring or 0.0], device=dev if not one_device else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed, elapsed_gen, elapsed_ring = float(t[0].item()), float(t[1].item()), float(t[2].item())
-
-    # sanity on what was just timed: finite state, resets happened if steps crossed an episode boundary
-    assert torch.isfinite(eng.state).all(), "non-finite state after the timed region"
+        elapsed = float(t[0].item())
+        if args.full:
+            elapsed_gen, elapsed_ring = float(t[1].item()), float(t[2].item())
 
     # ---- the STRONG-scaling reading of the metric ("@65536 envs, 1/2/4/8 GPUs"; SURVEY 8e partitions N over G): the same workload with
     # --strong-total envs IN TOTAL, rank r stepping shard_range(total, r, world) of them (global env ids and the reward schedule as in one
@@ -398,7 +451,7 @@ def main():
     # of timed steps, same barriers and max over ranks.  At one rank it is the weak leg itself and is not run twice.
     strong_total = args.strong_total if args.strong_total >= 0 else n
     strong = None
-    if strong_total > 0 and (world > 1 or strong_total != n):
+    if args.full and strong_total > 0 and (world > 1 or strong_total != n):
         from leibnizgym_amd.sharding import shard_range
         off, cnt = shard_range(strong_total, rank, world)
         cfg_s = make_config(lib, cnt, seed=7, env_id_offset=off, global_num_envs=strong_total,
@@ -437,7 +490,7 @@ def main():
     # it; `native.ff_middle_pairs: false` restores the distal pairs only - the faster step every earlier round's `value` was.  Same prelude, same
     # warm-up, same frame window, same number of timed steps, same barriers and max over ranks.
     fast = None
-    if not args.no_fast_contact_leg:
+    if args.full and not args.no_fast_contact_leg:
         model_f = lib.box_model((0.02, 0.08, 0.02), 500.0) if args.box else lib.default_model()
         model_f.ff_middle_pairs = 0
         cfg_f = make_config(lib, n, seed=7, env_id_offset=rank * n, global_num_envs=world * n, model=model_f, **workload_kwargs(asym, args.difficulty, args.dr))
@@ -469,45 +522,8 @@ def main():
 
     total_env_steps = world * n * args.steps
     value = total_env_steps / elapsed
-    kern_avg_s = (kern_ms / max(kern_n, 1)) * 1e-3
-    # `value` launches the step with the action source fused in (tf_step_random): it draws its actions and never reads the action tensor, so the
-    # 36 B/env of SURVEY's figure that are the action read are NOT counted for it (the resident-action instantiation would count them)
-    alg_bytes = BYTES_PER_ENV_STEP[asym] - ACTION_READ_BYTES
-    bytes_per_launch = alg_bytes * n
-    achieved_gbs = bytes_per_launch / kern_avg_s / 1e9 if kern_n else 0.0
-    ext = 2 if args.box else (1 if args.dr else 0)     # extended DR -> EXT = 1, box object -> EXT = 2 instantiation of the fused step
-    pmc, pmc_path = load_pmc_profile(n, asym, ext, eng.kernel_variant) if (headline or ext) else (None, None)      # counters of the kernel `value` launches
-    traffic = traffic_raw = issue = None
-    traffic_how = None
-    if pmc and "FETCH_SIZE" in pmc and "WRITE_SIZE" in pmc:
-        traffic_raw = (pmc["FETCH_SIZE"] + pmc["WRITE_SIZE"]) * 1024.0      # KiB per dispatch -> bytes
-        cal, cal_path = load_pmc_calibration()
-        if cal:
-            # write-only API tensors of a launch (obs, states, action_buf as tiles; 1.0 in the calibration) vs state rows that the
-            # step reads and rewrites in place (their stores are tallied twice, their loads once)
-            tile = n * 4.0 * (TF_OBS_BASE + eng.action_dim + ((TF_OBS_BASE + eng.action_dim + TF_STATES_EXTRA) if asym else 0) + eng.action_dim)
-            w_raw = pmc["WRITE_SIZE"] * 1024.0
-            w_true = tile * cal["write_tile"] + max(0.0, w_raw - tile) * cal["write_rows_in_place"]
-            traffic = pmc["FETCH_SIZE"] * 1024.0 * cal["fetch_rows_in_place"] + w_true
-            traffic_how = (f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes), {pmc_path}, corrected with the factors measured on "
-                           f"known byte counts in this kernel's access patterns ({cal_path}): stores of rows rewritten in place x{cal['write_rows_in_place']:.3f} "
-                           f"(the counter tallies them twice), tile stores x{cal['write_tile']:.3f} ({tile / 1e6:.1f} MB per launch: obs, states, action_buf), "
-                           f"loads of those rows x{cal['fetch_rows_in_place']:.3f}; the read-only rows (action 36 B, goal 40 B per env) may be "
-                           f"under-counted by up to half (x{cal['fetch_rows_read_only']:.2f} for a pure read stream); traffic_raw = the two counters as printed")
-        else:
-            traffic = traffic_raw
-            traffic_how = f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes, raw counters), {pmc_path}"
-    if pmc and "SQ_INSTS_VALU" in pmc and "SQ_WAVE_CYCLES" in pmc:
-        issue = {
-            "valu_insts_per_launch": pmc["SQ_INSTS_VALU"], "waves_per_launch": pmc.get("SQ_WAVES"),
-            "wave_cycles_per_launch": pmc["SQ_WAVE_CYCLES"] * 4.0,              # the counter is in quad-cycles
-            # fraction of the resident wave-cycles in which a VALU instruction of that wave occupies the SIMD
-            "valu_issue_frac": pmc["SQ_INSTS_VALU"] * VALU_CYCLES_PER_INST / (pmc["SQ_WAVE_CYCLES"] * 4.0),
-            "wait_frac": pmc.get("SQ_WAIT_ANY", 0.0) / pmc["SQ_WAVE_CYCLES"],
-            "source": f"rocprofv3 --pmc SQ_*, {pmc_path}",
-        }
-    clock_ghz = 2.4
-    simd_busy = (pmc["SQ_INSTS_VALU"] * VALU_CYCLES_PER_INST / (N_SIMD * kern_avg_s * clock_ghz * 1e9)) if (pmc and kern_n and "SQ_INSTS_VALU" in pmc) else None
+    # at one rank the strong partition of the envs is the weak one: its reading is `value` itself, no leg of its own
+    one_partition = world == 1 and strong_total == n
     secondary = "" if headline else " [secondary run: not the headline workload]"
     out = {
         "metric": "env-steps/sec (whole node), trifinger_difficulty_4 @65536 envs, 1/2/4/8 GPUs" + secondary,
@@ -520,26 +536,17 @@ def main():
         "higher_is_better": True,
         "scaling": "weak",
         # the strong-scaling reading of the metric: 65536 envs IN TOTAL partitioned over the ranks (at one rank: the weak figure itself)
-        "value_strong_65536_total": (strong["value"] if strong else (value if strong_total == n else None)) if strong_total == 65536 else None,
+        "value_strong_65536_total": (strong["value"] if strong else (value if one_partition else None)) if strong_total == 65536 else None,
         "strong_scaling": strong if strong else ({"global_envs": n, "envs_per_gpu": n, "ms_per_step": elapsed / args.steps * 1e3, "value": value,
-                                                  "same_as": "value (one rank: the weak and the strong partition coincide)"} if strong_total == n else None),
+                                                  "same_as": "value (one rank: the weak and the strong partition coincide)"} if one_partition else None),
         # the default model = the reference's contact set since API 8; the opt-out (the step of every earlier round) beside it
         "contact_set": "TfModel.ff_middle_pairs = 1 (default since API 8): every finger-finger pair the reference's self-collision group holds among the "
                        "modelled shapes - the three distal pairs and the six middle-distal pairs (trifinger_env.py:811-812)",
-        "value_fast_contact_set": fast["value"] if fast else None,
-        "fast_contact_set": fast,
         "comparability": "`value` of rounds 1-5 was timed on the fast contact set (compare their `value` with `value_fast_contact_set`); rounds 1-4 "
                          "did not set the frame counter back after the prelude (reward-schedule switch outside their window)",
         "vs_baseline": None,
         "dtype": "f32",
         "data": "synthetic",
-        "value_resident_actions": world * n * args.steps / elapsed_ring,
-        "value_with_torch_action_generation": world * n * gen_steps / elapsed_gen,
-        "action_generation": f"`value`: every step generates its actions 2*U-1 on the device (BASELINE.md section 4) inside the launch itself "
-                             f"(tf_step_random: Philox draws keyed by global env id and frame count); `value_resident_actions`: the same "
-                             f"{args.steps} steps fed from a ring of 16 resident action tensors (what rounds 1-3 reported as `value`); "
-                             f"`value_with_torch_action_generation`: {gen_steps} steps with torch.rand(N, A)*2-1 generated inside the loop "
-                             f"(three extra elementwise launches per step)",
         "reward_schedule_in_window": (f"frames {frame_first}..{frame_first + args.steps} are timed (the frame counter is set back after the prelude): the "
                                       f"finger_reach_object_rate term switches off at frame {switch_frame} (env_steps_count 1e7), "
                                       + ("inside the window" if frame_first < switch_frame <= frame_first + args.steps else "outside the window")),
@@ -560,50 +567,103 @@ def main():
             "parallelism": f"env-shard x{world} (no data-path collective"
                            + (f"; episode statistics all-reduced every {args.stats_every} steps on a side stream)" if reducer else ")"),
         },
-        "roofline": {
-            "bound": "hbm",
-            "achieved": achieved_gbs,
-            "achieved_is": "algorithmic bytes per launch (SURVEY 8d: 1075 B/env-step asymmetric, 623 B symmetric, MINUS the 36 B action read, which the "
-                           "timed instantiation - actions drawn inside the launch - does not perform; the solver's warm-start rows are an "
-                           "implementation choice and are not counted) / measured kernel time",
-            "peak": HBM_PEAK_GBS,
-            "unit": "GB/s",
-            "frac": achieved_gbs / HBM_PEAK_GBS,
-            "traffic": traffic,
-            "traffic_raw": traffic_raw,
-            "traffic_source": traffic_how,
-            "kernel": kernel_name(asym, eng.action_dim, ext, True, eng.kernel_variant),
-            "kernel_variant": eng.kernel_variant,
-            "kernel_avg_us": kern_avg_s * 1e6,
-            "kernel_launches_timed": kern_n,
-            "kernel_timing": f"one HIP event pair on the launch stream around every window of {max(1, args.time_window)} "
-                             f"consecutive launches of the fused step kernel in the timed region; kernel_avg_us = window time / launches",
-            "algorithmic_bytes_per_env_step": alg_bytes,
-            "algorithmic_bytes_per_env_step_survey": BYTES_PER_ENV_STEP[asym],
-            "note": "north star asks for the HBM fraction; what binds the fused step is the serial dependency chain of the "
-                    "Gauss-Seidel solve (one chain per 64 envs, carried by the cube wavefront of each workgroup) and "
-                    "instruction issue, not bandwidth: see valu_issue and DESIGN.md section 4",
-            "valu_issue": issue,
-            "valu_issue_frac": issue["valu_issue_frac"] if issue else None,
-            "simd_valu_busy": simd_busy,
-            # measured operation count: vector-ALU lane-operations per env-step = SQ_INSTS_VALU x 64 lanes / N (every wave64 VALU
-            # instruction of the launch, fp32 arithmetic and the integer / select / move instructions around it alike; an FMA is ONE
-            # lane-operation).  The chip retires 256 CU x 4 SIMD x 32 lanes x 2.4 GHz = 78.6 T lane-operations/s (its 157.3 TFLOP/s
-            # count an FMA as two), so valu_lane_ops_frac = lane-operations/s / 78.6e12.
-            "valu_lane_ops_per_env_step": (pmc["SQ_INSTS_VALU"] * 64.0 / n) if (pmc and "SQ_INSTS_VALU" in pmc) else None,
-            "valu_lane_ops_frac": (pmc["SQ_INSTS_VALU"] * 64.0 / kern_avg_s / (FP32_PEAK_TFLOPS * 0.5e12)) if (pmc and kern_n and "SQ_INSTS_VALU" in pmc) else None,
-            "flops_per_env_step": FLOPS_PER_ENV_STEP,
-            "flops_source": "exact count of the oracle's instrumented build on the default model of API 8 (tests/test_flop_count.py)",
-            "fp32_frac": (FLOPS_PER_ENV_STEP * n / kern_avg_s / 1e12 / FP32_PEAK_TFLOPS) if kern_n else 0.0,
-        },
     }
+    if args.full:
+        kern_avg_s = (kern_ms / max(kern_n, 1)) * 1e-3
+        # `value` launches the step with the action source fused in (tf_step_random): it draws its actions and never reads the action tensor, so the
+        # 36 B/env of SURVEY's figure that are the action read are NOT counted for it (the resident-action instantiation would count them)
+        alg_bytes = BYTES_PER_ENV_STEP[asym] - ACTION_READ_BYTES
+        bytes_per_launch = alg_bytes * n
+        achieved_gbs = bytes_per_launch / kern_avg_s / 1e9 if kern_n else 0.0
+        ext = 2 if args.box else (1 if args.dr else 0)     # extended DR -> EXT = 1, box object -> EXT = 2 instantiation of the fused step
+        pmc, pmc_path = load_pmc_profile(n, asym, ext, eng.kernel_variant) if (headline or ext) else (None, None)      # counters of the kernel `value` launches
+        traffic = traffic_raw = issue = None
+        traffic_how = None
+        if pmc and "FETCH_SIZE" in pmc and "WRITE_SIZE" in pmc:
+            traffic_raw = (pmc["FETCH_SIZE"] + pmc["WRITE_SIZE"]) * 1024.0      # KiB per dispatch -> bytes
+            cal, cal_path = load_pmc_calibration()
+            if cal:
+                # write-only API tensors of a launch (obs, states, action_buf as tiles; 1.0 in the calibration) vs state rows that the
+                # step reads and rewrites in place (their stores are tallied twice, their loads once)
+                tile = n * 4.0 * (TF_OBS_BASE + eng.action_dim + ((TF_OBS_BASE + eng.action_dim + TF_STATES_EXTRA) if asym else 0) + eng.action_dim)
+                w_raw = pmc["WRITE_SIZE"] * 1024.0
+                w_true = tile * cal["write_tile"] + max(0.0, w_raw - tile) * cal["write_rows_in_place"]
+                traffic = pmc["FETCH_SIZE"] * 1024.0 * cal["fetch_rows_in_place"] + w_true
+                traffic_how = (f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes), {pmc_path}, corrected with the factors measured on "
+                               f"known byte counts in this kernel's access patterns ({cal_path}): stores of rows rewritten in place x{cal['write_rows_in_place']:.3f} "
+                               f"(the counter tallies them twice), tile stores x{cal['write_tile']:.3f} ({tile / 1e6:.1f} MB per launch: obs, states, action_buf), "
+                               f"loads of those rows x{cal['fetch_rows_in_place']:.3f}; the read-only rows (action 36 B, goal 40 B per env) may be "
+                               f"under-counted by up to half (x{cal['fetch_rows_read_only']:.2f} for a pure read stream); traffic_raw = the two counters as printed")
+            else:
+                traffic = traffic_raw
+                traffic_how = f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes, raw counters), {pmc_path}"
+        if pmc and "SQ_INSTS_VALU" in pmc and "SQ_WAVE_CYCLES" in pmc:
+            issue = {
+                "valu_insts_per_launch": pmc["SQ_INSTS_VALU"], "waves_per_launch": pmc.get("SQ_WAVES"),
+                "wave_cycles_per_launch": pmc["SQ_WAVE_CYCLES"] * 4.0,              # the counter is in quad-cycles
+                # fraction of the resident wave-cycles in which a VALU instruction of that wave occupies the SIMD
+                "valu_issue_frac": pmc["SQ_INSTS_VALU"] * VALU_CYCLES_PER_INST / (pmc["SQ_WAVE_CYCLES"] * 4.0),
+                "wait_frac": pmc.get("SQ_WAIT_ANY", 0.0) / pmc["SQ_WAVE_CYCLES"],
+                "source": f"rocprofv3 --pmc SQ_*, {pmc_path}",
+            }
+        clock_ghz = 2.4
+        simd_busy = (pmc["SQ_INSTS_VALU"] * VALU_CYCLES_PER_INST / (N_SIMD * kern_avg_s * clock_ghz * 1e9)) if (pmc and kern_n and "SQ_INSTS_VALU" in pmc) else None
+        out.update({
+            "value_fast_contact_set": fast["value"] if fast else None,
+            "fast_contact_set": fast,
+            "value_resident_actions": world * n * args.steps / elapsed_ring,
+            "value_with_torch_action_generation": world * n * gen_steps / elapsed_gen,
+            "action_generation": f"`value`: every step generates its actions 2*U-1 on the device (BASELINE.md section 4) inside the launch itself "
+                                 f"(tf_step_random: Philox draws keyed by global env id and frame count); `value_resident_actions`: the same "
+                                 f"{args.steps} steps fed from a ring of 16 resident action tensors (what rounds 1-3 reported as `value`); "
+                                 f"`value_with_torch_action_generation`: {gen_steps} steps with torch.rand(N, A)*2-1 generated inside the loop "
+                                 f"(three extra elementwise launches per step)",
+            "roofline": {
+                "bound": "hbm",
+                "achieved": achieved_gbs,
+                "achieved_is": "algorithmic bytes per launch (SURVEY 8d: 1075 B/env-step asymmetric, 623 B symmetric, MINUS the 36 B action read, which the "
+                               "timed instantiation - actions drawn inside the launch - does not perform; the solver's warm-start rows are an "
+                               "implementation choice and are not counted) / measured kernel time",
+                "peak": HBM_PEAK_GBS,
+                "unit": "GB/s",
+                "frac": achieved_gbs / HBM_PEAK_GBS,
+                "traffic": traffic,
+                "traffic_raw": traffic_raw,
+                "traffic_source": traffic_how,
+                "kernel": kernel_name(asym, eng.action_dim, ext, True, eng.kernel_variant),
+                "kernel_variant": eng.kernel_variant,
+                "kernel_avg_us": kern_avg_s * 1e6,
+                "kernel_launches_timed": kern_n,
+                "kernel_timing": f"one HIP event pair on the launch stream around every window of {max(1, args.time_window)} "
+                                 f"consecutive launches of the fused step kernel in the timed region; kernel_avg_us = window time / launches",
+                "algorithmic_bytes_per_env_step": alg_bytes,
+                "algorithmic_bytes_per_env_step_survey": BYTES_PER_ENV_STEP[asym],
+                "note": "north star asks for the HBM fraction; what binds the fused step is the serial dependency chain of the "
+                        "Gauss-Seidel solve (one chain per 64 envs, carried by the cube wavefront of each workgroup) and "
+                        "instruction issue, not bandwidth: see valu_issue and DESIGN.md section 4",
+                "valu_issue": issue,
+                "valu_issue_frac": issue["valu_issue_frac"] if issue else None,
+                "simd_valu_busy": simd_busy,
+                # measured operation count: vector-ALU lane-operations per env-step = SQ_INSTS_VALU x 64 lanes / N (every wave64 VALU
+                # instruction of the launch, fp32 arithmetic and the integer / select / move instructions around it alike; an FMA is ONE
+                # lane-operation).  The chip retires 256 CU x 4 SIMD x 32 lanes x 2.4 GHz = 78.6 T lane-operations/s (its 157.3 TFLOP/s
+                # count an FMA as two), so valu_lane_ops_frac = lane-operations/s / 78.6e12.
+                "valu_lane_ops_per_env_step": (pmc["SQ_INSTS_VALU"] * 64.0 / n) if (pmc and "SQ_INSTS_VALU" in pmc) else None,
+                "valu_lane_ops_frac": (pmc["SQ_INSTS_VALU"] * 64.0 / kern_avg_s / (FP32_PEAK_TFLOPS * 0.5e12)) if (pmc and kern_n and "SQ_INSTS_VALU" in pmc) else None,
+                "flops_per_env_step": FLOPS_PER_ENV_STEP,
+                "flops_source": "exact count of the oracle's instrumented build on the default model of API 8 (tests/test_flop_count.py)",
+                "fp32_frac": (FLOPS_PER_ENV_STEP * n / kern_avg_s / 1e12 / FP32_PEAK_TFLOPS) if kern_n else 0.0,
+            },
+        })
     if global_stats is not None:
         out["episode_stats_all_reduced"] = global_stats[:11]
         out["episode_stats_rank0"] = local_stats[:11]          # this rank's own statistics of the same step (equal to the reduced ones in a world of one)
     gc.enable()
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(asym)
+        if outputs is not None:
+            write_outputs(outputs, args.dump_outputs)
         print(json.dumps(out), flush=True)
     eng.close()
     if distributed or reducer is not None:

@@ -26,9 +26,9 @@ def launch(script_args, nproc=2):
 
 
 def test_single_process_line_carries_the_contract(hip):
-    """`python bench.py` (N = 1): one JSON line with the contract's keys, `value` = envs x steps / elapsed of the step with on-device action
+    """`python bench.py --full` (N = 1): one JSON line with the contract's keys, `value` = envs x steps / elapsed of the step with on-device action
     generation, `roofline` (bound / achieved / peak / unit / frac / traffic, measured kernel time) and what the steady-state prelude did."""
-    p = subprocess.run([sys.executable, "bench.py", "--steps", "40", "--warmup", "3", "--envs", "8192", "--settle", "30", "--no-cpu-baseline"],
+    p = subprocess.run([sys.executable, "bench.py", "--steps", "40", "--warmup", "3", "--envs", "8192", "--settle", "30", "--no-cpu-baseline", "--full"],
                        cwd=REPO, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-1500:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -53,7 +53,7 @@ def test_single_process_line_carries_the_contract(hip):
 
 
 def test_two_ranks_print_one_aggregate_line(hip):
-    p = launch(["bench.py", "--gpus", "2", "--steps", "100", "--warmup", "5", "--envs", "8192"])
+    p = launch(["bench.py", "--gpus", "2", "--steps", "100", "--warmup", "5", "--envs", "8192", "--full"])
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, lines
     d = json.loads(lines[0])
@@ -73,7 +73,7 @@ def test_two_ranks_print_one_aggregate_line(hip):
 def test_eight_ranks_on_one_device(hip):
     """The driver's 8-GPU command line (`--nproc-per-node 8 ... bench.py --gpus 8`) with all eight ranks on cuda:0 and small shards:
     rank offsets 0, 2048, ..., one aggregate JSON line from rank 0 - so that the first real 8-GPU run cannot fail on plumbing."""
-    p = launch(["bench.py", "--gpus", "8", "--steps", "20", "--warmup", "5", "--envs", "2048", "--settle", "50", "--strong-total", "65536"], nproc=8)
+    p = launch(["bench.py", "--gpus", "8", "--steps", "20", "--warmup", "5", "--envs", "2048", "--settle", "50", "--strong-total", "65536", "--full"], nproc=8)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, lines
     d = json.loads(lines[0])

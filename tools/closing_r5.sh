@@ -10,10 +10,10 @@ python3 tools/sweep.py 2>&1 | grep -v amdgpu.ids > $O/${T}_sweep.txt; cat $O/${T
 python3 -c "from leibnizgym_amd import _capi; _capi.TfLib('leibnizgym_amd/csrc/libtrifinger_hip_timing.so')" 2>/dev/null || echo "STALE timing build: run make -C leibnizgym_amd/csrc libtrifinger_hip_timing.so before this script (the phase tables below will be an error trace)"
 { python3 tools/phase_timing.py 65536 600; python3 tools/phase_timing.py 8192 600; } 2>&1 | grep -v amdgpu.ids > $O/${T}_phase_timing_steady.txt
 python3 tools/api_bench.py 2>&1 | grep -v amdgpu.ids > $O/${T}_api_layers.txt
-python3 bench.py --difficulty 1 --envs 8192 --no-cpu-baseline > $O/${T}_bench_config1.json 2>/dev/null
+python3 bench.py --full --difficulty 1 --envs 8192 --no-cpu-baseline > $O/${T}_bench_config1.json 2>/dev/null
 # the multi-rank command lines on one device (plumbing, not rates): 2 and 8 ranks with the strong-scaling leg
-TF_BENCH_SINGLE_DEVICE_TEST=1 HSA_ENABLE_IPC_MODE_LEGACY=0 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29617 bench.py --gpus 8 --steps 50 --warmup 5 --envs 8192 --settle 100 --strong-total 65536 2>/dev/null | grep "^{" > $O/${T}_bench_8_ranks_one_device.json
-for i in 1 2 3; do python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | python3 -c "
+TF_BENCH_SINGLE_DEVICE_TEST=1 HSA_ENABLE_IPC_MODE_LEGACY=0 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29617 bench.py --full --gpus 8 --steps 50 --warmup 5 --envs 8192 --settle 100 --strong-total 65536 2>/dev/null | grep "^{" > $O/${T}_bench_8_ranks_one_device.json
+for i in 1 2 3; do python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

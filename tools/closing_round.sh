@@ -8,7 +8,7 @@ bash tools/profile_round.sh $T > $O/${T}_profile_log.txt 2>&1
 bash tools/profile_ext.sh $T > $O/${T}_ext_log.txt 2>&1
 python3 tools/sweep.py 2>&1 | grep -v amdgpu.ids > $O/${T}_sweep.txt
 python3 tools/api_bench.py 2>&1 | grep -v amdgpu.ids > $O/${T}_api_layers.txt
-python3 bench.py --difficulty 1 --envs 8192 --no-cpu-baseline > $O/${T}_bench_config1.json 2>/dev/null
+python3 bench.py --full --difficulty 1 --envs 8192 --no-cpu-baseline > $O/${T}_bench_config1.json 2>/dev/null
 [ -f leibnizgym_amd/csrc/libtrifinger_hip_timing.so ] && { python3 tools/phase_timing.py 65536; python3 tools/phase_timing.py 8192; } 2>&1 | grep -v amdgpu.ids > $O/${T}_phase_timing.txt
 { timeout 600 python tools/penetration_stats.py 65536 3000; timeout 600 python tools/penetration_stats.py 65536 3000 dr; } 2>&1 | grep -v amdgpu.ids > $O/${T}_penetration.txt
 for S in 7 11 23; do timeout 500 python tools/ppo_learning_check.py 800 8192 $S fused 4 2>&1 | grep -v amdgpu.ids > $O/${T}_ppo_learning_d4_seed$S.txt; done

@@ -5,7 +5,7 @@
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:?}" || exit 1
 O=gpurun_out; mkdir -p $O
 TF_BENCH_SINGLE_DEVICE_TEST=1 HSA_ENABLE_IPC_MODE_LEGACY=0 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29571 \
-  bench.py --gpus 8 --dr --envs 16384 --steps 200 --warmup 5 --stats-every 4 2>/dev/null | grep "^{" > $O/${1:-rX}_config3_8_ranks_one_device.json
+  bench.py --full --gpus 8 --dr --envs 16384 --steps 200 --warmup 5 --stats-every 4 2>/dev/null | grep "^{" > $O/${1:-rX}_config3_8_ranks_one_device.json
 python3 -c "
 import json,sys
 d=json.load(open('$O/${1:-rX}_config3_8_ranks_one_device.json'))

@@ -16,12 +16,12 @@ for l in sys.stdin:
 "; }
 {
 echo "# rocm-smi clocks before"; rocm-smi --showclocks 2>/dev/null | grep -i -E "sclk|mclk|fclk" | head -4
-for i in 1 2 3 4 5 6; do echo "# run $i: python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline (fresh process)"; python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | pick; done
-echo "# the driver's command as is (with the cpu_baseline leg)"; python3 bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | pick
-for W in 100 500 2000; do echo "# --steps 20 --warmup $W"; python3 bench.py --gpus 1 --steps 20 --warmup $W --no-cpu-baseline 2>/dev/null | pick; done
-for S in 200 2000; do echo "# --steps $S --warmup 10"; python3 bench.py --gpus 1 --steps $S --warmup 10 --no-cpu-baseline 2>/dev/null | pick; done
+for i in 1 2 3 4 5 6; do echo "# run $i: python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline (fresh process)"; python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | pick; done
+echo "# the same command with the cpu_baseline leg"; python3 bench.py --full --gpus 1 --steps 20 --warmup 5 2>/dev/null | pick
+for W in 100 500 2000; do echo "# --steps 20 --warmup $W"; python3 bench.py --full --gpus 1 --steps 20 --warmup $W --no-cpu-baseline 2>/dev/null | pick; done
+for S in 200 2000; do echo "# --steps $S --warmup 10"; python3 bench.py --full --gpus 1 --steps $S --warmup 10 --no-cpu-baseline 2>/dev/null | pick; done
 echo "# per-launch durations of k_env under rocprofv3 --kernel-trace, driver command (us, launch order: reset, 5 warm-up, 20 timed, ...)"
-rm -rf $O/prof_dr; rocprofv3 --kernel-trace -d $O/prof_dr -o r -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > /dev/null 2>&1
+rm -rf $O/prof_dr; rocprofv3 --kernel-trace -d $O/prof_dr -o r -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > /dev/null 2>&1
 python3 - <<PY
 import sqlite3, glob
 db = glob.glob("$O/prof_dr/**/*.db", recursive=True)[0]

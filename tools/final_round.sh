@@ -6,8 +6,8 @@ T=${1:-rX}; O=gpurun_out
 bash tools/profile_round.sh $T > $O/${T}_profile_log.txt 2>&1
 python3 tools/sweep.py 2>&1 | grep -v amdgpu.ids > $O/${T}_sweep.txt
 python3 tools/api_bench.py 2>&1 | grep -v amdgpu.ids > $O/${T}_api_layers.txt
-python3 bench.py --difficulty 1 --envs 8192 --no-cpu-baseline > $O/${T}_bench_config1.json 2>/dev/null
-python3 bench.py --dr --envs 16384 --no-cpu-baseline > $O/${T}_bench_config3.json 2>/dev/null
+python3 bench.py --full --difficulty 1 --envs 8192 --no-cpu-baseline > $O/${T}_bench_config1.json 2>/dev/null
+python3 bench.py --full --dr --envs 16384 --no-cpu-baseline > $O/${T}_bench_config3.json 2>/dev/null
 [ -f leibnizgym_amd/csrc/libtrifinger_hip_timing.so ] && { python3 tools/phase_timing.py 65536; python3 tools/phase_timing.py 8192; } 2>&1 | grep -v amdgpu.ids > $O/${T}_phase_timing.txt
 bash tools/ppo_profile.sh $T > /dev/null 2>&1
 python3 tools/gemm_kernels_bench.py 8192 2>&1 | grep -v amdgpu.ids > $O/${T}_gemm_kernels.txt

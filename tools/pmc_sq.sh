@@ -7,8 +7,8 @@ OUT=gpurun_out/${P}_sq.txt
 : > $OUT
 run() {
   d=gpurun_out/pmc_$P/$1; shift
-  rocprofv3 --pmc "$@" -d $d -o r -- python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline > /dev/null 2>&1
-  echo "# rocprofv3 --pmc $* -- python3 bench.py --steps 50 --warmup 5 --no-cpu-baseline" >> $OUT
+  rocprofv3 --pmc "$@" -d $d -o r -- python3 bench.py --full --steps 50 --warmup 5 --no-cpu-baseline > /dev/null 2>&1
+  echo "# rocprofv3 --pmc $* -- python3 bench.py --full --steps 50 --warmup 5 --no-cpu-baseline" >> $OUT
   python3 tools/rocprof_summary.py pmc $(find $d -name "*.db" | head -1) "k_env<9, false, true, 63" >> $OUT
   rm -rf $d
 }

@@ -9,7 +9,7 @@ for W in dr box; do
   for N in 16384 65536; do
     # <= 32768 envs: the 256-register instantiation; <= 16384 envs and not the box object: with helper wavefronts
     K="k_env<9, false, true, 127, $([ $W = box ] && echo 2 || echo 1), $([ $N -le 32768 ] && echo true || echo false), $([ $N -le 16384 ] && [ $W != box ] && echo true || echo false)>"
-    B="python3 bench.py --$W --envs $N --no-cpu-baseline --no-fast-contact-leg"
+    B="python3 bench.py --full --$W --envs $N --no-cpu-baseline --no-fast-contact-leg"
     P=$O/${T}_ext_${W}_${N}
     rocprofv3 --kernel-trace --stats -d $O/prof_$T/trace -o r -- $B --steps 300 --warmup 5 > /dev/null 2>&1
     { echo "# command: rocprofv3 --kernel-trace --stats -- $B --steps 300 --warmup 5   (MI355X)"

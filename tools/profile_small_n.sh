@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:?}" || exit 1
 T=${1:-rX}; O=gpurun_out; mkdir -p $O
 : > $O/${T}_small_n_kernel_trace.txt; : > $O/${T}_small_n_pmc.txt
 for N in 8192 16384; do
-  B="python3 bench.py --envs $N --no-cpu-baseline --no-fast-contact-leg"
+  B="python3 bench.py --full --envs $N --no-cpu-baseline --no-fast-contact-leg"
   rocprofv3 --kernel-trace --stats -d $O/prof_sn/trace -o r -- $B --steps 500 --warmup 5 > /dev/null 2>&1
   { echo "# command: rocprofv3 --kernel-trace --stats -- $B --steps 500 --warmup 5   (MI355X)"
     python3 tools/rocprof_summary.py trace $(find $O/prof_sn/trace -name "*.db" | head -1) | head -8; echo; } >> $O/${T}_small_n_kernel_trace.txt

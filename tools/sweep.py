@@ -4,7 +4,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 rows = []
 for sym in (False, True):
     for n in (8192, 16384, 32768, 65536, 131072, 262144):
-        cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--envs", str(n), "--steps", "500", "--warmup", "10", "--no-cpu-baseline"]
+        cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--full", "--envs", str(n), "--steps", "500", "--warmup", "10", "--no-cpu-baseline"]
         if sym: cmd.append("--symmetric")
         out = subprocess.run(cmd, capture_output=True, text=True).stdout.strip().splitlines()[-1]
         d = json.loads(out)
