@@ -45,7 +45,8 @@
 extern "C" {
 #endif
 
-#define TF_API_VERSION 8
+/* 9: TfModel.cube_wall_surface appended (opt-in surface normal for the cube corners on the flared part of the boundary) */
+#define TF_API_VERSION 9
 
 typedef enum TfStatus {
     TF_OK = 0,
@@ -109,7 +110,9 @@ enum {
     TF_S_LAM_TW = 122,   /*  9 fingertip-boundary-wall contact of finger f, same layout                             */
     TF_S_LAM_CF = 131,   /* 12 cube corner i against the floor at [3i..3i+2]: +z (normal), +x, +y                   */
     TF_S_CF_FACE = 143,  /*  1 cube face whose corners those were (0 none, 1..6)                                   */
-    TF_S_LAM_CW = 144,   /* 12 cube corner i against the boundary wall at [3i..3i+2]: normal, tangent, +z          */
+    TF_S_LAM_CW = 144,   /* 12 cube corner i against the boundary wall at [3i..3i+2]: normal, tangent, +z; with TfModel.cube_wall_surface
+                          *    on, a corner above wall_z[0] holds the tilted normal (c n_h, s), the horizontal tangent and the UP-SLOPE
+                          *    tangent (-s n_h, c) in place of +z (on the vertical ring the two models coincide)                       */
     TF_S_CW_FACE = 156,  /*  1 feature those rows belong to: cube face 1..6 + 8 x which pair of its corners is the lower one (0..3) + 32 x order
                           *    inside that pair (nearer corner first); 0 while no corner touches the boundary (TF_S_LAM_CW then undefined) */
     /* Samples of the env's NEXT reset (API 6; an implementation choice like the warm start, not algorithmic traffic).  The step that flags an env for
@@ -213,10 +216,12 @@ typedef struct TfModel {
      * pieces of meshes/convex_table_boundary/convex_*.obj (high_table_boundary.urdf:20-259) via tests/golden/model.npz: mid-way
      * between the chords and the corners of the polygonal inner surface.  The FINGERTIP contact follows the tilt of the surface (normal (c n_h, s) with
      * c, s the cosine and sine of the slope angle of the segment, gap = distance to the tilted surface).  The CUBE CORNERS see the same profile - the radius
-     * at the corner's height - with the HORIZONTAL normal at every height: THIS IS THE MODEL, not an omission pending repair.  A cube that lies on the table
-     * meets the boundary with its lower corners, below the first knot, where the two normals coincide; a corner on the cone (a lifted or tumbling cube at the
-     * boundary: 0.007 % of the env-steps of the bench workload) is stopped radially and gets no vertical impulse where the surface normal would give
-     * 0.57 |dv_r| (tests/test_contact_scenarios.py: test_cube_corner_on_the_cone_keeps_the_horizontal_normal, test_random_actions_rarely_put_...). */
+     * at the corner's height - and, in the default model (cube_wall_surface = 0), the HORIZONTAL normal at every height: a corner on the cone (a lifted or
+     * tumbling cube at the boundary: 0.007 % of the env-steps of the bench workload) is stopped radially and gets no vertical impulse where the surface
+     * normal would give (s / c) |dv_r| = 0.57 |dv_r| (tests/test_contact_scenarios.py: test_cube_corner_on_the_cone_keeps_the_horizontal_normal,
+     * test_random_actions_rarely_put_...).  With cube_wall_surface = 1 a corner above wall_z[0] gets the fingertip's geometry: normal (c n_h, s), gap
+     * (r(z) - rho) c, friction rows along the horizontal tangent and the up-slope tangent (-s n_h, c).  A cube that lies on the table meets the boundary
+     * with its lower corners, below the first knot, where the two models coincide bit for bit. */
     float wall_r[4], wall_z[4];
     /* materials: PhysX "average" combine of trifinger_env.py:364-365,876-878,914-915,934-936 */
     float mu_finger_cube, mu_cube_floor, mu_tip_floor, mu_cube_wall, mu_tip_wall, mu_finger_finger;
@@ -249,6 +254,12 @@ typedef struct TfModel {
      * middle-distal pair 1.4 % of the time, in a distal pair 1.7 %).  API 8: tf_default_model sets 1 - the reference's contact set is the default;
      * 0 = the three distal pairs only (`native.ff_middle_pairs: false`, the faster step of API 7).  Cost: INTEGRATION.md. */
     int32_t ff_middle_pairs;
+    /* API 9.  Boundary normal of the cube corners: 0 = horizontal at every height (the default, see wall_r above), 1 = the surface normal of the
+     * flared part for a corner above wall_z[0] (rows: TF_S_LAM_CW).  Built into the 256-register kernels of the cube with and without the extended
+     * domain randomisation only: with the switch on, TF_KERNEL_AUTO picks TF_KERNEL_WIDE_HELPERS up to TF_HELPERS_MAX_ENVS envs and TF_KERNEL_WIDE
+     * above; TF_KERNEL_NARROW, the general box (box != 0) and developer builds answer TF_ERR_UNSUPPORTED; other values: TF_ERR_INVALID_ARG.
+     * The oracle does not model it (tf_default_model leaves it 0).  Cost: DESIGN.md 8. */
+    int32_t cube_wall_surface;
 } TfModel;
 
 /* Fill the box fields of `m` for an object of `size` (x, y, z, metres) and `density` (kg/m^3): mass, principal moments,
@@ -364,7 +375,8 @@ enum { TF_KERNEL_AUTO = 0, TF_KERNEL_NARROW = 1, TF_KERNEL_WIDE = 2, TF_KERNEL_W
 /* TF_KERNEL_WIDE_HELPERS (API 8, additive): the 256-register instantiation in workgroups of EIGHT wavefronts - three helper wavefronts build
  * the middle-distal finger-finger rows (TfModel.ff_middle_pairs) beside the finger wavefronts' contact generation, in the second wavefront slot a CU
  * that holds one workgroup leaves empty -, a fourth runs the distal finger-finger pass in the cube wavefront's place.  Same arithmetic, identical results.
- * TF_KERNEL_AUTO picks it for num_envs <= TF_HELPERS_MAX_ENVS. */
+ * TF_KERNEL_AUTO picks it for num_envs <= TF_HELPERS_MAX_ENVS.  With TfModel.cube_wall_surface on, only the 256-register instantiations exist:
+ * TF_KERNEL_AUTO picks TF_KERNEL_WIDE above TF_HELPERS_MAX_ENVS too, and TF_KERNEL_NARROW is TF_ERR_UNSUPPORTED. */
 #define TF_HELPERS_MAX_ENVS 16384
 int tf_set_kernel_variant(tf_handle h, int32_t variant);
 int tf_kernel_variant(tf_handle h);

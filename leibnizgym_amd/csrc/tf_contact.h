@@ -21,7 +21,7 @@ DEV float solve_tangent(float& lam, float Dinv, float vrel, float lim) {
 // A contact slot is LIVE (gets rows) when its gap is inside the broad margin and can close within this substep at the approach
 // speed of the free velocities, plus a slack for what other impulses may add.  Everything a dead slot would do is skipped:
 // the rows sit behind per-lane branches, so a wavefront with no live lane for a slot jumps over them.
-DEV bool contact_live(const TfModel& m, float gap, float vn0, float h) {
+DEV bool contact_live(const DevModel& m, float gap, float vn0, float h) {
     return (gap < m.contact_margin) && (gap < FMA(h, f_max(-vn0, 0.0f), m.contact_slack));
 }
 
@@ -179,7 +179,7 @@ DEV void seg_seg_s(const float p1[3], const float q1[3], const float p2[3], cons
 // inner radius of the boundary at height z: the piecewise-linear profile through the knots (wall_z[i], wall_r[i]) - a vertical ring below
 // the first knot, the flaring cone of the stage above it (slopes wall_s precomputed at tf_create), nothing above the last knot (1e3)
 DEV float wall_radius_at(const DevParams& P, float z) {
-    const TfModel& m = P.m;
+    const DevModel& m = P.m;
     float r = m.wall_r[0];
     r = (z > m.wall_z[0]) ? FMA(z - m.wall_z[0], P.wall_s[0], m.wall_r[0]) : r;
     r = (z > m.wall_z[1]) ? FMA(z - m.wall_z[1], P.wall_s[1], m.wall_r[1]) : r;
@@ -191,9 +191,10 @@ DEV float wall_radius_at(const DevParams& P, float z) {
 // the same with the TILT of the surface at that height: (c, sn) = (cos, sin) of the slope angle of the profile segment, (1, 0) on the vertical ring.
 // The inward surface normal is (c n_h, sn) with n_h the inward horizontal unit vector (the stage is a bowl: above 32 mm its wall leans outward by
 // 29-35 degrees, high_table_boundary.urdf:20-259); the distance of a point at radius rho to the surface is (r(z) - rho) c.  Used by the fingertip -
-// boundary contact; the cube corners keep the horizontal normal (their tilted rows cost the cube wavefront 5 us: DESIGN.md section 4).
+// boundary contact, and by the cube corners of the instantiations with TfModel.cube_wall_surface on (surface_rows below); the default model keeps the
+// horizontal normal for the cube corners (their tilted rows cost the 128-register cube wavefront 5 us: DESIGN.md section 4).
 DEV float wall_profile(const DevParams& P, float z, float& c, float& sn) {
-    const TfModel& m = P.m;
+    const DevModel& m = P.m;
     const bool b0 = z > m.wall_z[0], b1 = z > m.wall_z[1], b2 = z > m.wall_z[2];
     float r = m.wall_r[0];
     c = 1.0f; sn = 0.0f;
@@ -262,6 +263,18 @@ DEV void cy_apply(const float r[3], float dl, float inv_m, float inv_I, float v[
     w[0] = FMA(-r[2], q, w[0]);
     w[2] = FMA(r[0], q, w[2]);
 }
+// Boundary rows of a cube corner above wall_z[0] with the SURFACE normal (TfModel.cube_wall_surface; the oracle has none of it - the default model
+// keeps the ring's rows below at every height): with n_h = (n0, n1) the inward horizontal unit vector and (c, sn) the tilt of the profile segment there
+// (wall_profile), the directions are N = (c n_h, sn), the horizontal tangent T = (-n1, n0, 0) and the up-slope tangent U = (-sn n_h, c) = N x T;
+// d[3 k..] direction, a[3 k..] arm r x d of row k.  General rows: g_vrel / g_apply (scalar), pk_row_vel / pk_row_apply (packed, rec[j] = (d_j, a_j)).
+DEV void surface_rows(const float r[3], const float n[2], float c, float sn, float d[9], float a[9]) {
+    d[0] = c * n[0]; d[1] = c * n[1]; d[2] = sn;
+    d[3] = -n[1]; d[4] = n[0]; d[5] = 0.0f;
+    d[6] = -(sn * n[0]); d[7] = -(sn * n[1]); d[8] = c;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) cross3(r, &d[3 * k], &a[3 * k]);
+}
+
 // wall rows: inward horizontal normal n = (n0, n1, 0) and tangent t = (-n1, n0, 0)
 DEV void wall_arm_n(const float r[3], const float n[2], float a[3]) {
     a[0] = -(r[2] * n[1]);
@@ -312,6 +325,12 @@ DEV void pk_row_apply_neg(const float2v rec[3], float dl, float2v mI, Twist& t) 
     const float2v s = pk_splat(dl) * mI;
 #pragma unroll
     for (int j = 0; j < 3; ++j) t.p[j] = pk_fma(-rec[j], s, t.p[j]);
+}
+// v += dir dl / m, w += rxd dl / I
+DEV void pk_row_apply(const float2v rec[3], float dl, float2v mI, Twist& t) {
+    const float2v s = pk_splat(dl) * mI;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) t.p[j] = pk_fma(rec[j], s, t.p[j]);
 }
 DEV float cz_vrel(const float r[3], const Twist& t) { return FMA(r[1], t.p[0].y, FMA(-r[0], t.p[1].y, t.p[2].x)); }
 DEV void cz_apply(const float r[3], float dl, float2v mI, Twist& t) {

@@ -8,7 +8,78 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <stddef.h>
+
 #include "../../include/trifinger.h"
+
+// The model as the kernels read it: TfModel of API 8, field for field.  TfModel (API 9) appends cube_wall_surface, a switch that picks an
+// instantiation on the host and that no kernel reads; the parameter block (tf_params.h: DevParams) embeds this mirror instead, so that its layout
+// - and the code of every kernel of the default model - stays what it was.  tf_create copies the leading sizeof(DevModel) bytes of the TfModel.
+struct DevModel {
+    float base_height;
+    float base_yaw_cos[3];
+    float base_yaw_sin[3];
+    float base_half_yaw_cos[3];
+    float base_half_yaw_sin[3];
+    float j2_origin[3];
+    float j3_origin[3];
+    float tip_origin[3];
+    float link_mass[3];
+    float link_com[3][3];
+    float link_inertia[3][6];
+    float q_lo[3], q_hi[3];
+    float qd_max;
+    float tau_max;
+    float link_angular_damping;
+    float q_default[3];
+    float cap_a[3], cap_b[3];
+    float cap_radius;
+    TfLinkShape shape3; TfSphere sph3[1];
+    TfLinkShape shape2; TfSphere sph2[2];
+    TfLinkShape shape1;
+    float upper_check_z;
+    float middle_check_z;
+    float cube_half;
+    float cube_mass;
+    float cube_inertia;
+    float cube_linear_damping, cube_angular_damping;
+    float wall_r[4], wall_z[4];
+    float mu_finger_cube, mu_cube_floor, mu_tip_floor, mu_cube_wall, mu_tip_wall, mu_finger_finger;
+    float mu_robot, mu_object, mu_floor, mu_stage;
+    float restitution_finger;
+    float restitution_ff;
+    float bounce_threshold;
+    float contact_margin;
+    float contact_slack;
+    float contact_offset;
+    float erp;
+    float max_depenetration_velocity;
+    float warm_start;
+    int32_t box;
+    int32_t box_gyroscopic;
+    float box_half[3];
+    float box_inertia[3];
+    float obj_radius_3d;
+    float obj_max_com_dist;
+    float obj_min_height;
+    float obj_span_min_height;
+    float obj_span_radius;
+    int32_t ff_middle_pairs;
+};
+static_assert(sizeof(DevModel) == offsetof(TfModel, cube_wall_surface), "DevModel: TfModel without cube_wall_surface");
+#define TF_DEVMODEL_SAME_OFFSET(f) static_assert(offsetof(DevModel, f) == offsetof(TfModel, f), "DevModel." #f ": offset of TfModel." #f)
+TF_DEVMODEL_SAME_OFFSET(base_height); TF_DEVMODEL_SAME_OFFSET(base_yaw_cos); TF_DEVMODEL_SAME_OFFSET(base_yaw_sin); TF_DEVMODEL_SAME_OFFSET(base_half_yaw_cos); TF_DEVMODEL_SAME_OFFSET(base_half_yaw_sin); TF_DEVMODEL_SAME_OFFSET(j2_origin);
+TF_DEVMODEL_SAME_OFFSET(j3_origin); TF_DEVMODEL_SAME_OFFSET(tip_origin); TF_DEVMODEL_SAME_OFFSET(link_mass); TF_DEVMODEL_SAME_OFFSET(link_com); TF_DEVMODEL_SAME_OFFSET(link_inertia); TF_DEVMODEL_SAME_OFFSET(q_lo);
+TF_DEVMODEL_SAME_OFFSET(q_hi); TF_DEVMODEL_SAME_OFFSET(qd_max); TF_DEVMODEL_SAME_OFFSET(tau_max); TF_DEVMODEL_SAME_OFFSET(link_angular_damping); TF_DEVMODEL_SAME_OFFSET(q_default); TF_DEVMODEL_SAME_OFFSET(cap_a);
+TF_DEVMODEL_SAME_OFFSET(cap_b); TF_DEVMODEL_SAME_OFFSET(cap_radius); TF_DEVMODEL_SAME_OFFSET(shape3); TF_DEVMODEL_SAME_OFFSET(sph3); TF_DEVMODEL_SAME_OFFSET(shape2); TF_DEVMODEL_SAME_OFFSET(sph2);
+TF_DEVMODEL_SAME_OFFSET(shape1); TF_DEVMODEL_SAME_OFFSET(upper_check_z); TF_DEVMODEL_SAME_OFFSET(middle_check_z); TF_DEVMODEL_SAME_OFFSET(cube_half); TF_DEVMODEL_SAME_OFFSET(cube_mass); TF_DEVMODEL_SAME_OFFSET(cube_inertia);
+TF_DEVMODEL_SAME_OFFSET(cube_linear_damping); TF_DEVMODEL_SAME_OFFSET(cube_angular_damping); TF_DEVMODEL_SAME_OFFSET(wall_r); TF_DEVMODEL_SAME_OFFSET(wall_z); TF_DEVMODEL_SAME_OFFSET(mu_finger_cube); TF_DEVMODEL_SAME_OFFSET(mu_cube_floor);
+TF_DEVMODEL_SAME_OFFSET(mu_tip_floor); TF_DEVMODEL_SAME_OFFSET(mu_cube_wall); TF_DEVMODEL_SAME_OFFSET(mu_tip_wall); TF_DEVMODEL_SAME_OFFSET(mu_finger_finger); TF_DEVMODEL_SAME_OFFSET(mu_robot); TF_DEVMODEL_SAME_OFFSET(mu_object);
+TF_DEVMODEL_SAME_OFFSET(mu_floor); TF_DEVMODEL_SAME_OFFSET(mu_stage); TF_DEVMODEL_SAME_OFFSET(restitution_finger); TF_DEVMODEL_SAME_OFFSET(restitution_ff); TF_DEVMODEL_SAME_OFFSET(bounce_threshold); TF_DEVMODEL_SAME_OFFSET(contact_margin);
+TF_DEVMODEL_SAME_OFFSET(contact_slack); TF_DEVMODEL_SAME_OFFSET(contact_offset); TF_DEVMODEL_SAME_OFFSET(erp); TF_DEVMODEL_SAME_OFFSET(max_depenetration_velocity); TF_DEVMODEL_SAME_OFFSET(warm_start); TF_DEVMODEL_SAME_OFFSET(box);
+TF_DEVMODEL_SAME_OFFSET(box_gyroscopic); TF_DEVMODEL_SAME_OFFSET(box_half); TF_DEVMODEL_SAME_OFFSET(box_inertia); TF_DEVMODEL_SAME_OFFSET(obj_radius_3d); TF_DEVMODEL_SAME_OFFSET(obj_max_com_dist); TF_DEVMODEL_SAME_OFFSET(obj_min_height);
+TF_DEVMODEL_SAME_OFFSET(obj_span_min_height); TF_DEVMODEL_SAME_OFFSET(obj_span_radius); TF_DEVMODEL_SAME_OFFSET(ff_middle_pairs);
+#undef TF_DEVMODEL_SAME_OFFSET
 
 #define DEV __device__ __forceinline__
 
@@ -251,7 +322,7 @@ template <int LINK> DEV void rot_link_T(const FK& k, const float v[3], float o[3
     o[0] = wx; o[1] = wy; o[2] = wz;
 }
 
-DEV void fk_setup(const TfModel& m, const float q[3], FK& k) {
+DEV void fk_setup(const DevModel& m, const float q[3], FK& k) {
     tf_sincos(q[0], k.s1, k.c1);
     tf_sincos(q[1], k.s2, k.c2);
     tf_sincos(q[1] + q[2], k.s23, k.c23);
@@ -277,7 +348,7 @@ DEV void levers(const FK& k, const float P[3], float L1[3], float L2[3], float L
 // hence  dw x r + w x (w x r) = (w (2 a r_y - w r_x), -a^2 r_y, -(a^2 + w^2) r_z).  Only the components that reach
 // the three joint torques (n1_y, n2_x, n3_x) are formed.  tests/test_physics_analytic.py checks M against the fp64
 // kinetic energy and h against the Lagrangian derivatives of an independent model.
-DEV void finger_dynamics(const TfModel& m, const FK& k, const float qd[3], const float grav[3], float M[6], float bias[3]) {
+DEV void finger_dynamics(const DevModel& m, const FK& k, const float qd[3], const float grav[3], float M[6], float bias[3]) {
     const float m1 = m.link_mass[0], m2 = m.link_mass[1], m3 = m.link_mass[2];
     const float* I1 = m.link_inertia[0];
     const float* I2 = m.link_inertia[1];
@@ -436,7 +507,7 @@ DEV void tangent_basis(const float n[3], float t1[3], float t2[3]) {
     cross3(n, t1, t2);
 }
 
-DEV float contact_bias(const TfModel& m, float gap, float vn0, float inv_h, float restitution) {
+DEV float contact_bias(const DevModel& m, float gap, float vn0, float inv_h, float restitution) {
     float b;
     if (gap >= 0.0f) b = gap * inv_h;
     else b = f_max(m.erp * gap * inv_h, -m.max_depenetration_velocity);

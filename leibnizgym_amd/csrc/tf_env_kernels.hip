@@ -1,6 +1,6 @@
 // tf_env_kernels.hip - the fused TriFinger step kernel (roles: tf_roles.h) and its launcher for ONE (EXT, WIDE) pair.
 //
-// Compiled nine times (Makefile: -DTF_EXT=0|1|2 -DTF_WIDE=0|1, and -DTF_EXT=0|1|2 -DTF_WIDE=2): EXT 0 the headline kernels, 1 the extended domain
+// Compiled nine times, plus four with -DTF_SURF=1 (below) (Makefile: -DTF_EXT=0|1|2 -DTF_WIDE=0|1, and -DTF_EXT=0|1|2 -DTF_WIDE=2): EXT 0 the headline kernels, 1 the extended domain
 // randomisation, 2 the general box object; WIDE 0 the 128-register instantiation (four workgroups per CU), 1 the 256-register one for populations of at
 // most 32768 envs, 2 the 256-register one with four helper wavefronts per workgroup (one workgroup per CU: at most 16384 envs; the launches that
 // simulate only - the others are served by the WIDE = 1 unit).
@@ -13,6 +13,19 @@
 #ifndef TF_EXT
 #error "compile with -DTF_EXT=0|1|2 -DTF_WIDE=0|1|2"
 #endif
+// -DTF_SURF=1: the instantiations with the surface normal of the cube corners on the flared part of the boundary (TfModel.cube_wall_surface; EXT 0 and 1,
+// WIDE 1 and 2 only).  Their kernel (k_env_surf), launcher and occupancy query have names of their own; they carry the launches that simulate.
+#ifndef TF_SURF
+#define TF_SURF 0
+#endif
+#if TF_SURF
+#if TF_EXT == 2 || TF_WIDE == 0
+#error "TF_SURF: the 256-register cube kernels only (-DTF_EXT=0|1 -DTF_WIDE=1|2)"
+#endif
+#define K_ENV k_env_surf
+#else
+#define K_ENV k_env
+#endif
 
 // One launch = one or more hooks of the reference step (MODE) for every env of the handle.
 // WIDE = false: 128 registers, 4 workgroups per CU (4 wavefronts per SIMD) - populations that fill the chip; WIDE = true: 256 registers, no spills,
@@ -21,8 +34,8 @@
 // HELP: the WIDE kernel in workgroups of eight wavefronts - 0..2 fingers, 3 cube, 4..7 helpers (tf_roles.h: helper_role) - for populations that leave a CU to
 // one workgroup: the second wavefront slot of every SIMD, empty otherwise, carries the finger-finger rows (middle-distal: 4..6, distal pass: 7).  Same arithmetic again.
 template <int A, bool IS_RESET, bool ASYM, int MODE, int EXT, bool WIDE, bool HELP = false>
-__global__ void __launch_bounds__(HELP ? NT_HELP : NT, HELP ? 1 : (WIDE ? 2 : 4)) k_env(const DevParams* __restrict__ Pp, const StepArgs sa, const float* __restrict__ action) {
-    __shared__ __attribute__((aligned(16))) float lds[((EXT == 2) ? (WIDE ? LDS_SLOTS_BOX_WIDE : LDS_SLOTS_BOX) : (HELP ? LDS_SLOTS_HELP : LDS_SLOTS)) * WAVE];
+__global__ void __launch_bounds__(HELP ? NT_HELP : NT, HELP ? 1 : (WIDE ? 2 : 4)) K_ENV(const DevParams* __restrict__ Pp, const StepArgs sa, const float* __restrict__ action) {
+    __shared__ __attribute__((aligned(16))) float lds[(TF_SURF ? LDS_SLOTS_SURF : (EXT == 2) ? (WIDE ? LDS_SLOTS_BOX_WIDE : LDS_SLOTS_BOX) : (HELP ? LDS_SLOTS_HELP : LDS_SLOTS)) * WAVE];
     const DevParams& P = *Pp;
     {   // Warm the scalar cache with the parameter block (one dword per 64-byte line) BEFORE the state loads of every workgroup of the
         // launch saturate the L2: the model constants the free motion needs then come out of the constant cache instead of queueing
@@ -51,7 +64,7 @@ __global__ void __launch_bounds__(HELP ? NT_HELP : NT, HELP ? 1 : (WIDE ? 2 : 4)
 #elif defined(TF_ONLY_CUBE)
     cube_role<A, IS_RESET, ASYM, MODE, EXT, WIDE>(P, sa, action, lds, cx);
 #else
-    if (cx.role == 3) cube_role<A, IS_RESET, ASYM, MODE, EXT, WIDE, HELP>(P, sa, action, lds, cx);
+    if (cx.role == 3) cube_role<A, IS_RESET, ASYM, MODE, EXT, WIDE, HELP, TF_SURF != 0>(P, sa, action, lds, cx);
     else if (HELP && cx.role > 3) helper_role<ASYM, MODE, EXT>(P, sa, lds, cx);
     else finger_role<A, IS_RESET, ASYM, MODE, EXT, WIDE, HELP>(P, sa, action, lds, cx);
 #endif
@@ -64,26 +77,33 @@ static void go(const EnvLaunch& a) {
     constexpr bool WIDE = TF_WIDE != 0, HELP = TF_WIDE == 2;
     dim3 grid(a.grid), block(HELP ? NT_HELP : NT);
     if (a.action_dim == 9) {
-        if (a.asym) hipLaunchKernelGGL((k_env<9, IS_RESET, true, MODE, EXT, WIDE, HELP>), grid, block, 0, a.stream, a.d_params, a.sa, a.action);
-        else hipLaunchKernelGGL((k_env<9, IS_RESET, false, MODE, EXT, WIDE, HELP>), grid, block, 0, a.stream, a.d_params, a.sa, a.action);
+        if (a.asym) hipLaunchKernelGGL((K_ENV<9, IS_RESET, true, MODE, EXT, WIDE, HELP>), grid, block, 0, a.stream, a.d_params, a.sa, a.action);
+        else hipLaunchKernelGGL((K_ENV<9, IS_RESET, false, MODE, EXT, WIDE, HELP>), grid, block, 0, a.stream, a.d_params, a.sa, a.action);
     } else {
 #if !defined(TF_DEV_MIN)
-        if (a.asym) hipLaunchKernelGGL((k_env<18, IS_RESET, true, MODE, EXT, WIDE, HELP>), grid, block, 0, a.stream, a.d_params, a.sa, a.action);
-        else hipLaunchKernelGGL((k_env<18, IS_RESET, false, MODE, EXT, WIDE, HELP>), grid, block, 0, a.stream, a.d_params, a.sa, a.action);
+        if (a.asym) hipLaunchKernelGGL((K_ENV<18, IS_RESET, true, MODE, EXT, WIDE, HELP>), grid, block, 0, a.stream, a.d_params, a.sa, a.action);
+        else hipLaunchKernelGGL((K_ENV<18, IS_RESET, false, MODE, EXT, WIDE, HELP>), grid, block, 0, a.stream, a.d_params, a.sa, a.action);
 #endif
     }
 }
 
 #define TF_CAT3_(a, b, c) a##b##_##c
 #define TF_CAT3(a, b, c) TF_CAT3_(a, b, c)
-void TF_CAT3(tf_launch_env_, TF_EXT, TF_WIDE)(int lm, const EnvLaunch& a) {
+#if TF_SURF
+#define TF_LAUNCH_PREFIX tf_launch_env_surf_
+#define TF_OCC_PREFIX tf_occupancy_env_surf_
+#else
+#define TF_LAUNCH_PREFIX tf_launch_env_
+#define TF_OCC_PREFIX tf_occupancy_env_
+#endif
+void TF_CAT3(TF_LAUNCH_PREFIX, TF_EXT, TF_WIDE)(int lm, const EnvLaunch& a) {
     switch (lm) {
     case TF_LM_STEP: go<M_FUSED_STEP, false>(a); break;
     case TF_LM_STEP_RAND: go<M_FUSED_STEP_RAND, false>(a); break;
     case TF_LM_RESET: go<M_FUSED_RESET, true>(a); break;
 #if !defined(TF_DEV_MIN)      // developer builds carry the fused launches only
     case TF_LM_SIM: go<M_SIM, false>(a); break;
-#if TF_WIDE != 2              // (the helper unit carries the launches that simulate; the host sends the others to the WIDE = 1 unit)
+#if TF_WIDE != 2 && !TF_SURF   // (the helper and surface units carry the launches that simulate; the host sends the others to the WIDE = 1 unit)
     case TF_LM_RESETS: go<M_RESETS, false>(a); break;
     case TF_LM_TORQUE: go<M_TORQUE, false>(a); break;
     case TF_LM_POST: go<M_POST, false>(a); break;
@@ -94,18 +114,18 @@ void TF_CAT3(tf_launch_env_, TF_EXT, TF_WIDE)(int lm, const EnvLaunch& a) {
     }
 }
 
-int TF_CAT3(tf_occupancy_env_, TF_EXT, TF_WIDE)(int action_dim, bool asym) {
+int TF_CAT3(TF_OCC_PREFIX, TF_EXT, TF_WIDE)(int action_dim, bool asym) {
     constexpr int EXT = TF_EXT;
     constexpr bool WIDE = TF_WIDE != 0, HELP = TF_WIDE == 2;
     int n = -1;
     hipError_t e = hipSuccess;
     if (action_dim == 9) {
-        if (asym) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_env<9, false, true, M_FUSED_STEP_RAND, EXT, WIDE, HELP>, HELP ? NT_HELP : NT, 0);
-        else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_env<9, false, false, M_FUSED_STEP_RAND, EXT, WIDE, HELP>, HELP ? NT_HELP : NT, 0);
+        if (asym) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, K_ENV<9, false, true, M_FUSED_STEP_RAND, EXT, WIDE, HELP>, HELP ? NT_HELP : NT, 0);
+        else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, K_ENV<9, false, false, M_FUSED_STEP_RAND, EXT, WIDE, HELP>, HELP ? NT_HELP : NT, 0);
     } else {
 #if !defined(TF_DEV_MIN)
-        if (asym) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_env<18, false, true, M_FUSED_STEP_RAND, EXT, WIDE, HELP>, HELP ? NT_HELP : NT, 0);
-        else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_env<18, false, false, M_FUSED_STEP_RAND, EXT, WIDE, HELP>, HELP ? NT_HELP : NT, 0);
+        if (asym) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, K_ENV<18, false, true, M_FUSED_STEP_RAND, EXT, WIDE, HELP>, HELP ? NT_HELP : NT, 0);
+        else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, K_ENV<18, false, false, M_FUSED_STEP_RAND, EXT, WIDE, HELP>, HELP ? NT_HELP : NT, 0);
 #endif
     }
     return e == hipSuccess ? n : -1;

@@ -41,3 +41,13 @@ void tf_launch_env_2_1(int lm, const EnvLaunch& a);
 void tf_launch_env_0_2(int lm, const EnvLaunch& a);
 void tf_launch_env_1_2(int lm, const EnvLaunch& a);
 void tf_launch_env_2_2(int lm, const EnvLaunch& a);
+// the same with the surface normal of the cube corners (TfModel.cube_wall_surface, -DTF_SURF=1): the 256-register cube kernels, the launches that
+// simulate (TF_LM_STEP, _STEP_RAND, _RESET, _SIM)
+int tf_occupancy_env_surf_0_1(int action_dim, bool asym);
+int tf_occupancy_env_surf_1_1(int action_dim, bool asym);
+int tf_occupancy_env_surf_0_2(int action_dim, bool asym);
+int tf_occupancy_env_surf_1_2(int action_dim, bool asym);
+void tf_launch_env_surf_0_1(int lm, const EnvLaunch& a);
+void tf_launch_env_surf_1_1(int lm, const EnvLaunch& a);
+void tf_launch_env_surf_0_2(int lm, const EnvLaunch& a);
+void tf_launch_env_surf_1_2(int lm, const EnvLaunch& a);

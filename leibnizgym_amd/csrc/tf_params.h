@@ -72,7 +72,7 @@ struct DevParams {
     int32_t substeps, iters, inner, control_decimation;      // iters = solver_iterations x solver_inner passes; the finger-only rows run on every inner-th
     float dt, hsub;
     float grav[3];
-    TfModel m;
+    DevModel m;              // the model without its host-side selection switch (tf_device_math.h: DevModel)
     float wall_s[3];         // slopes of the boundary profile between its knots: (wall_r[i+1] - wall_r[i]) / (wall_z[i+1] - wall_z[i])
     float wall_c[3], wall_sn[3];   // cos and sin of the slope angle of each segment: 1 / sqrt(1 + s^2), s / sqrt(1 + s^2) (fingertip - boundary contact)
     // obs/states offset and 1/range tables, action limits, PD gains (index = TAB_*).  Embedded so that every access

@@ -83,6 +83,11 @@ DEV constexpr int ffm_own_mbox(int fm, int k) { return L_HELP_OWN + 6 * fm + k; 
 #define L_POSE_S 150                    //   6: box kernels only: S = R diag(sqrt(I_ref / I_k)) R^T (00 01 02 11 12 22), published by the cube role
 #define LDS_SLOTS_BOX 159
 #define LDS_SLOTS_BOX_WIDE 198             //   256-register box kernels (at most two workgroups per CU): + helper slots 159..179, mailboxes 180..197
+// The instantiations with the surface normal of the cube corners (TfModel.cube_wall_surface: the 256-register cube kernels, EXT 0 and 1, with and
+// without helpers): the rows of a corner above wall_z[0] are general rows, kept in slots of their own through the sweeps (their impulses stay in
+// L_WALL + 12 c + 9.., the warm-start rows of the corner slot; the ring rows of that slot are dead for the lane).  2 x 268 x 256 B = 134 KB per CU.
+#define L_CONE 180                      //  88: corner c at 22 c: direction and arm of N, T, U (6 each: tf_contact.h surface_rows), Dinv[3], bias
+#define LDS_SLOTS_SURF 268
 // post phase (aliases the above)
 #define L_XCH (MAX_STATES)              //  18: fingertip position (3) and previous fingertip position (3) of finger f at 6 f
 #define L_NAN (MAX_STATES + 18)         //   4: non-finite flag of each role
@@ -356,7 +361,7 @@ DEV float norm_p3(const float a[3], const float b[3], int p) {
 }
 
 // fingertip link state in the world frame: position, quaternion (xyzw), linear and angular velocity
-DEV void tip_state(const TfModel& m, const Yaw& y, const FK& k, const float q[3], const float qd[3], float out[13]) {
+DEV void tip_state(const DevModel& m, const Yaw& y, const FK& k, const float q[3], const float qd[3], float out[13]) {
     float To[3];
     link_point<3>(k, m.tip_origin, To);
     base_to_world(y, To, &out[0]);
@@ -405,7 +410,7 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
     // WIDE: the 256-register instantiation (2 wavefronts per SIMD) launched for populations that never put more than two workgroups on a
     // CU (num_envs <= 32768): nothing is parked in LDS or re-read from the state rows between substeps.  Same arithmetic, bit for bit.
     constexpr bool BOXK = X == 2;
-    const TfModel& m = P.m;
+    const DevModel& m = P.m;
     const int f = cx.role, lane = cx.lane;
     constexpr int OD = TF_OBS_DIM_BASE + A, SD = OD + TF_STATES_EXTRA;
     constexpr int TW = ASYM ? SD : OD;                 // width of the tile staged in LDS in the post phase
@@ -1391,7 +1396,7 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
 template <bool ASYM, int MODE, int X>
 DEV void helper_role(const DevParams& P, const StepArgs& sa, float* lds, const Ctx& cx) {
     constexpr bool BOXK = X == 2;
-    const TfModel& m = P.m;
+    const DevModel& m = P.m;
     const int lane = cx.lane;
     const int fm = cx.role - 4;
     BAR();                                                      // #1
@@ -1672,6 +1677,14 @@ DEV void stats_zero(LaneStats& st) {
 }
 
 
+// a general row of the cube whose record (direction[3], arm[3]) sits in LDS at slot `rb` (the surface rows of L_CONE): pk_row_vel / pk_row_apply
+DEV void ld_row(const float* lds, int lane, int rb, float2v rec[3]) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { rec[j].x = LD(rb + j); rec[j].y = LD(rb + 3 + j); }
+}
+DEV float pk_row_vel_lds(const float* lds, int lane, int rb, const Twist& t) { float2v rec[3]; ld_row(lds, lane, rb, rec); return pk_row_vel(rec, t); }
+DEV void pk_row_apply_lds(const float* lds, int lane, int rb, float dl, float2v mI, Twist& t) { float2v rec[3]; ld_row(lds, lane, rb, rec); pk_row_apply(rec, dl, mI, t); }
+
 // arms of the three rows of a wall corner: r x n, r x t and (box only) r x z, inertia-scaled for a box (S from LDS)
 DEV void wall_arms(bool box, const float* lds, int lane, const float r[3], const float n[2], float a[3], float b[3], float c3[3]) {
     wall_arm_n(r, n, a);
@@ -1688,11 +1701,12 @@ DEV void wall_arms(bool box, const float* lds, int lane, const float r[3], const
     }
 }
 
-template <int A, bool IS_RESET, bool ASYM, int MODE, int X, bool WIDE, bool HELP = false>
+template <int A, bool IS_RESET, bool ASYM, int MODE, int X, bool WIDE, bool HELP = false, bool SURF = false>
 DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restrict__ action, float* lds, const Ctx& cx) {
     constexpr bool EXT = X != 0;
     constexpr bool BOXK = X == 2;
-    const TfModel& m = P.m;
+    static_assert(!SURF || (WIDE && !BOXK), "the surface normal of the cube corners is built into the 256-register cube kernels only");
+    const DevModel& m = P.m;
     const int lane = cx.lane;
     constexpr int OD = TF_OBS_DIM_BASE + A, SD = OD + TF_STATES_EXTRA;
     constexpr int TW = ASYM ? SD : OD;
@@ -1925,6 +1939,7 @@ DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restri
             }
             bool wall_lane = false;
             bool slot_any[4] = {false, false, false, false};     // wave-uniform: a lane of this wavefront has a live corner in slot c
+            unsigned cone_any = 0u;                             // SURF, wave-uniform: bit c - ... a live corner above the vertical ring (rows in L_CONE)
             // WIDE (cube kernels): the rows of corner slots 0 and 1 stay in registers through the sweeps - normal, arms, 1/D, bias, impulses; LDS only
             // keeps their impulses between substeps (slots 2 and 3, practically never live, go through LDS as in the 128-register build)
             constexpr bool WREG = WIDE && !BOXK;
@@ -2102,6 +2117,18 @@ DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restri
                     cz_apply(r, LD(wb + 11), mI, tw);
                 }
             }
+            if constexpr (SURF) {                               // corners above the ring: behind the ring's, per lane (a lane without one does nothing)
+                if (__builtin_expect(cone_any != 0u, 0)) {
+#pragma unroll 1
+                    for (int c = 0; c < 4; ++c) {
+                        const int cb = L_CONE + 22 * c, wb = L_WALL + 12 * c;
+                        if (((cone_any >> c) & 1u) && LD(cb + 18) > 0.0f) {
+#pragma unroll 1
+                            for (int d = 0; d < 3; ++d) pk_row_apply_lds(lds, lane, cb + 6 * d, LD(wb + 9 + d), mI, tw);
+                        }
+                    }
+                }
+            }
             uint32_t t_wait = 0u, t_fc = 0u, t_floor = 0u;
             STAMP(sb_ + 9);
             for (int it = 0; it < P.iters; ++it) {
@@ -2195,6 +2222,26 @@ DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restri
 #pragma unroll
                             for (int d = 0; d < 3; ++d) LD(wb + 9 + d) = lam[d];
                         }
+                    }
+                }
+                if constexpr (SURF) {                           // cube - boundary above the ring: rows N (normal), T, U (tf_contact.h: surface_rows)
+                    if (__builtin_expect(cone_any != 0u, 0)) {  // wave-uniform; the records are read row by row (no spills at 256 VGPRs)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        const int cb = L_CONE + 22 * c, wb = L_WALL + 12 * c;
+                        if (((cone_any >> c) & 1u) && LD(cb + 18) > 0.0f) {     // per lane: the other lanes leave their twist untouched
+                            float lim = 0.0f;
+#pragma unroll
+                            for (int d = 0; d < 3; ++d) {
+                                const float vr = pk_row_vel_lds(lds, lane, cb + 6 * d, tw);
+                                float lam = LD(wb + 9 + d);
+                                const float dl = (d == 0) ? solve_normal(lam, LD(cb + 18), vr, LD(cb + 21)) : solve_tangent(lam, LD(cb + 18 + d), vr, lim);
+                                lim = (d == 0) ? mu_cw * lam : lim;
+                                LD(wb + 9 + d) = lam;
+                                pk_row_apply_lds(lds, lane, cb + 6 * d, dl, mI, tw);
+                            }
+                        }
+                    }
                     }
                 }
                 if (last) {                                     // what the finger roles keep: normal impulse, world friction impulse, force (read behind W2)

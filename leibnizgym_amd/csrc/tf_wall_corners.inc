@@ -1,7 +1,8 @@
 // tf_wall_corners.inc - the cube role's boundary-corner block (tf_roles.h includes it at the place the instantiation builds these rows: before S1, or -
 // with helper wavefronts, where another wavefront runs the distal finger-finger pass - between S1 and S1b).  Textual inclusion, as tf_floor_corners.inc.
 // Uses the cube role's locals: R, hc, cp, v, w, h, inv_h, inv_m, inv_I, ws, m, box, soff, cw_face, P, lds, lane; fills wall_lane, slot_any, cw_face, the
-// rows in LDS (L_WALL) and - WREG - w_r, w_n, w_D, w_bias, w_lam, w_a, w_b.
+// rows in LDS (L_WALL) and - WREG - w_r, w_n, w_D, w_bias, w_lam, w_a, w_b; SURF (TfModel.cube_wall_surface): a corner above wall_z[0] gets the rows of
+// the tilted surface instead (L_CONE, cone_any) and its ring rows stay dead.  A corner on the vertical ring takes the same path with or without SURF.
             {   // cube vs boundary wall: the four corners of the face that points outward most; rows go to LDS
                 const float cx_ = EXT ? cp[0] - soff[0] : cp[0], cy_ = EXT ? cp[1] - soff[1] : cp[1];      // relative to the stage centre
                 float rc2 = FMA(cx_, cx_, cy_ * cy_);
@@ -68,9 +69,35 @@
                     float rho2 = FMA(px, px, py * py);
                     float inv = f_rsqrt(f_max(rho2, 1e-24f));
                     float rho = rho2 * inv;
-                    float gap = wall_radius_at(P, pz) - rho;
+                    float gap, wc = 1.0f, wsn = 0.0f;
+                    bool cone = false, cone_live = false;       // SURF: the corner is above the vertical ring / has live rows of the tilted surface
+                    float cone_lam[3] = {0.0f, 0.0f, 0.0f}, cone_D0 = 0.0f;
+                    if constexpr (SURF) {
+                        const float rz = wall_profile(P, pz, wc, wsn);
+                        cone = pz > m.wall_z[0];
+                        gap = cone ? (rz - rho) * wc : rz - rho;     // distance to the tilted surface; on the ring the horizontal gap as below
+                    } else {
+                        gap = wall_radius_at(P, pz) - rho;
+                    }
                     if (__builtin_expect(any && gap < m.contact_margin && rho > 1e-6f, 0)) {
                         float nn[2] = {-px * inv, -py * inv};
+                        if (SURF && cone) {                     // rows N, T, U of the surface (general rows; the slot's ring rows stay dead)
+                            float dd[9], aa[9];
+                            surface_rows(r, nn, wc, wsn, dd, aa);
+                            const float vn0 = g_vrel(&dd[0], &aa[0], v, w);
+                            if (contact_live(m, gap, vn0, h)) {
+                                cone_live = true;
+                                const int cb = L_CONE + 22 * c;
+#pragma unroll
+                                for (int j = 0; j < 9; ++j) { LD(cb + 6 * (j / 3) + j % 3) = dd[j]; LD(cb + 6 * (j / 3) + 3 + j % 3) = aa[j]; }
+                                cone_D0 = f_rcp2(FMA(dot3(&aa[0], &aa[0]), inv_I, inv_m));
+                                LD(cb + 19) = f_rcp2(FMA(dot3(&aa[3], &aa[3]), inv_I, inv_m));
+                                LD(cb + 20) = f_rcp2(FMA(dot3(&aa[6], &aa[6]), inv_I, inv_m));
+                                LD(cb + 21) = contact_bias(m, gap, vn0, inv_h, 0.0f);
+#pragma unroll
+                                for (int d = 0; d < 3; ++d) cone_lam[d] = ((c < 2) ? (((c ^ swap01) == 0) ? lam_old[d] : lam_old[3 + d]) : LD(wb + 9 + d)) * keep;
+                            }
+                        } else {
                         float a[3], b[3], c3[3];
                         wall_arms(box, lds, lane, r, nn, a, b, c3);
                         const float vn0 = wn_vrel(nn, a, v, w);
@@ -83,7 +110,9 @@
 #pragma unroll
                             for (int d = 0; d < 3; ++d) lam[d] = ((c < 2) ? (((c ^ swap01) == 0) ? lam_old[d] : lam_old[3 + d]) : LD(wb + 9 + d)) * keep;
                         }
+                        }
                     }
+                    if constexpr (SURF) LD(L_CONE + 22 * c + 18) = cone_D0;        // 0 unless live: the sweeps test the lane's 1/D of N
                     if (WREG && c < 2) {
 #pragma unroll
                         for (int j = 0; j < 3; ++j) { w_r[3 * c + j] = r[j]; w_D[3 * c + j] = Dinv[j]; w_lam[3 * c + j] = lam[j]; LD(wb + 9 + j) = lam[j]; }
@@ -97,6 +126,14 @@
                     }
                     wall_lane = wall_lane || (Dinv[0] > 0.0f);
                     slot_any[c] = __builtin_amdgcn_ballot_w64(Dinv[0] > 0.0f) != 0ull;
+                    if constexpr (SURF) {
+                        if (cone_live) {
+#pragma unroll
+                            for (int d = 0; d < 3; ++d) LD(wb + 9 + d) = cone_lam[d];     // the impulses live in the corner slot's rows
+                        }
+                        wall_lane = wall_lane || cone_live;
+                        cone_any |= (__builtin_amdgcn_ballot_w64(cone_live) != 0ull) ? (1u << c) : 0u;
+                    }
                 }
                 cw_face = wall_lane ? face : 0.0f;              // 0: no corner touches the boundary (the rows carry nothing)
             }

@@ -341,6 +341,13 @@ int tf_create(const TfConfig* cfg, tf_handle* out) {
         if (!(z - z == 0.0f) || !(r - r == 0.0f) || !(r > 0.0f)) return TF_ERR_INVALID_ARG;
         if (i > 0 && !(z > cfg->model.wall_z[i - 1])) return TF_ERR_INVALID_ARG;
     }
+    /* the surface normal of the cube corners (API 9): 0 or 1; built into the 256-register cube kernels only (not the general box, not the
+     * developer builds) */
+    if (cfg->model.cube_wall_surface != 0 && cfg->model.cube_wall_surface != 1) return TF_ERR_INVALID_ARG;
+#if defined(TF_DEV_MIN)
+    if (cfg->model.cube_wall_surface) return TF_ERR_UNSUPPORTED;
+#endif
+    if (cfg->model.cube_wall_surface && cfg->model.box) return TF_ERR_UNSUPPORTED;
     TfHandle_* h = new TfHandle_();
     memset(h, 0, sizeof(*h));
     h->cfg = *cfg;
@@ -348,7 +355,7 @@ int tf_create(const TfConfig* cfg, tf_handle* out) {
     if (h->cfg.global_num_envs <= 0) h->cfg.global_num_envs = cfg->num_envs;
     h->action_dim = tf_action_dim(cfg->command_mode);
     h->variant = TF_KERNEL_AUTO;
-    h->wide = cfg->num_envs <= TF_WIDE_MAX_ENVS;
+    h->wide = cfg->model.cube_wall_surface || cfg->num_envs <= TF_WIDE_MAX_ENVS;     // with the surface normal: the 256-register kernels at any size
     int od = 0, sd = 0;
     DevParams& P = h->dp;
     build_tables(&h->cfg, h->action_dim, P.tables, &od, &sd);
@@ -380,9 +387,10 @@ int tf_create(const TfConfig* cfg, tf_handle* out) {
     P.substeps = cfg->substeps; P.iters = cfg->solver_iterations * cfg->solver_inner; P.inner = cfg->solver_inner; P.control_decimation = cfg->control_decimation;
     P.dt = cfg->dt; P.hsub = cfg->dt / (float)cfg->substeps;
     for (int i = 0; i < 3; ++i) P.grav[i] = cfg->gravity[i];
-    P.m = cfg->model;
+    memcpy(&P.m, &cfg->model, sizeof(DevModel));      // the model without cube_wall_surface (tf_device_math.h: DevModel)
     for (int i = 0; i < 3; ++i) {
-        const double sl = ((double)P.m.wall_r[i + 1] - (double)P.m.wall_r[i]) / ((double)P.m.wall_z[i + 1] - (double)P.m.wall_z[i]);
+        const TfModel& cm = cfg->model;
+        const double sl = ((double)cm.wall_r[i + 1] - (double)cm.wall_r[i]) / ((double)cm.wall_z[i + 1] - (double)cm.wall_z[i]);
         P.wall_s[i] = (float)sl;
         P.wall_c[i] = (float)(1.0 / sqrt(1.0 + sl * sl));
         P.wall_sn[i] = (float)(sl / sqrt(1.0 + sl * sl));
@@ -458,8 +466,10 @@ static bool use_helpers(const TfHandle_* h) {
 }
 int tf_set_kernel_variant(tf_handle h, int32_t variant) {
     if (!h || variant < TF_KERNEL_AUTO || variant > TF_KERNEL_WIDE_HELPERS) return TF_ERR_INVALID_ARG;
+    const bool surf = h->cfg.model.cube_wall_surface != 0;
+    if (surf && variant == TF_KERNEL_NARROW) return TF_ERR_UNSUPPORTED;      // no 128-register kernel with the surface normal of the cube corners
     h->variant = variant;
-    h->wide = (variant == TF_KERNEL_AUTO) ? (h->cfg.num_envs <= TF_WIDE_MAX_ENVS) : (variant != TF_KERNEL_NARROW);
+    h->wide = (variant == TF_KERNEL_AUTO) ? (surf || h->cfg.num_envs <= TF_WIDE_MAX_ENVS) : (variant != TF_KERNEL_NARROW);
     return TF_OK;
 }
 int tf_kernel_variant(tf_handle h) { return h ? (h->wide ? (use_helpers(h) ? TF_KERNEL_WIDE_HELPERS : TF_KERNEL_WIDE) : TF_KERNEL_NARROW) : TF_ERR_INVALID_ARG; }
@@ -472,6 +482,10 @@ int tf_kernel_occupancy(tf_handle h) {
     return h->wide ? tf_occupancy_env_0_1(h->action_dim, asym) : tf_occupancy_env_0_0(h->action_dim, asym);
 #else
     const int k = ext_kind(h->cfg);
+    if (h->cfg.model.cube_wall_surface) {
+        if (help) return k == 1 ? tf_occupancy_env_surf_1_2(h->action_dim, asym) : tf_occupancy_env_surf_0_2(h->action_dim, asym);
+        return k == 1 ? tf_occupancy_env_surf_1_1(h->action_dim, asym) : tf_occupancy_env_surf_0_1(h->action_dim, asym);
+    }
     if (help) return k == 2 ? tf_occupancy_env_2_2(h->action_dim, asym) : (k == 1 ? tf_occupancy_env_1_2(h->action_dim, asym) : tf_occupancy_env_0_2(h->action_dim, asym));
     if (k == 2) return h->wide ? tf_occupancy_env_2_1(h->action_dim, asym) : tf_occupancy_env_2_0(h->action_dim, asym);
     if (k == 1) return h->wide ? tf_occupancy_env_1_1(h->action_dim, asym) : tf_occupancy_env_1_0(h->action_dim, asym);
@@ -544,11 +558,17 @@ static void launch_env(TfHandle_* h, int lm, const float* action, hipStream_t s)
     a.grid = (unsigned)n_waves(h); a.action_dim = h->action_dim; a.asym = h->cfg.asymmetric_obs != 0;
     a.d_params = h->d_params; a.sa = h->sa; a.action = action; a.stream = s;
     // the helper units carry the launches that simulate; a launch of one of the other hooks (split path) is the plain 256-register kernel
-    const bool help = use_helpers(h) && (lm == TF_LM_STEP || lm == TF_LM_STEP_RAND || lm == TF_LM_RESET || lm == TF_LM_SIM);
+    const bool sim = lm == TF_LM_STEP || lm == TF_LM_STEP_RAND || lm == TF_LM_RESET || lm == TF_LM_SIM;
+    const bool help = use_helpers(h) && sim;
 #if defined(TF_DEV_MIN)      // developer builds (tools/ab_bench.py, tools/variant_sweep.py): the headline kernels only (the fused launches: no split path)
     if (help && lm != TF_LM_SIM) tf_launch_env_0_2(lm, a); else if (h->wide) tf_launch_env_0_1(lm, a); else tf_launch_env_0_0(lm, a);
 #else
     const int k = ext_kind(h->cfg);
+    if (sim && h->cfg.model.cube_wall_surface) {      // the surface normal of the cube corners: its own units (EXT 0 / 1; tf_create keeps it wide)
+        if (help) { if (k == 1) tf_launch_env_surf_1_2(lm, a); else tf_launch_env_surf_0_2(lm, a); }
+        else { if (k == 1) tf_launch_env_surf_1_1(lm, a); else tf_launch_env_surf_0_1(lm, a); }
+        return;
+    }
     if (help) { if (k == 2) tf_launch_env_2_2(lm, a); else if (k == 1) tf_launch_env_1_2(lm, a); else tf_launch_env_0_2(lm, a); }
     else if (k == 2) { if (h->wide) tf_launch_env_2_1(lm, a); else tf_launch_env_2_0(lm, a); }
     else if (k == 1) { if (h->wide) tf_launch_env_1_1(lm, a); else tf_launch_env_1_0(lm, a); }

@@ -187,6 +187,10 @@ class TrifingerEngine:
                     "the TriFinger step runs only as HIP kernels on an MI355X: device must be 'cuda:N' "
                     f"(got '{device}'); there is no CPU path in this package")
             lib = capi.load_hip_library()
+        if cfg.model.cube_wall_surface and lib.backend != "hip-gfx950":
+            # the oracle does not know the field (API 9) and would step the default model without a word
+            raise NotImplementedError(f"TfModel.cube_wall_surface: the surface normal of the cube corners exists in the gfx950 HIP build only, "
+                                      f"not in `{lib.backend}` ({lib.path})")
         self.lib = lib
         self.cfg = cfg
         n = cfg.num_envs

@@ -154,6 +154,14 @@ class TrifingerEnv(IsaacEnvBase):
         if not native.get("ff_middle_pairs", True):
             model = model if model is not None else lib.default_model()
             model.ff_middle_pairs = 0
+        # "native.cube_wall_normal" (API 9): the boundary normal of the cube corners - "horizontal" (default) at every height, or "surface": the
+        # tilted normal of the flared part of the stage above its vertical ring, as the fingertips have it (include/trifinger.h: TfModel.cube_wall_surface)
+        cube_wall_normal = native.get("cube_wall_normal", "horizontal")
+        if cube_wall_normal not in ("horizontal", "surface"):
+            raise ValueError(f"native.cube_wall_normal: 'horizontal' or 'surface', got {cube_wall_normal!r}")
+        if cube_wall_normal == "surface":
+            model = model if model is not None else lib.default_model()
+            model.cube_wall_surface = 1
         cfg = make_config(
             lib, int(c["num_instances"]), seed=int(c["seed"]), env_id_offset=self._env_id_offset,
             global_num_envs=self._global_num_instances(), command_mode=c["command_mode"],

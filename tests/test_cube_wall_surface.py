@@ -1,0 +1,358 @@
+"""TfModel.cube_wall_surface (API 9): the opt-in surface normal of the cube corners on the flared part of the boundary.
+
+The stage is a bowl - a vertical ring up to wall_z[0], above it a cone that leans outward.  The default model gives the cube corners the HORIZONTAL
+normal at every height (tests/test_contact_scenarios.py: test_cube_corner_on_the_cone_keeps_the_horizontal_normal); with the switch on a corner above
+wall_z[0] gets the rows of the tilted surface - normal (c n_h, s), gap (r(z) - rho) c, friction along the horizontal tangent and the up-slope tangent
+(-s n_h, c) - as the fingertips have them.  Only the 256-register kernels of the cube (EXT 0, 1) carry it; the oracle does not model it.
+
+* known answer: a weightless cube flying outward at 110 mm meets the cone with its two lower outward corners and is thrown upward along the surface
+  normal (fails without the feature: the default model leaves dv_z at 0);
+* fp64 restatement: the cube cases of test_contact_lcp_reference._boundary_cases against an independent fixed point whose cube-boundary rows are the
+  tilted ones;
+* where the two models coincide - every corner on the vertical ring - the switch changes nothing: HIP with the switch on == the oracle on the default
+  model, bit for bit, env by env, until the env's cube brings a corner above wall_z[0] near the boundary;
+* selection of the instantiation, guards, and a soak.
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import parity_util as pu
+import physics_ref as PR
+import test_physics_analytic as T
+from leibnizgym_amd import _capi as capi
+from leibnizgym_amd.engine import TrifingerEngine, make_config
+from test_contact_lcp_reference import _boundary_cases, scaled_error
+
+H = 0.01
+
+
+def _surface(m):
+    m.cube_wall_surface = 1
+
+
+# ---- CPU: the field, the key, the guards ---------------------------------------------------------------------------------------------------
+def test_default_model_has_the_switch_off(oracle):
+    assert capi.TF_API_VERSION == 9 and oracle.tf_api_version() == 9
+    assert capi.TfModel._fields_[-1] == ("cube_wall_surface", C.c_int32)           # appended: the last field of the struct
+    assert capi.TfModel.cube_wall_surface.offset == C.sizeof(capi.TfModel) - 4
+    assert oracle.default_model().cube_wall_surface == 0
+    hip = capi.TfLib(capi.hip_library_path())                                       # host-side entry: no GPU needed
+    assert hip.default_model().cube_wall_surface == 0
+
+
+def test_bad_cube_wall_normal_is_a_value_error(oracle):
+    from leibnizgym_amd.envs import TrifingerEnv
+    with pytest.raises(ValueError, match="cube_wall_normal"):
+        TrifingerEnv(config={"num_instances": 2, "command_mode": "torque", "native": {"cube_wall_normal": "tilted"}},
+                     device="cpu", verbose=False, lib=oracle)
+
+
+def test_the_oracle_refuses_the_switch(oracle):
+    """the oracle does not know the field and would step the default model without a word: the engine refuses"""
+    from leibnizgym_amd.envs import TrifingerEnv
+    m = oracle.default_model()
+    _surface(m)
+    with pytest.raises(NotImplementedError, match="cube_wall_surface"):
+        TrifingerEngine(make_config(oracle, 2, model=m), device="cpu", lib=oracle)
+    with pytest.raises(NotImplementedError, match="cube_wall_surface"):
+        TrifingerEnv(config={"num_instances": 2, "command_mode": "torque", "native": {"cube_wall_normal": "surface"}},
+                     device="cpu", verbose=False, lib=oracle)
+    # the default key builds the default model
+    env = TrifingerEnv(config={"num_instances": 2, "command_mode": "torque", "native": {"cube_wall_normal": "horizontal"}},
+                       device="cpu", verbose=False, lib=oracle)
+    assert env._engine.cfg.model.cube_wall_surface == 0
+
+
+# ---- known answer ------------------------------------------------------------------------------------------------------------------------
+def _flying_cube_hits_the_cone(lib, device, variant, surface=True, v_r=0.3):
+    """the scenario of test_contact_scenarios._flying_cube_hits_the_cone with the switch: a cube without weight, 110 mm up, flies outward; its two
+    lower outward corners (77.5 mm: second segment of the cone) meet the boundary"""
+    def edit(m):
+        m.cube_linear_damping = 0.0
+        m.cube_angular_damping = 0.0
+        m.mu_cube_wall = 0.0                                   # the normal row alone
+        m.cube_wall_surface = 1 if surface else 0
+    eng = T.engine(lib, device=device, model_edit=edit, gravity=(0.0, 0.0, 0.0), **T.HOLD)
+    eng.kernel_variant = variant
+    assert eng.kernel_variant == variant
+    m = lib.default_model()
+    f32 = dict(dtype=torch.float32, device=device)
+    r_at = T.wall_radius_at(0.11 - 0.0325, m)
+    eng.cube[0:3, 0] = torch.tensor([r_at - 0.0325 - 0.004, 0.0, 0.11], **f32)      # the corners 4 mm inside the profile: they arrive within the step
+    eng.cube[7, 0] = v_r
+    act = torch.tensor([[0.0, 0.9, -1.7] * 3], **f32)
+    before = eng.cube[:, 0].cpu().numpy().astype(np.float64)
+    eng.step(act)
+    after = eng.cube[:, 0].cpu().numpy().astype(np.float64)
+    lam = eng.state[capi.S_LAM_CW:capi.S_LAM_CW + 12, 0].cpu().numpy().astype(np.float64)
+    eng.close()
+    return before, after, lam, m
+
+
+def _outward_corner_n0(cube):
+    """x component of the inward horizontal unit vector at the two lower outward corners (x + h, +-h) of an unrotated-in-yaw cube"""
+    h = PR.CUBE_HALF
+    R = PR.quat_rot(cube[3:7])
+    xs = [(cube[0:3] + R @ np.array([h, sy, -h]))[0:2] for sy in (-h, h)]
+    return [abs(p[0]) / np.hypot(p[0], p[1]) for p in xs]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant", ["wide", "wide_helpers"])
+def test_cube_corner_on_the_cone_gets_the_surface_normal_gpu(hip, variant):
+    before, after, lam, m = _flying_cube_hits_the_cone(hip, "cuda:0", variant)
+    assert (lam[0::3] > 0).sum() == 2, lam                                 # the two lower outward corners pushed
+    dv = after[7:10] - before[7:10]
+    sl = (float(m.wall_r[2]) - float(m.wall_r[1])) / (float(m.wall_z[2]) - float(m.wall_z[1]))   # s / c of the segment the corners are on
+    assert float(m.wall_z[1]) < before[2] - 0.0325 < float(m.wall_z[2])
+    assert dv[0] < -0.3 * 0.3 and abs(dv[1]) < 1e-5, dv
+    # each corner's impulse is along its own surface normal (c n_h, s): dv_z / |dv_x| = (s / c) / n0, n0 the radial share of x at the corners
+    # (0.985 here: they sit at y = +-32.5 mm) - the corners move a little in the step, so n0 is bracketed by the poses before and after it
+    n0 = _outward_corner_n0(before) + _outward_corner_n0(after)
+    ratio = dv[2] / -dv[0]
+    lo, hi = sl / max(n0) * (1 - 1e-3), sl / min(n0) * (1 + 1e-3)
+    assert lo <= ratio <= hi, (ratio, lo, hi, sl)
+    assert abs(ratio - sl) < 0.03 * sl                                     # = (s / c) |dv_x| to the corners' 1.5 % off-axis share
+    # the same instantiation without the switch: the horizontal normal, no vertical impulse
+    b0, a0, _, _ = _flying_cube_hits_the_cone(hip, "cuda:0", variant, surface=False)
+    assert abs(a0[9] - b0[9]) < 1e-6
+
+
+# ---- fp64 restatement with the tilted cube-boundary rows -------------------------------------------------------------------------------
+def ref_substep_surface(q, qd, cube, tau, h, max_sweeps=50000, tol=1e-13):
+    """physics_ref.ref_substep with the cube-boundary rows of the SURFACE: directions (n, t, u) = ((c n_h, s), (-n_h1, n_h0, 0), (-s n_h, c)) and the
+    gap (r(z) - rho) c for a corner above WALL_Z[0] (the ring's rows below it).  Every other row is the reference's own (its contact generation,
+    its matrices); its cube-boundary rows - built just before the nine limit rows - are replaced, and the problem is solved to the fixed point again.
+    Returns (qd, cube v, cube w, number of cube-boundary corners that push)."""
+    det = PR.ref_substep(q, qd, cube, tau, h, max_sweeps=1)[3]
+    rows, Minv, v_start = det["rows"], det["Minv"], det["v_start"]
+    nw = 3 * det["n_wall"]
+    head, limits = rows[:len(rows) - 9 - nw], rows[len(rows) - 9:]
+    assert all(r.kind == "limit" for r in limits) and len(head) + nw + 9 == len(rows)
+    cube = np.asarray(cube, dtype=np.float64)
+    cp, R = cube[0:3], PR.quat_rot(cube[3:7])
+    hc = np.full(3, PR.CUBE_HALF)
+    wall = []
+    rho_c = np.hypot(cp[0], cp[1])
+    if rho_c > 1e-6:
+        pr = R.T @ np.array([cp[0] / rho_c, cp[1] / rho_c, 0.0])
+        k = int(np.argmax(np.abs(pr) * hc))
+        sk = -1.0 if pr[k] < 0 else 1.0
+        others = [i for i in range(3) if i != k]
+        for idx in range(4):
+            yv = np.zeros(3)
+            yv[k] = sk * hc[k]
+            yv[others[0]] = hc[others[0]] if idx & 1 else -hc[others[0]]
+            yv[others[1]] = hc[others[1]] if idx & 2 else -hc[others[1]]
+            r = R @ yv
+            P = cp + r
+            rho = np.hypot(P[0], P[1])
+            wc, wsn = PR.wall_tilt(P[2]) if P[2] > PR.WALL_Z[0] else (1.0, 0.0)
+            gap = (PR.wall_radius_at(P[2]) - rho) * wc
+            if not (gap < PR.MARGIN and rho > 1e-6):
+                continue
+            nh = np.array([-P[0] / rho, -P[1] / rho])
+            n = np.array([wc * nh[0], wc * nh[1], wsn])
+            t = np.array([-nh[1], nh[0], 0.0])
+            u = np.cross(n, t)
+            Jc = np.zeros((3, 15))
+            Jc[:, 9:12] = np.eye(3)
+            Jc[:, 12:15] = -np.array([[0, -r[2], r[1]], [r[2], 0, -r[0]], [-r[1], r[0], 0]])
+            Jr = [d @ Jc for d in (n, t, u)]
+            vn0 = float(Jr[0] @ v_start)                        # the cube dofs of v_start are the free velocities
+            if not PR.contact_live(gap, vn0, h):
+                continue
+            n_row = PR.Row(Jr[0], "normal", bias=PR.contact_bias(gap, vn0, h, 0.0))
+            wall += [n_row, PR.Row(Jr[1], "tangent", parent=n_row, mu=PR.MU["cw"]), PR.Row(Jr[2], "tangent", parent=n_row, mu=PR.MU["cw"])]
+    rows = head + wall + limits
+    for r in rows:
+        r.lam = 0.0
+    v = v_start.copy()
+    W = [Minv @ r.J for r in rows]
+    D = [float(r.J @ w) for r, w in zip(rows, W)]
+    for sweeps in range(1, max_sweeps + 1):                 # projected Gauss-Seidel to the fixed point (physics_ref.ref_substep)
+        change = 0.0
+        for r, w, d in zip(rows, W, D):
+            if d <= 0.0:
+                continue
+            vrel = float(r.J @ v)
+            if r.kind == "normal":
+                new = max(r.lam - (vrel + r.bias) / d, 0.0)
+            elif r.kind == "tangent":
+                lim = r.mu * r.parent.lam
+                new = float(np.clip(r.lam - vrel / d, -lim, lim))
+            else:
+                v0 = vrel - d * r.lam
+                new = (float(np.clip(v0, r.lo, r.hi)) - v0) / d
+            dl = new - r.lam
+            if dl != 0.0:
+                v = v + w * dl
+                r.lam = new
+                change = max(change, abs(dl) * np.sqrt(d))
+        if change < tol:
+            break
+    assert sweeps < max_sweeps, "the reference did not reach its fixed point"
+    return v[0:9].copy(), v[9:12].copy(), v[12:15].copy(), sum(r.lam > 0 for r in wall if r.kind == "normal")
+
+
+def product_substep_surface(lib, device, variant, q, qd, cube, tau, sweeps):
+    eng = T.engine(lib, device=device, model_edit=_surface, dt=H, substeps=1, solver_iterations=sweeps)
+    eng.kernel_variant = variant
+    f32 = dict(dtype=torch.float32, device=device)
+    eng.q[:, 0] = torch.tensor(q, **f32)
+    eng.qd[:, 0] = torch.tensor(qd, **f32)
+    eng.cube[:, 0] = torch.tensor(cube, **f32)
+    eng.tau[:, 0] = torch.tensor(tau, **f32)
+    eng.simulate()
+    st = eng.state[:, 0].cpu().numpy().astype(np.float64)
+    eng.close()
+    return st[9:18], st[25:28], st[28:31]
+
+
+@pytest.mark.gpu
+def test_surface_rows_agree_with_the_independent_solution_gpu(hip):
+    cases = [c for c in _boundary_cases(np.random.default_rng(77), 20) if np.hypot(c[2][0], c[2][1]) > 1e-6]     # the cube cases
+    errs, hits = {"wide": [], "wide_helpers": []}, 0
+    for q, qd, cube, tau in cases:
+        ref_qd, ref_v, ref_w, n_push = ref_substep_surface(q, qd, cube, tau, H)
+        hits += n_push > 0
+        for variant in errs:
+            errs[variant].append([scaled_error(product_substep_surface(hip, "cuda:0", variant, q, qd, cube, tau, k), (ref_qd, ref_v, ref_w))
+                                  for k in (8, 1024)])
+    n = len(cases)
+    assert n >= 12 and hits >= n // 2, (hits, n)
+    for variant, e in errs.items():
+        e = np.array(e)
+        print(f"\n{variant}: cube cases with a pushing corner on the cone {hits} of {n};  8 sweeps median {np.median(e[:, 0]):.2e} "
+              f"max {e[:, 0].max():.2e};  1024 sweeps median {np.median(e[:, 1]):.2e} max {e[:, 1].max():.2e}")
+        assert e[:, 1].max() < 1e-3 and np.median(e[:, 1]) < 2e-5 and np.median(e[:, 0]) < 5e-3, (variant, e)
+
+
+# ---- on the vertical ring the two models coincide, bit for bit ---------------------------------------------------------------------------
+def _cone_event(st, m, dt):
+    """per env: a corner of the cube (any of the eight) above wall_z[0] near the boundary in the pose of state `st` - near = within the slack of the
+    contact test plus the distance it can travel in a control step at the speed of that state, with 5 mm to spare.
+
+    Why not contact_margin (40 mm): a cube that rests upright within 40 mm of the ring has its upper corners (65 mm up) within 40 mm of the cone, so a
+    quarter of the spawns alone would count - yet such a corner only gets rows once it is LIVE, i.e. within contact_slack + h |v_n| of the surface
+    (contact_live), and the two models can differ only from that substep on.  The window here covers that: it is checked on the pose before AND after
+    every step (_ring_parity), each with the corner speed bound |v| + 2 h_c |w| of its own state, doubled, over the whole control step (two
+    substeps), plus 5 mm - a corner that crosses it within one step has to be faster than both end states say by more than a factor of two.  The
+    rollout is deterministic (fixed seed and actions), so the window cannot make the test flaky: an env it missed would fail on every run."""
+    dr = st[capi.S_DR:capi.S_DR + capi.TF_NUM_DR]
+    hc = float(m.cube_half) * dr[1]                                               # cube size of the env (1 without randomisation)
+    cp = st[capi.S_CUBE_P:capi.S_CUBE_P + 3]
+    cp = cp - np.concatenate([dr[capi.DR_STAGE_POS:capi.DR_STAGE_POS + 2], np.zeros((1, cp.shape[1]))])      # relative to the stage centre
+    q = st[capi.S_CUBE_Q:capi.S_CUBE_Q + 4].T
+    speed = np.linalg.norm(st[capi.S_CUBE_V:capi.S_CUBE_V + 3], axis=0) + np.linalg.norm(st[capi.S_CUBE_W:capi.S_CUBE_W + 3], axis=0) * hc * 2.0
+    reach = float(m.contact_slack) + 0.005 + 2.0 * speed * dt
+    wz, wr = np.array(m.wall_z[:], dtype=np.float64), np.array(m.wall_r[:], dtype=np.float64)
+    ev = np.zeros(cp.shape[1], dtype=bool)
+    for s in np.array([[sx, sy, sz] for sx in (-1, 1) for sy in (-1, 1) for sz in (-1, 1)], dtype=np.float64):
+        x, y, z, w = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+        loc = s[:, None] * hc                                                     # (3, N)
+        # rotate by the unit quaternion (x, y, z, w)
+        tx = 2 * (y * loc[2] - z * loc[1]); ty = 2 * (z * loc[0] - x * loc[2]); tz = 2 * (x * loc[1] - y * loc[0])
+        px = cp[0] + loc[0] + w * tx + (y * tz - z * ty)
+        py = cp[1] + loc[1] + w * ty + (z * tx - x * tz)
+        pz = cp[2] + loc[2] + w * tz + (x * ty - y * tx)
+        gap = np.interp(pz, wz, wr) - np.hypot(px, py)
+        ev |= (pz > wz[0] - reach) & (gap < reach)
+    return ev
+
+
+def _ring_parity(hip, oracle, cfg_name, n=4096, steps=200, seed=3):
+    kw = dict(pu.CONFIGS[cfg_name])
+    m_on = hip.default_model()
+    _surface(m_on)
+    engines = {}
+    for variant in ("wide", "wide_helpers"):
+        eng = TrifingerEngine(make_config(hip, n, seed=seed, episode_length=40, model=m_on, **kw), device="cuda:0", lib=hip)
+        eng.kernel_variant = variant
+        assert eng.kernel_variant == variant
+        engines[variant] = eng
+    ref = TrifingerEngine(make_config(oracle, n, seed=seed, episode_length=40, **kw), device="cpu", lib=oracle)
+    m, dt = oracle.default_model(), float(ref.cfg.dt)
+    for e in (ref, *engines.values()):
+        e.reset()
+    excluded = np.zeros(n, dtype=bool)
+    compared = 0
+    for t in range(steps + 1):
+        want = pu.snapshot(ref)
+        excluded |= _cone_event(want["state"].astype(np.float64), m, dt)           # (t = 0: the spawn of the reset)
+        keep = ~excluded
+        for variant, eng in engines.items():
+            got = pu.snapshot(eng)
+            for k in pu.PER_ENV_FIELDS:
+                a, b = got[k], want[k]
+                a, b = (a[:, keep], b[:, keep]) if k == "state" else (a[keep], b[keep])
+                same = (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b)) if a.dtype.kind == "f" else a == b
+                if not np.all(same):
+                    bad = np.argwhere(~same)[0]
+                    raise AssertionError(f"{cfg_name} {variant} step {t}: `{k}` differs in an env whose corners stayed on the ring: {tuple(bad)}")
+        compared += int(keep.sum())
+        if t == steps:
+            break
+        act = pu.actions_for(t, n, ref.action_dim, seed)
+        ref.step(act)
+        for eng in engines.values():
+            eng.step(act.to("cuda:0"))
+        excluded |= _cone_event(ref.state.numpy().astype(np.float64), m, dt)     # the pose after the step bounds it from the other side
+    for e in (ref, *engines.values()):
+        e.close()
+    print(f"\n{cfg_name}: {n} envs x {steps} steps, {int(excluded.sum())} envs brought a corner near the cone; {compared} env-steps compared bit for bit")
+    assert excluded.sum() < 0.5 * n, excluded.sum()                                # most envs never leave the ring
+    return excluded
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cfg_name", ["d4_torque_asym", "d4_domain_randomization_extended"])
+def test_switch_changes_nothing_on_the_vertical_ring_gpu(hip, oracle, cfg_name):
+    _ring_parity(hip, oracle, cfg_name)
+
+
+# ---- selection and guards on the GPU -----------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_auto_selection_with_the_switch_gpu(hip):
+    m = hip.default_model()
+    _surface(m)
+    kw = dict(pu.CONFIGS["d4_torque_asym"])
+    for n, want in ((8192, "wide_helpers"), (65536, "wide")):
+        eng = TrifingerEngine(make_config(hip, n, model=m, **kw), device="cuda:0", lib=hip)
+        assert eng.kernel_variant == want, (n, eng.kernel_variant)
+        assert eng.kernel_occupancy >= 1
+        eng.step_random()
+        with pytest.raises(NotImplementedError):                                  # TF_ERR_UNSUPPORTED: no 128-register kernel with the switch
+            eng.kernel_variant = "narrow"
+        assert eng.kernel_variant == want
+        eng.close()
+    torch.cuda.synchronize()
+    # the general box is not built with the switch: refused at create time
+    mb = hip.box_model([0.02, 0.08, 0.02], 500.0)
+    _surface(mb)
+    with pytest.raises(NotImplementedError):
+        TrifingerEngine(make_config(hip, 64, model=mb, **kw), device="cuda:0", lib=hip)
+    bad = hip.default_model()
+    bad.cube_wall_surface = 2
+    with pytest.raises(ValueError):
+        TrifingerEngine(make_config(hip, 64, model=bad, **kw), device="cuda:0", lib=hip)
+
+
+@pytest.mark.gpu
+def test_soak_with_the_switch_gpu(hip):
+    """16384 envs of the bench workload (difficulty 4, random actions) with the switch, 20 000 steps: the NaN guard never fires"""
+    m = hip.default_model()
+    _surface(m)
+    eng = TrifingerEngine(make_config(hip, 16384, seed=11, model=m, **dict(pu.CONFIGS["d4_torque_asym"])), device="cuda:0", lib=hip)
+    assert eng.kernel_variant == "wide_helpers"
+    eng.reset()
+    guard = torch.zeros((), dtype=torch.float64, device="cuda:0")
+    for _ in range(20000):
+        eng.step_random()
+        guard += eng.info[capi.INFO_NUM_NONFINITE]
+    assert float(guard) == 0.0
+    assert bool(torch.isfinite(eng.state).all())
+    eng.close()
