@@ -1,9 +1,9 @@
 // tf_launch.h - the seam between the C ABI host half (trifinger_hip.hip) and the fused step kernel (tf_env_kernels.hip).
 //
-// k_env<A, IS_RESET, ASYM, MODE, EXT, WIDE, HELP> has 2 x 2 x 8 instantiations per (EXT, WIDE) pair (2 x 2 x 4 with helper wavefronts: WIDE = 2);
-// tf_env_kernels.hip is compiled once per pair (-DTF_EXT=0|1|2 -DTF_WIDE=0|1, -DTF_EXT=0|1|2 -DTF_WIDE=2) and exports one launcher each, so that the
-// nine translation units build in parallel (make -j: ~1 min
-// instead of ~4 for one translation unit).  Host side only: plain pointers and a stream.
+// k_env<A, IS_RESET, ASYM, MODE, EXT, WIDE, HELP> (k_env_surf with the surface normal of the cube corners) is split into translation units ("units"):
+// tf_env_kernels.hip is compiled once per (EXT, WIDE) pair and once per (EXT, WIDE) pair of the surface-normal kernels (Makefile: UNITS), so that the
+// thirteen units build in parallel (make -j: ~1 min instead of ~4 for one translation unit).  Each unit exports one EnvUnit object; the host picks one
+// from its table (trifinger_hip.hip: unit_for).  Host side only: plain pointers and a stream.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -22,32 +22,16 @@ struct EnvLaunch {
 // which hooks of the reference step a launch performs (MODE of tf_roles.h)
 enum { TF_LM_STEP = 0, TF_LM_STEP_RAND, TF_LM_RESET, TF_LM_RESETS, TF_LM_TORQUE, TF_LM_SIM, TF_LM_POST, TF_LM_FINISH };
 
-// workgroups of the fused step (actions drawn in the launch) that fit a CU at once, as the HIP runtime computes it from registers and LDS
-int tf_occupancy_env_0_0(int action_dim, bool asym);
-int tf_occupancy_env_0_1(int action_dim, bool asym);
-int tf_occupancy_env_1_0(int action_dim, bool asym);
-int tf_occupancy_env_1_1(int action_dim, bool asym);
-int tf_occupancy_env_2_0(int action_dim, bool asym);
-int tf_occupancy_env_2_1(int action_dim, bool asym);
-int tf_occupancy_env_0_2(int action_dim, bool asym);      // WIDE = 2: the 256-register kernels with helper wavefronts (TF_LM_STEP, _STEP_RAND, _RESET, _SIM)
-int tf_occupancy_env_1_2(int action_dim, bool asym);
-int tf_occupancy_env_2_2(int action_dim, bool asym);
-void tf_launch_env_0_0(int lm, const EnvLaunch& a);      // tf_launch_env_<EXT>_<WIDE>
-void tf_launch_env_0_1(int lm, const EnvLaunch& a);
-void tf_launch_env_1_0(int lm, const EnvLaunch& a);
-void tf_launch_env_1_1(int lm, const EnvLaunch& a);
-void tf_launch_env_2_0(int lm, const EnvLaunch& a);
-void tf_launch_env_2_1(int lm, const EnvLaunch& a);
-void tf_launch_env_0_2(int lm, const EnvLaunch& a);
-void tf_launch_env_1_2(int lm, const EnvLaunch& a);
-void tf_launch_env_2_2(int lm, const EnvLaunch& a);
-// the same with the surface normal of the cube corners (TfModel.cube_wall_surface, -DTF_SURF=1): the 256-register cube kernels, the launches that
-// simulate (TF_LM_STEP, _STEP_RAND, _RESET, _SIM)
-int tf_occupancy_env_surf_0_1(int action_dim, bool asym);
-int tf_occupancy_env_surf_1_1(int action_dim, bool asym);
-int tf_occupancy_env_surf_0_2(int action_dim, bool asym);
-int tf_occupancy_env_surf_1_2(int action_dim, bool asym);
-void tf_launch_env_surf_0_1(int lm, const EnvLaunch& a);
-void tf_launch_env_surf_1_1(int lm, const EnvLaunch& a);
-void tf_launch_env_surf_0_2(int lm, const EnvLaunch& a);
-void tf_launch_env_surf_1_2(int lm, const EnvLaunch& a);
+struct EnvUnit {
+    // enqueues launch mode lm: TF_OK (launch errors: hipGetLastError), or TF_ERR_UNSUPPORTED where the unit does not instantiate (lm, action_dim)
+    int (*launch)(int lm, const EnvLaunch& a);
+    // workgroups of the fused step (actions drawn in the launch) that fit a CU at once, as the HIP runtime computes it from registers and LDS; -1 on failure
+    int (*occupancy)(int action_dim, bool asym);
+};
+
+// tf_unit_<EXT>_<WIDE>: WIDE 0 the 128-register kernels, 1 the 256-register ones, 2 those with helper wavefronts (the launches that simulate only:
+// TF_LM_STEP, _STEP_RAND, _RESET, _SIM); tf_unit_s<EXT>_<WIDE>: with the surface normal of the cube corners (TfModel.cube_wall_surface, -DTF_SURF=1),
+// the launches that simulate.  Developer builds (-DTF_DEV_MIN) carry tf_unit_0_<WIDE> with the fused launches of A = 9 only.  (Not const: hipcc would
+// emit a const one for the device as well, where its host functions do not exist.)
+extern EnvUnit tf_unit_0_0, tf_unit_0_1, tf_unit_0_2, tf_unit_1_0, tf_unit_1_1, tf_unit_1_2, tf_unit_2_0, tf_unit_2_1, tf_unit_2_2;
+extern EnvUnit tf_unit_s0_1, tf_unit_s0_2, tf_unit_s1_1, tf_unit_s1_2;

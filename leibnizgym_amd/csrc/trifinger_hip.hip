@@ -112,12 +112,50 @@ struct TfHandle_ {
     int64_t frame_count;
     int action_dim;
     int variant;             // TF_KERNEL_AUTO / NARROW / WIDE / WIDE_HELPERS as asked for (tf_set_kernel_variant)
-    bool wide;               // what the launches use
+    int width;               // what the launches use: 0 the 128-register kernels, 1 the 256-register ones, 2 those with helper wavefronts (TF_WIDE)
     // optional kernel timing (bench.py): event pairs around the fused step kernel
     hipEvent_t* ev;          // [2 * ev_cap]
     int ev_cap, ev_used;
     int ev_stride, ev_phase; // one event pair per window of ev_stride consecutive launches
 };
+
+// The fused step kernel k_env<A, IS_RESET, ASYM, MODE, EXT, WIDE, HELP> lives in tf_env_kernels.hip, compiled once per unit (tf_launch.h).  The extended
+// domain randomisation (robot base / stage position, per-body friction) and the general box object (TfModel.box) are their own instantiations (EXT = 1, 2):
+// the kernels of the headline path stay exactly what they were - a run-time flag for either cost 9 to 26 us per step through register pressure - and the
+// extended randomisation with the cube (BASELINE configs[3]) does not carry the box code either (round 3: with both behind one template flag the cube role
+// of that kernel spilled 95 registers on its serial chain).
+static int ext_kind(const TfConfig& c) {
+    if (c.model.box) return 2;
+    if (!c.dr_enable) return 0;
+    for (int i = 0; i < 3; ++i) if (c.dr_base_pos[i] > 0.0f) return 1;
+    for (int i = 0; i < 2; ++i) if (c.dr_stage_pos[i] > 0.0f) return 1;
+    const float* f[3] = {c.dr_friction_robot, c.dr_friction_object, c.dr_friction_stage};
+    for (int b = 0; b < 3; ++b) if (f[b][0] != 1.0f || f[b][1] != 1.0f) return 1;
+    return 0;
+}
+// the width (TfHandle_::width) of a kernel variant: TF_KERNEL_AUTO picks the 256-register kernels for populations of at most TF_WIDE_MAX_ENVS (with the
+// surface normal of the cube corners at any size), and helper wavefronts for a population that leaves every CU to one workgroup (with the fast contact set
+// too: the distal pass on wavefront 7 alone is worth 1.4 us at 8192 envs)
+static int resolve_width(const TfConfig& c, int variant) {
+    if (variant != TF_KERNEL_AUTO) return variant - TF_KERNEL_NARROW;
+    if (!c.model.cube_wall_surface && c.num_envs > TF_WIDE_MAX_ENVS) return 0;
+    return c.num_envs <= TF_HELPERS_MAX_ENVS ? 2 : 1;
+}
+// The unit that carries launch mode lm, from [surf][ext][width]; nullptr where none is built - the one place that decides which combinations exist.  The
+// launches that simulate use the handle's own width and surface normal; the other hooks (split path) the plain unit of at most 256 registers, which is
+// built wherever the handle's fused step is: tf_create and tf_set_kernel_variant admit a (config, width) only if unit_for(.., TF_LM_STEP) is.
+static const EnvUnit* unit_for(const TfConfig& c, int width, int lm) {
+#if defined(TF_DEV_MIN)      // developer builds (tools/ab_bench.py, tools/variant_sweep.py): the headline kernels, fused launches of A = 9 only
+    static const EnvUnit* const units[2][3][3] = {{{&tf_unit_0_0, &tf_unit_0_1, &tf_unit_0_2}}};
+#else
+    static const EnvUnit* const units[2][3][3] = {
+        {{&tf_unit_0_0, &tf_unit_0_1, &tf_unit_0_2}, {&tf_unit_1_0, &tf_unit_1_1, &tf_unit_1_2}, {&tf_unit_2_0, &tf_unit_2_1, &tf_unit_2_2}},
+        {{nullptr, &tf_unit_s0_1, &tf_unit_s0_2}, {nullptr, &tf_unit_s1_1, &tf_unit_s1_2}, {nullptr, nullptr, nullptr}},
+    };
+#endif
+    const bool sim = lm == TF_LM_STEP || lm == TF_LM_STEP_RAND || lm == TF_LM_RESET || lm == TF_LM_SIM;
+    return sim ? units[c.model.cube_wall_surface][ext_kind(c)][width] : units[0][ext_kind(c)][width < 1 ? width : 1];
+}
 
 static thread_local char g_err[512] = "";
 static void free_events(TfHandle_* h);
@@ -341,13 +379,10 @@ int tf_create(const TfConfig* cfg, tf_handle* out) {
         if (!(z - z == 0.0f) || !(r - r == 0.0f) || !(r > 0.0f)) return TF_ERR_INVALID_ARG;
         if (i > 0 && !(z > cfg->model.wall_z[i - 1])) return TF_ERR_INVALID_ARG;
     }
-    /* the surface normal of the cube corners (API 9): 0 or 1; built into the 256-register cube kernels only (not the general box, not the
-     * developer builds) */
+    /* the surface normal of the cube corners (API 9): 0 or 1 */
     if (cfg->model.cube_wall_surface != 0 && cfg->model.cube_wall_surface != 1) return TF_ERR_INVALID_ARG;
-#if defined(TF_DEV_MIN)
-    if (cfg->model.cube_wall_surface) return TF_ERR_UNSUPPORTED;
-#endif
-    if (cfg->model.cube_wall_surface && cfg->model.box) return TF_ERR_UNSUPPORTED;
+    const int width = resolve_width(*cfg, TF_KERNEL_AUTO);
+    if (!unit_for(*cfg, width, TF_LM_STEP)) return TF_ERR_UNSUPPORTED;
     TfHandle_* h = new TfHandle_();
     memset(h, 0, sizeof(*h));
     h->cfg = *cfg;
@@ -355,7 +390,7 @@ int tf_create(const TfConfig* cfg, tf_handle* out) {
     if (h->cfg.global_num_envs <= 0) h->cfg.global_num_envs = cfg->num_envs;
     h->action_dim = tf_action_dim(cfg->command_mode);
     h->variant = TF_KERNEL_AUTO;
-    h->wide = cfg->model.cube_wall_surface || cfg->num_envs <= TF_WIDE_MAX_ENVS;     // with the surface normal: the 256-register kernels at any size
+    h->width = width;
     int od = 0, sd = 0;
     DevParams& P = h->dp;
     build_tables(&h->cfg, h->action_dim, P.tables, &od, &sd);
@@ -456,41 +491,18 @@ int tf_set_gravity(tf_handle h, const float g[3]) {
     HIP_TRY(push_params(h));
     return TF_OK;
 }
-static int ext_kind(const TfConfig& c);
-// helper wavefronts (the WIDE = 2 units): asked for, or picked for a population that leaves every CU to one workgroup (with the fast contact set too: the
-// distal pass on wavefront 7 alone is worth 1.4 us at 8192 envs)
-static bool use_helpers(const TfHandle_* h) {
-    if (!h->wide) return false;
-    if (h->variant == TF_KERNEL_WIDE_HELPERS) return true;
-    return h->variant == TF_KERNEL_AUTO && h->cfg.num_envs <= TF_HELPERS_MAX_ENVS;
-}
 int tf_set_kernel_variant(tf_handle h, int32_t variant) {
     if (!h || variant < TF_KERNEL_AUTO || variant > TF_KERNEL_WIDE_HELPERS) return TF_ERR_INVALID_ARG;
-    const bool surf = h->cfg.model.cube_wall_surface != 0;
-    if (surf && variant == TF_KERNEL_NARROW) return TF_ERR_UNSUPPORTED;      // no 128-register kernel with the surface normal of the cube corners
+    const int width = resolve_width(h->cfg, variant);
+    if (!unit_for(h->cfg, width, TF_LM_STEP)) return TF_ERR_UNSUPPORTED;
     h->variant = variant;
-    h->wide = (variant == TF_KERNEL_AUTO) ? (surf || h->cfg.num_envs <= TF_WIDE_MAX_ENVS) : (variant != TF_KERNEL_NARROW);
+    h->width = width;
     return TF_OK;
 }
-int tf_kernel_variant(tf_handle h) { return h ? (h->wide ? (use_helpers(h) ? TF_KERNEL_WIDE_HELPERS : TF_KERNEL_WIDE) : TF_KERNEL_NARROW) : TF_ERR_INVALID_ARG; }
+int tf_kernel_variant(tf_handle h) { return h ? TF_KERNEL_NARROW + h->width : TF_ERR_INVALID_ARG; }
 int tf_kernel_occupancy(tf_handle h) {
     if (!h) return TF_ERR_INVALID_ARG;
-    const bool asym = h->cfg.asymmetric_obs != 0;
-    const bool help = use_helpers(h);
-#if defined(TF_DEV_MIN)
-    if (help) return tf_occupancy_env_0_2(h->action_dim, asym);
-    return h->wide ? tf_occupancy_env_0_1(h->action_dim, asym) : tf_occupancy_env_0_0(h->action_dim, asym);
-#else
-    const int k = ext_kind(h->cfg);
-    if (h->cfg.model.cube_wall_surface) {
-        if (help) return k == 1 ? tf_occupancy_env_surf_1_2(h->action_dim, asym) : tf_occupancy_env_surf_0_2(h->action_dim, asym);
-        return k == 1 ? tf_occupancy_env_surf_1_1(h->action_dim, asym) : tf_occupancy_env_surf_0_1(h->action_dim, asym);
-    }
-    if (help) return k == 2 ? tf_occupancy_env_2_2(h->action_dim, asym) : (k == 1 ? tf_occupancy_env_1_2(h->action_dim, asym) : tf_occupancy_env_0_2(h->action_dim, asym));
-    if (k == 2) return h->wide ? tf_occupancy_env_2_1(h->action_dim, asym) : tf_occupancy_env_2_0(h->action_dim, asym);
-    if (k == 1) return h->wide ? tf_occupancy_env_1_1(h->action_dim, asym) : tf_occupancy_env_1_0(h->action_dim, asym);
-    return h->wide ? tf_occupancy_env_0_1(h->action_dim, asym) : tf_occupancy_env_0_0(h->action_dim, asym);
-#endif
+    return unit_for(h->cfg, h->width, TF_LM_STEP_RAND)->occupancy(h->action_dim, h->cfg.asymmetric_obs != 0);
 }
 int64_t tf_frame_count(tf_handle h) { return h ? h->frame_count : -1; }
 int tf_set_frame_count(tf_handle h, int64_t f) { if (!h) return TF_ERR_INVALID_ARG; h->frame_count = f; return TF_OK; }
@@ -539,41 +551,14 @@ static inline int n_waves(const TfHandle_* h) { return (h->cfg.num_envs + WAVE -
         if (e_ != hipSuccess) return hip_fail(e_, what);           \
     } while (0)
 
-// The fused step kernel k_env<A, IS_RESET, ASYM, MODE, EXT, WIDE> lives in tf_env_kernels.hip, compiled once per (EXT, WIDE) pair so that the six
-// translation units build in parallel (tf_launch.h).  The extended domain randomisation (robot base / stage position, per-body friction) and the
-// general box object (TfModel.box) are their own instantiations (EXT = 1, 2): the kernels of the headline path stay exactly what they were - a
-// run-time flag for either cost 9 to 26 us per step through register pressure - and the extended randomisation with the cube (BASELINE configs[3])
-// does not carry the box code either (round 3: with both behind one template flag the cube role of that kernel spilled 95 registers on its serial chain).
-static int ext_kind(const TfConfig& c) {
-    if (c.model.box) return 2;
-    if (!c.dr_enable) return 0;
-    for (int i = 0; i < 3; ++i) if (c.dr_base_pos[i] > 0.0f) return 1;
-    for (int i = 0; i < 2; ++i) if (c.dr_stage_pos[i] > 0.0f) return 1;
-    const float* f[3] = {c.dr_friction_robot, c.dr_friction_object, c.dr_friction_stage};
-    for (int b = 0; b < 3; ++b) if (f[b][0] != 1.0f || f[b][1] != 1.0f) return 1;
-    return 0;
-}
-static void launch_env(TfHandle_* h, int lm, const float* action, hipStream_t s) {
+static int launch_env(TfHandle_* h, int lm, const float* action, hipStream_t s, const char* what) {
     EnvLaunch a;
     a.grid = (unsigned)n_waves(h); a.action_dim = h->action_dim; a.asym = h->cfg.asymmetric_obs != 0;
     a.d_params = h->d_params; a.sa = h->sa; a.action = action; a.stream = s;
-    // the helper units carry the launches that simulate; a launch of one of the other hooks (split path) is the plain 256-register kernel
-    const bool sim = lm == TF_LM_STEP || lm == TF_LM_STEP_RAND || lm == TF_LM_RESET || lm == TF_LM_SIM;
-    const bool help = use_helpers(h) && sim;
-#if defined(TF_DEV_MIN)      // developer builds (tools/ab_bench.py, tools/variant_sweep.py): the headline kernels only (the fused launches: no split path)
-    if (help && lm != TF_LM_SIM) tf_launch_env_0_2(lm, a); else if (h->wide) tf_launch_env_0_1(lm, a); else tf_launch_env_0_0(lm, a);
-#else
-    const int k = ext_kind(h->cfg);
-    if (sim && h->cfg.model.cube_wall_surface) {      // the surface normal of the cube corners: its own units (EXT 0 / 1; tf_create keeps it wide)
-        if (help) { if (k == 1) tf_launch_env_surf_1_2(lm, a); else tf_launch_env_surf_0_2(lm, a); }
-        else { if (k == 1) tf_launch_env_surf_1_1(lm, a); else tf_launch_env_surf_0_1(lm, a); }
-        return;
-    }
-    if (help) { if (k == 2) tf_launch_env_2_2(lm, a); else if (k == 1) tf_launch_env_1_2(lm, a); else tf_launch_env_0_2(lm, a); }
-    else if (k == 2) { if (h->wide) tf_launch_env_2_1(lm, a); else tf_launch_env_2_0(lm, a); }
-    else if (k == 1) { if (h->wide) tf_launch_env_1_1(lm, a); else tf_launch_env_1_0(lm, a); }
-    else { if (h->wide) tf_launch_env_0_1(lm, a); else tf_launch_env_0_0(lm, a); }
-#endif
+    const int st = unit_for(h->cfg, h->width, lm)->launch(lm, a);
+    if (st != TF_OK) return st;
+    LAUNCH_CHECK(what);
+    return TF_OK;
 }
 
 static int launch_step(TfHandle_* h, const float* action, bool is_reset, hipStream_t s, bool random_actions = false) {
@@ -588,8 +573,8 @@ static int launch_step(TfHandle_* h, const float* action, bool is_reset, hipStre
     if (is_reset) HIP_TRY(hipMemsetAsync((void*)h->dp.tickets, 0, STAT_WORDS * sizeof(unsigned long long), s));
     const bool timing = !is_reset && h->ev && h->ev_used < h->ev_cap;
     if (timing && h->ev_phase == 0) HIP_TRY(hipEventRecord(h->ev[2 * h->ev_used], s));      // window opens
-    launch_env(h, is_reset ? TF_LM_RESET : (random_actions ? TF_LM_STEP_RAND : TF_LM_STEP), random_actions ? nullptr : action, s);
-    LAUNCH_CHECK("k_env");
+    const int st = launch_env(h, is_reset ? TF_LM_RESET : (random_actions ? TF_LM_STEP_RAND : TF_LM_STEP), random_actions ? nullptr : action, s, "k_env");
+    if (st != TF_OK) return st;
     if (timing) {
         h->ev_phase += 1;
         if (h->ev_phase == h->ev_stride) {                                                   // window closes
@@ -654,58 +639,28 @@ int tf_kernel_time_ms(tf_handle h, double* total_ms, int64_t* launches) {
 // ---- split path: one hook of the reference step per launch (parity tests) ----
 int tf_apply_resets(tf_handle h, void* stream) {
     CHECK_HANDLE(h)
-#if defined(TF_DEV_MIN)
-    return TF_ERR_UNSUPPORTED;
-#else
-    launch_env(h, TF_LM_RESETS, nullptr, (hipStream_t)stream);
-#endif
-    LAUNCH_CHECK("k_env<resets>");
-    return TF_OK;
+    return launch_env(h, TF_LM_RESETS, nullptr, (hipStream_t)stream, "k_env<resets>");
 }
 int tf_pre_step(tf_handle h, void* stream) {
     CHECK_HANDLE(h)
     h->sa.frame0 = (uint32_t)h->frame_count;
-#if defined(TF_DEV_MIN)
-    return TF_ERR_UNSUPPORTED;
-#else
-    launch_env(h, TF_LM_TORQUE, nullptr, (hipStream_t)stream);
-#endif
-    LAUNCH_CHECK("k_env<torque>");
-    return TF_OK;
+    return launch_env(h, TF_LM_TORQUE, nullptr, (hipStream_t)stream, "k_env<torque>");
 }
 int tf_simulate(tf_handle h, void* stream) {
     CHECK_HANDLE(h)
     h->frame_count += 1;
     h->sa.nsim = 1;
-#if defined(TF_DEV_MIN)
-    return TF_ERR_UNSUPPORTED;
-#else
-    launch_env(h, TF_LM_SIM, nullptr, (hipStream_t)stream);
-#endif
-    LAUNCH_CHECK("k_env<simulate>");
-    return TF_OK;
+    return launch_env(h, TF_LM_SIM, nullptr, (hipStream_t)stream, "k_env<simulate>");
 }
 int tf_post_step(tf_handle h, void* stream) {
     CHECK_HANDLE(h)
     reward_coefs(h);
     h->sa.frame = (uint32_t)h->frame_count;
-#if defined(TF_DEV_MIN)
-    return TF_ERR_UNSUPPORTED;
-#else
-    launch_env(h, TF_LM_POST, nullptr, (hipStream_t)stream);
-#endif
-    LAUNCH_CHECK("k_env<post>");
-    return TF_OK;
+    return launch_env(h, TF_LM_POST, nullptr, (hipStream_t)stream, "k_env<post>");
 }
 int tf_finish_step(tf_handle h, void* stream) {
     CHECK_HANDLE(h)
-#if defined(TF_DEV_MIN)
-    return TF_ERR_UNSUPPORTED;
-#else
-    launch_env(h, TF_LM_FINISH, nullptr, (hipStream_t)stream);
-#endif
-    LAUNCH_CHECK("k_env<finish>");
-    return TF_OK;
+    return launch_env(h, TF_LM_FINISH, nullptr, (hipStream_t)stream, "k_env<finish>");
 }
 
 #define LEAF_GRID(n) dim3(((n) + 255) / 256), dim3(256), 0, (hipStream_t)stream

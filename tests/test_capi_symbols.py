@@ -173,3 +173,18 @@ def test_ppo_library_exports_every_symbol_its_header_declares():
     bound = pk.load()                                   # the binding sets argtypes for every declared entry point
     for n in names:
         assert getattr(bound, n).restype is C.c_int, n
+
+
+def test_developer_library_refuses_what_it_does_not_carry():
+    """variants/libtf_min.so carries the headline kernels only: tf_create answers TF_ERR_UNSUPPORTED for the extended domain randomisation, the
+    general box and the surface normal of the cube corners (refused before any device allocation: no GPU needed)."""
+    from leibnizgym_amd.engine import make_config
+    csrc = os.path.join(REPO, "leibnizgym_amd", "csrc")
+    subprocess.check_call(["make", "-j8", "-s", "-C", csrc, "variants/libtf_min.so"])
+    lib = capi.TfLib(os.path.join(csrc, "variants", "libtf_min.so"))
+    box, surf = lib.box_model((0.02, 0.08, 0.02), 500.0), lib.default_model()
+    surf.cube_wall_surface = 1
+    for cfg in (make_config(lib, 64, domain_randomization=dict(activate=True, robot_base_position=(0.01, 0.02, 0.005))),
+                make_config(lib, 64, model=box), make_config(lib, 64, model=surf)):
+        h = C.c_void_p()
+        assert lib.tf_create(C.byref(cfg), C.byref(h)) == capi.TF_ERR_UNSUPPORTED

@@ -7,10 +7,10 @@ T=${1:-rX}; O=gpurun_out
 mkdir -p $O
 for W in dr box; do
   for N in 16384 65536; do
-    # <= 32768 envs: the 256-register instantiation; <= 16384 envs and not the box object: with helper wavefronts
-    K="k_env<9, false, true, 127, $([ $W = box ] && echo 2 || echo 1), $([ $N -le 32768 ] && echo true || echo false), $([ $N -le 16384 ] && [ $W != box ] && echo true || echo false)>"
     B="python3 bench.py --full --$W --envs $N --no-cpu-baseline --no-fast-contact-leg"
     P=$O/${T}_ext_${W}_${N}
+    $B > ${P}_bench.json 2>/dev/null
+    K=$(python3 -c "import json, sys; print(json.load(open(sys.argv[1]))['roofline']['kernel'])" ${P}_bench.json) || exit 1      # what the workload launches
     rocprofv3 --kernel-trace --stats -d $O/prof_$T/trace -o r -- $B --steps 300 --warmup 5 > /dev/null 2>&1
     { echo "# command: rocprofv3 --kernel-trace --stats -- $B --steps 300 --warmup 5   (MI355X)"
       python3 tools/rocprof_summary.py trace $(find $O/prof_$T/trace -name "*.db" | head -1); } > ${P}_kernel_trace.txt
@@ -24,7 +24,6 @@ for W in dr box; do
     done
     echo "# units: FETCH_SIZE / WRITE_SIZE in KiB per dispatch (raw rocprofv3 expressions); SQ cycle counters in quad-cycles summed over waves" >> ${P}_pmc.txt
     rm -rf $O/prof_$T
-    $B > ${P}_bench.json 2>/dev/null
   done
 done
 head -c 400 $O/${T}_ext_dr_16384_bench.json; echo; grep "k_env" $O/${T}_ext_*_kernel_trace.txt
