@@ -258,7 +258,8 @@ typedef struct TfModel {
      * flared part for a corner above wall_z[0] (rows: TF_S_LAM_CW).  Built into the 256-register kernels of the cube with and without the extended
      * domain randomisation only: with the switch on, TF_KERNEL_AUTO picks TF_KERNEL_WIDE_HELPERS up to TF_HELPERS_MAX_ENVS envs and TF_KERNEL_WIDE
      * above; TF_KERNEL_NARROW, the general box (box != 0) and developer builds answer TF_ERR_UNSUPPORTED; other values: TF_ERR_INVALID_ARG.
-     * The oracle does not model it (tf_default_model leaves it 0).  Cost: DESIGN.md 8. */
+     * The oracle restates it (same refusals for other values and for the box; it has no kernel variants): tests/test_parity_surface.py holds the four
+     * kernel units to it bit for bit.  tf_default_model leaves it 0.  Cost: DESIGN.md 8. */
     int32_t cube_wall_surface;
 } TfModel;
 

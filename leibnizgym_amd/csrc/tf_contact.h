@@ -263,7 +263,7 @@ DEV void cy_apply(const float r[3], float dl, float inv_m, float inv_I, float v[
     w[0] = FMA(-r[2], q, w[0]);
     w[2] = FMA(r[0], q, w[2]);
 }
-// Boundary rows of a cube corner above wall_z[0] with the SURFACE normal (TfModel.cube_wall_surface; the oracle has none of it - the default model
+// Boundary rows of a cube corner above wall_z[0] with the SURFACE normal (TfModel.cube_wall_surface; oracle: surface_rows, same name - the default model
 // keeps the ring's rows below at every height): with n_h = (n0, n1) the inward horizontal unit vector and (c, sn) the tilt of the profile segment there
 // (wall_profile), the directions are N = (c n_h, sn), the horizontal tangent T = (-n1, n0, 0) and the up-slope tangent U = (-sn n_h, c) = N x T;
 // d[3 k..] direction, a[3 k..] arm r x d of row k.  General rows: g_vrel / g_apply (scalar), pk_row_vel / pk_row_apply (packed, rec[j] = (d_j, a_j)).

@@ -187,10 +187,8 @@ class TrifingerEngine:
                     "the TriFinger step runs only as HIP kernels on an MI355X: device must be 'cuda:N' "
                     f"(got '{device}'); there is no CPU path in this package")
             lib = capi.load_hip_library()
-        if cfg.model.cube_wall_surface and lib.backend != "hip-gfx950":
-            # the oracle does not know the field (API 9) and would step the default model without a word
-            raise NotImplementedError(f"TfModel.cube_wall_surface: the surface normal of the cube corners exists in the gfx950 HIP build only, "
-                                      f"not in `{lib.backend}` ({lib.path})")
+        # TfModel.cube_wall_surface: every library of API 9 answers for itself in tf_create below - TF_ERR_UNSUPPORTED (NotImplementedError) where the
+        # build does not carry the rows (developer builds, the general box, the 128-register kernels), so nothing steps the default model without a word
         self.lib = lib
         self.cfg = cfg
         n = cfg.num_envs

@@ -528,6 +528,9 @@ int tf_create(const TfConfig* cfg, tf_handle* out) {
         if (!(z - z == 0.0f) || !(r - r == 0.0f) || !(r > 0.0f)) return TF_ERR_INVALID_ARG;
         if (i > 0 && !(z > cfg->model.wall_z[i - 1])) return TF_ERR_INVALID_ARG;
     }
+    /* the surface normal of the cube corners (API 9): 0 or 1; not with the general box (as the product: no such instantiation) */
+    if (cfg->model.cube_wall_surface != 0 && cfg->model.cube_wall_surface != 1) return TF_ERR_INVALID_ARG;
+    if (cfg->model.cube_wall_surface && cfg->model.box) return TF_ERR_UNSUPPORTED;
     struct TfHandle_* h = (struct TfHandle_*)calloc(1, sizeof(*h));
     if (h) { h->clip_obs = 3.402823466e38f; h->clip_act = 3.402823466e38f; }
     if (!h) return TF_ERR_INVALID_ARG;
@@ -802,6 +805,15 @@ typedef struct {
     float bias;
     float lam[3];
 } CubeContact;
+/* TfModel.cube_wall_surface: a cube corner above wall_z[0] against the tilted surface of the boundary.  Rows N, T, U (surface_rows) as general
+ * rows: d direction, a arm r x d of row k at [3 k..]; the impulses live in the corner slot's lam_cw rows (the slot's ring rows stay dead) */
+typedef struct {
+    int active;
+    float d[9], a[9];
+    float Dinv[3];
+    float bias;
+    float lam[3];
+} ConeContact;
 
 static void base_to_world(const TfModel* m, int f, const float b[3], float w[3]) {
     float c = m->base_yaw_cos[f], s = m->base_yaw_sin[f];
@@ -1024,7 +1036,8 @@ static float wall_radius_at(const struct TfHandle_* H, float z) {
     return r;
 }
 /* the same with the tilt of the surface at that height: (c, sn) = (cos, sin) of the slope angle of the profile segment, (1, 0) on the vertical ring;
- * inward surface normal (c n_h, sn), distance of a point at radius rho to the surface (r(z) - rho) c.  Fingertip - boundary contact only. */
+ * inward surface normal (c n_h, sn), distance of a point at radius rho to the surface (r(z) - rho) c.  Fingertip - boundary contact, and the cube corners
+ * above wall_z[0] with TfModel.cube_wall_surface on. */
 static float wall_profile(const struct TfHandle_* H, float z, float* c, float* sn) {
     const TfModel* m = &H->cfg.model;
     float r = m->wall_r[0];
@@ -1034,6 +1047,16 @@ static float wall_profile(const struct TfHandle_* H, float z, float* c, float* s
     if (z > m->wall_z[2]) { r = FMA(z - m->wall_z[2], H->wall_s[2], m->wall_r[2]); *c = H->wall_c[2]; *sn = H->wall_sn[2]; }
     if (!(z < m->wall_z[3])) r = 1000.0f;
     return r;
+}
+
+/* Boundary rows of a cube corner above wall_z[0] with the SURFACE normal (TfModel.cube_wall_surface): with n_h = (n0, n1) the inward horizontal
+ * unit vector and (c, sn) the tilt of the profile segment there (wall_profile), the directions are N = (c n_h, sn), the horizontal tangent
+ * T = (-n1, n0, 0) and the up-slope tangent U = (-sn n_h, c) = N x T; d[3 k..] direction, a[3 k..] arm r x d of row k (g_vrel / g_apply) */
+static void surface_rows(const float r[3], const float n[2], float c, float sn, float d[9], float a[9]) {
+    d[0] = c * n[0]; d[1] = c * n[1]; d[2] = sn;
+    d[3] = -n[1]; d[4] = n[0]; d[5] = 0.0f;
+    d[6] = -(sn * n[0]); d[7] = -(sn * n[1]); d[8] = c;
+    for (int k = 0; k < 3; ++k) cross3(r, &d[3 * k], &a[3 * k]);
 }
 
 static void cube_corner(const float R[9], const float hc[3], int k, float sk, int idx, float r[3]) {
@@ -1337,6 +1360,8 @@ static void substep(const struct TfHandle_* H, Env* e, float h) {
         }
     }
     CubeContact cf[4], cwl[4];
+    ConeContact cone[4];         /* cube_wall_surface: the corners above the vertical ring */
+    const int surf = m->cube_wall_surface;
     float cf_face, cw_face;
     {   /* cube vs floor: the four corners of the face that points down most */
         int k = 0;
@@ -1425,8 +1450,27 @@ static void substep(const struct TfHandle_* H, Env* e, float h) {
             float rho2 = FMA(px, px, py * py);
             float inv = f_rsqrt(f_max(rho2, 1e-24f));
             float rho = rho2 * inv;
-            float gap = wall_radius_at(H, pz) - rho;
+            float gap, wc = 1.0f, wsn = 0.0f;
+            int on_cone = 0;
+            cone[i].active = 0;
+            if (surf) {
+                const float rz = wall_profile(H, pz, &wc, &wsn);
+                on_cone = pz > m->wall_z[0];
+                gap = on_cone ? (rz - rho) * wc : rz - rho;      /* distance to the tilted surface; on the ring the horizontal gap as below */
+            } else gap = wall_radius_at(H, pz) - rho;
             if (!(any && gap < m->contact_margin && rho > 1e-6f)) continue;
+            if (on_cone) {                   /* rows N, T, U of the surface (general rows; the slot's ring rows stay dead) */
+                ConeContact* g = &cone[i];
+                const float nn[2] = {-px * inv, -py * inv};
+                surface_rows(c->r, nn, wc, wsn, g->d, g->a);
+                const float vn0 = g_vrel(&g->d[0], &g->a[0], v, w);
+                if (!contact_live(m, gap, vn0, h)) continue;
+                g->active = 1;
+                for (int d = 0; d < 3; ++d) g->Dinv[d] = f_rcp2(FMA(dot3(&g->a[3 * d], &g->a[3 * d]), inv_I, inv_m));
+                g->bias = contact_bias(m, gap, vn0, inv_h, 0.0f);
+                for (int d = 0; d < 3; ++d) g->lam[d] = e->lam_cw[(i < 2) ? (i ^ swap01) : i][d] * keep;
+                continue;
+            }
             c->n[0] = -px * inv; c->n[1] = -py * inv;
             {
                 const float* r = c->r;
@@ -1708,6 +1752,10 @@ static void substep(const struct TfHandle_* H, Env* e, float h) {
         if (box) g_apply(BOX_AXES[0], c3, cwl[i].lam[2], inv_m, inv_I, v, w);
         else cz_apply(cwl[i].r, cwl[i].lam[2], inv_m, inv_I, v, w);
     }
+    for (int i = 0; i < 4 && surf; ++i) {     /* corners above the ring: behind the ring's */
+        if (!cone[i].active) continue;
+        for (int d = 0; d < 3; ++d) g_apply(&cone[i].d[3 * d], &cone[i].a[3 * d], cone[i].lam[d], inv_m, inv_I, v, w);
+    }
     /* ---- projected Gauss-Seidel ---- */
     /* solver_inner > 1: the block of all rows that touch the cube is visited solver_inner times per sweep, the finger-only rows once (on the last pass) */
     for (int it = 0; it < cfg->solver_iterations * cfg->solver_inner; ++it) {
@@ -1798,6 +1846,17 @@ static void substep(const struct TfHandle_* H, Env* e, float h) {
                 cz_apply(c->r, dl, inv_m, inv_I, v, w);
             }
         }
+        for (int i = 0; i < 4 && surf; ++i) {     /* cube - boundary above the ring: rows N (normal), T, U, behind the ring's */
+            ConeContact* g = &cone[i];
+            if (!g->active) continue;
+            float lim = 0.0f;
+            for (int d = 0; d < 3; ++d) {
+                const float vr = g_vrel(&g->d[3 * d], &g->a[3 * d], v, w);
+                const float dl = (d == 0) ? solve_normal(&g->lam[0], g->Dinv[0], vr, g->bias) : solve_tangent(&g->lam[d], g->Dinv[d], vr, lim);
+                if (d == 0) lim = mu_cw * g->lam[0];
+                g_apply(&g->d[3 * d], &g->a[3 * d], dl, inv_m, inv_I, v, w);
+            }
+        }
     }
     /* ---- impulses kept for the next substep; fingertip wrench sensor: contact impulses / h, world frame, about the
      * tip-link origin (contacts on the distal link and the fingertip only) ---- */
@@ -1829,10 +1888,14 @@ static void substep(const struct TfHandle_* H, Env* e, float h) {
         }
     }
     for (int i = 0; i < 4; ++i) for (int d = 0; d < 3; ++d) { e->lam_cf[i][d] = cf[i].lam[d]; e->lam_cw[i][d] = cwl[i].lam[d]; }
+    for (int i = 0; i < 4 && surf; ++i) {        /* a live corner above the ring keeps its impulses in the slot's rows */
+        if (cone[i].active) for (int d = 0; d < 3; ++d) e->lam_cw[i][d] = cone[i].lam[d];
+    }
     e->cf_face = cf_face;
     {   /* 0 while no corner touches the boundary: the wall-corner rows then carry nothing */
         int any_wall = 0;
         for (int i = 0; i < 4; ++i) any_wall |= cwl[i].active;
+        for (int i = 0; i < 4 && surf; ++i) any_wall |= cone[i].active;
         e->cw_face = any_wall ? cw_face : 0.0f;
     }
     /* ---- integrate ---- */

@@ -104,7 +104,86 @@ def oracle_rollout(oracle, n, steps, cfg_name, **kw):
     return _ORACLE_ROLLOUTS[key]
 
 
-def rollout(lib, device, n, steps, cfg_name, seed=3, episode_length=40, extra=None, variant=None):
+LOW_RING_Z0 = -0.01      # wall_z[0] of the low-ring model: the vertical ring ends below the floor, the whole boundary is cone
+
+
+def surface_model(lib, low_ring=False, base=None):
+    """the default model (or `base`) with TfModel.cube_wall_surface on; `low_ring`: wall_z[0] = LOW_RING_Z0, the other knots as they are - a cube
+    that slides to the boundary on the floor then touches the cone with its lower corners, so random rollouts run the surface rows all the time
+    (on the shipped profile they almost never do)"""
+    m = base if base is not None else lib.default_model()
+    m.cube_wall_surface = 1
+    if low_ring:
+        m.wall_z[0] = LOW_RING_Z0
+    return m
+
+
+def cube_corner_positions(state, m):
+    """The eight corners (+-h, +-h, +-h) of every env's cube in the pose of `state` (TF_STATE_ROWS x N), relative to the stage centre: h = cube_half
+    of model `m` times the env's cube-size factor, rotated by the cube quaternion (x, y, z, w), the env's stage offset subtracted (0 without the
+    extended domain randomisation).  -> (px, py, pz), each (8, N), and h (N,)"""
+    from leibnizgym_amd import _capi as capi
+    st = np.asarray(state, dtype=np.float64)
+    dr = st[capi.S_DR:capi.S_DR + capi.TF_NUM_DR]
+    hc = float(m.cube_half) * dr[1]                                               # cube size of the env (1 without randomisation)
+    cp = st[capi.S_CUBE_P:capi.S_CUBE_P + 3].copy()
+    cp[0:2] -= dr[capi.DR_STAGE_POS:capi.DR_STAGE_POS + 2]
+    x, y, z, w = st[capi.S_CUBE_Q:capi.S_CUBE_Q + 4]
+    px, py, pz = [], [], []
+    for sx in (-1.0, 1.0):
+        for sy in (-1.0, 1.0):
+            for sz in (-1.0, 1.0):
+                lx, ly, lz = sx * hc, sy * hc, sz * hc
+                tx = 2 * (y * lz - z * ly); ty = 2 * (z * lx - x * lz); tz = 2 * (x * ly - y * lx)
+                px.append(cp[0] + lx + w * tx + (y * tz - z * ty))
+                py.append(cp[1] + ly + w * ty + (z * tx - x * tz))
+                pz.append(cp[2] + lz + w * tz + (x * ty - y * tx))
+    return np.array(px), np.array(py), np.array(pz), hc
+
+
+def cone_census(state, m):
+    """Per env (bool array): the pose of `state` has a boundary contact (cw_face != 0) and a cube corner - any of the eight - above wall_z[0] within
+    contact_slack of the boundary profile of model `m`.  Geometric, from the pose alone: what says that the rows of the tilted surface
+    (TfModel.cube_wall_surface) were live in the step that left this state."""
+    from leibnizgym_amd import _capi as capi
+    px, py, pz, _ = cube_corner_positions(state, m)
+    wz, wr = np.array(m.wall_z[:], dtype=np.float64), np.array(m.wall_r[:], dtype=np.float64)
+    r_at = np.where(pz < wz[-1], np.interp(pz, wz, wr), np.inf)                    # nothing above the last knot
+    near = (pz > wz[0]) & (r_at - np.hypot(px, py) < float(m.contact_slack))
+    return near.any(axis=0) & (np.asarray(state)[capi.S_CW_FACE] != 0)
+
+
+def place_cubes_at_the_boundary(eng, m, first=0, speed=0.4):
+    """Overwrite the cube state of envs first.. (after a reset, the same call on every engine of a comparison): the cube lies on the floor, one face
+    towards the boundary, its lower outward corners 6 mm inside the profile of model `m` at floor height, sliding outward at `speed` - env i at the
+    azimuth 2.4 i rad, so that the envs of a small population meet the boundary at different places within the first steps.  For the low-ring model
+    (surface_model): the corners then arrive on the cone."""
+    from leibnizgym_amd import _capi as capi
+    n = eng.num_envs - first
+    hc = float(m.cube_half)
+    wz, wr = np.array(m.wall_z[:], dtype=np.float64), np.array(m.wall_r[:], dtype=np.float64)
+    r_corner = float(np.interp(0.0, wz, wr)) - 0.006
+    r_centre = np.sqrt(r_corner * r_corner - hc * hc) - hc                       # corners at (r_centre + hc, +-hc) in the frame of the azimuth
+    phi = 2.4 * np.arange(n, dtype=np.float64)
+    cube = np.zeros((13, n))
+    cube[0], cube[1], cube[2] = r_centre * np.cos(phi), r_centre * np.sin(phi), hc
+    cube[5], cube[6] = np.sin(phi / 2), np.cos(phi / 2)                          # yaw phi (quaternion x, y, z, w)
+    cube[7], cube[8] = speed * np.cos(phi), speed * np.sin(phi)
+    eng.cube[:, first:] = torch.tensor(cube, dtype=torch.float32).to(eng.cube.device)
+
+
+def census_summary(flags):
+    """flags: list of cone_census arrays of consecutive compared snapshots -> (env-steps counted, env-steps in all, envs that ever had one, envs in
+    which the flag changes between two consecutive compared snapshots: a corner went from no boundary rows to live surface rows or back - on the
+    low-ring model that is all a change can be, there is no ring a corner could cross over from)"""
+    f = np.array(flags, dtype=bool)
+    changes = (f[1:] != f[:-1]).any(axis=0) if len(f) > 1 else np.zeros(f.shape[1], dtype=bool)
+    return int(f.sum()), int(f.size), int(f.any(axis=0).sum()), int(changes.sum())
+
+
+def rollout(lib, device, n, steps, cfg_name, seed=3, episode_length=40, extra=None, variant=None, surface=None, place=False):
+    """`surface`: None, "default" (TfModel.cube_wall_surface on) or "low_ring" (the same on the low-ring model: surface_model); `place`: the cubes
+    are put at the boundary after the reset (place_cubes_at_the_boundary)"""
     kw = dict(CONFIGS[cfg_name])
     kw.update(extra or {})
     clipping = kw.pop("_clipping", None)
@@ -113,6 +192,9 @@ def rollout(lib, device, n, steps, cfg_name, seed=3, episode_length=40, extra=No
         kw["model"] = lib.default_model()
         for name, value in model_edit.items():
             setattr(kw["model"], name, value)
+    if surface is not None:
+        assert surface in ("default", "low_ring"), surface
+        kw["model"] = surface_model(lib, low_ring=surface == "low_ring", base=kw.get("model"))
     cfg = make_config(lib, n, seed=seed, episode_length=episode_length, **kw)
     eng = TrifingerEngine(cfg, device=device, lib=lib)
     if variant is not None:
@@ -121,6 +203,8 @@ def rollout(lib, device, n, steps, cfg_name, seed=3, episode_length=40, extra=No
     if clipping:
         eng.set_clipping(*clipping)
     eng.reset()
+    if place:                                        # hand-placed cubes at the boundary (place_cubes_at_the_boundary), the same on every backend
+        place_cubes_at_the_boundary(eng, cfg.model)
     snaps = [snapshot(eng)]
     for t in range(steps):
         act = actions_for(t, n, eng.action_dim, seed).to(device)

@@ -153,23 +153,25 @@ def contact_live(gap, vn0, h):
     return gap < MARGIN and gap < SLACK + h * max(0.0, -vn0)
 
 
-def wall_radius_at(z):
+def wall_radius_at(z, profile=None):
     """the boundary profile of the spec: piecewise linear through the knots (WALL_Z[i], WALL_R[i]), a vertical ring below the first
-    knot, no wall above the last"""
-    if not z < WALL_Z[-1]:
+    knot, no wall above the last.  `profile`: other knots (wall_z, wall_r) than the default model's"""
+    wz, wr = profile if profile is not None else (WALL_Z, WALL_R)
+    if not z < wz[-1]:
         return 1000.0
-    return float(np.interp(z, WALL_Z, WALL_R))
+    return float(np.interp(z, wz, wr))
 
 
-def wall_tilt(z):
+def wall_tilt(z, profile=None):
     """(cos, sin) of the slope angle of the profile segment at height z: the inward surface normal of the boundary is (cos * n_h, sin) with n_h the
     inward horizontal unit vector; (1, 0) on the vertical ring below the first knot.  Spec: the FINGERTIP contact uses the tilted normal and the
     distance to the tilted surface, the cube corners the horizontal normal."""
-    i = int(np.searchsorted(WALL_Z, z, side="left")) - 1          # z > WALL_Z[i]
+    wz, wr = profile if profile is not None else (WALL_Z, WALL_R)
+    i = int(np.searchsorted(wz, z, side="left")) - 1              # z > wz[i]
     if i < 0:
         return 1.0, 0.0
-    i = min(i, len(WALL_Z) - 2)
-    sl = (WALL_R[i + 1] - WALL_R[i]) / (WALL_Z[i + 1] - WALL_Z[i])
+    i = min(i, len(wz) - 2)
+    sl = (wr[i + 1] - wr[i]) / (wz[i + 1] - wz[i])
     return 1.0 / np.sqrt(1.0 + sl * sl), sl / np.sqrt(1.0 + sl * sl)
 
 
@@ -220,9 +222,10 @@ def box_spec(size, density, gyroscopic=True):
     return {"half": size / 2.0, "mass": mass, "inertia": inertia, "gyroscopic": gyroscopic}
 
 
-def ref_substep(q, qd, cube, tau, h, gravity=(0.0, 0.0, -9.81), tol=1e-13, max_sweeps=200000, box=None, ff_middle=True):
+def ref_substep(q, qd, cube, tau, h, gravity=(0.0, 0.0, -9.81), tol=1e-13, max_sweeps=200000, box=None, ff_middle=True, profile=None):
     """One substep of length h in fp64.  q, qd, tau: (9,), cube: (13,) [p, quat xyzw, v, w].  `box`: a `box_spec` for a
     general box object (full world-frame inertia tensor here - the product's inertia-scaled coordinates are not used).
+    `profile`: knots (wall_z, wall_r) of the boundary other than the default model's.
     Returns (qd_new (9,), cube_v (3,), cube_w (3,), details)."""
     q, qd, cube, tau = (np.asarray(a, dtype=np.float64) for a in (q, qd, cube, tau))
     cp, cq, cv, cw = cube[0:3], cube[3:7], cube[7:10], cube[10:13]
@@ -369,8 +372,8 @@ def ref_substep(q, qd, cube, tau, h, gravity=(0.0, 0.0, -9.81), tol=1e-13, max_s
             else:
                 if not rho > 1e-6:
                     continue
-                wc, wsn = wall_tilt(B[2])
-                gp, n = (wall_radius_at(B[2]) - rho) * wc - rad, np.array([-B[0] / rho * wc, -B[1] / rho * wc, wsn])
+                wc, wsn = wall_tilt(B[2], profile)
+                gp, n = (wall_radius_at(B[2], profile) - rho) * wc - rad, np.array([-B[0] / rho * wc, -B[1] / rho * wc, wsn])
             if gp < MARGIN:
                 t1, t2 = tangent_basis(n)
                 Jm = np.zeros((3, 15))
@@ -410,7 +413,7 @@ def ref_substep(q, qd, cube, tau, h, gravity=(0.0, 0.0, -9.81), tol=1e-13, max_s
             r = R @ yv
             P = cp + r
             rho = np.hypot(P[0], P[1])
-            gap = wall_radius_at(P[2]) - rho
+            gap = wall_radius_at(P[2], profile) - rho
             if gap < MARGIN and rho > 1e-6:
                 n = np.array([-P[0] / rho, -P[1] / rho, 0.0])
                 t = np.array([-n[1], n[0], 0.0])

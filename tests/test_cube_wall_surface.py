@@ -3,12 +3,14 @@
 The stage is a bowl - a vertical ring up to wall_z[0], above it a cone that leans outward.  The default model gives the cube corners the HORIZONTAL
 normal at every height (tests/test_contact_scenarios.py: test_cube_corner_on_the_cone_keeps_the_horizontal_normal); with the switch on a corner above
 wall_z[0] gets the rows of the tilted surface - normal (c n_h, s), gap (r(z) - rho) c, friction along the horizontal tangent and the up-slope tangent
-(-s n_h, c) - as the fingertips have them.  Only the 256-register kernels of the cube (EXT 0, 1) carry it; the oracle does not model it.
+(-s n_h, c) - as the fingertips have them.  Only the 256-register kernels of the cube (EXT 0, 1) carry it; the oracle restates it in scalar C, and
+tests/test_parity_surface.py holds the kernels to it bit for bit.  The oracle is a referee only if it is right on its own, so the two independent
+checks run on both backends:
 
 * known answer: a weightless cube flying outward at 110 mm meets the cone with its two lower outward corners and is thrown upward along the surface
   normal (fails without the feature: the default model leaves dv_z at 0);
-* fp64 restatement: the cube cases of test_contact_lcp_reference._boundary_cases against an independent fixed point whose cube-boundary rows are the
-  tilted ones;
+* fp64 restatement: the cube cases of test_contact_lcp_reference._boundary_cases, and cubes that lie on the floor of the low-ring model
+  (wall_z[0] below the floor: their LOWER corners are on the cone), against an independent fixed point whose cube-boundary rows are the tilted ones;
 * where the two models coincide - every corner on the vertical ring - the switch changes nothing: HIP with the switch on == the oracle on the default
   model, bit for bit, env by env, until the env's cube brings a corner above wall_z[0] near the boundary;
 * selection of the instantiation, guards, and a soak.
@@ -50,17 +52,30 @@ def test_bad_cube_wall_normal_is_a_value_error(oracle):
                      device="cpu", verbose=False, lib=oracle)
 
 
-def test_the_oracle_refuses_the_switch(oracle):
-    """the oracle does not know the field and would step the default model without a word: the engine refuses"""
+def test_the_oracle_steps_the_switch_and_refuses_what_the_kernels_refuse(oracle):
+    """No silent fallback: with the switch on the oracle computes something else than with it off (and what it computes is the known answer:
+    _check_known_answer), and it answers the configurations the HIP library refuses with the same error classes - from its own tf_create."""
     from leibnizgym_amd.envs import TrifingerEnv
-    m = oracle.default_model()
-    _surface(m)
-    with pytest.raises(NotImplementedError, match="cube_wall_surface"):
-        TrifingerEngine(make_config(oracle, 2, model=m), device="cpu", lib=oracle)
-    with pytest.raises(NotImplementedError, match="cube_wall_surface"):
-        TrifingerEnv(config={"num_instances": 2, "command_mode": "torque", "native": {"cube_wall_normal": "surface"}},
-                     device="cpu", verbose=False, lib=oracle)
-    # the default key builds the default model
+    b1, a1, lam1, _ = _flying_cube_hits_the_cone(oracle, "cpu", None, surface=True)
+    b0, a0, lam0, _ = _flying_cube_hits_the_cone(oracle, "cpu", None, surface=False)
+    assert np.array_equal(b0, b1) and not np.array_equal(a0[7:13], a1[7:13])      # same start, another twist after the step
+    assert abs(a0[9] - b0[9]) < 1e-6 and a1[9] - b1[9] > 0.03                     # switch off: no vertical impulse; on: thrown upward
+    kw = dict(pu.CONFIGS["d4_torque_asym"])
+    bad = oracle.default_model()
+    bad.cube_wall_surface = 2
+    h = C.c_void_p()
+    assert oracle.tf_create(C.byref(make_config(oracle, 64, model=bad, **kw)), C.byref(h)) == capi.TF_ERR_INVALID_ARG
+    with pytest.raises(ValueError):
+        TrifingerEngine(make_config(oracle, 64, model=bad, **kw), device="cpu", lib=oracle)
+    mb = oracle.box_model([0.02, 0.08, 0.02], 500.0)
+    _surface(mb)
+    assert oracle.tf_create(C.byref(make_config(oracle, 64, model=mb, **kw)), C.byref(h)) == capi.TF_ERR_UNSUPPORTED
+    with pytest.raises(NotImplementedError):
+        TrifingerEngine(make_config(oracle, 64, model=mb, **kw), device="cpu", lib=oracle)
+    # the keys of the env config: "surface" sets the switch (and the oracle steps it), "horizontal" builds the default model
+    env = TrifingerEnv(config={"num_instances": 2, "command_mode": "torque", "native": {"cube_wall_normal": "surface"}},
+                       device="cpu", verbose=False, lib=oracle)
+    assert env._engine.cfg.model.cube_wall_surface == 1
     env = TrifingerEnv(config={"num_instances": 2, "command_mode": "torque", "native": {"cube_wall_normal": "horizontal"}},
                        device="cpu", verbose=False, lib=oracle)
     assert env._engine.cfg.model.cube_wall_surface == 0
@@ -76,8 +91,9 @@ def _flying_cube_hits_the_cone(lib, device, variant, surface=True, v_r=0.3):
         m.mu_cube_wall = 0.0                                   # the normal row alone
         m.cube_wall_surface = 1 if surface else 0
     eng = T.engine(lib, device=device, model_edit=edit, gravity=(0.0, 0.0, 0.0), **T.HOLD)
-    eng.kernel_variant = variant
-    assert eng.kernel_variant == variant
+    if variant is not None:                                    # (the oracle has no variants)
+        eng.kernel_variant = variant
+        assert eng.kernel_variant == variant
     m = lib.default_model()
     f32 = dict(dtype=torch.float32, device=device)
     r_at = T.wall_radius_at(0.11 - 0.0325, m)
@@ -100,10 +116,8 @@ def _outward_corner_n0(cube):
     return [abs(p[0]) / np.hypot(p[0], p[1]) for p in xs]
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("variant", ["wide", "wide_helpers"])
-def test_cube_corner_on_the_cone_gets_the_surface_normal_gpu(hip, variant):
-    before, after, lam, m = _flying_cube_hits_the_cone(hip, "cuda:0", variant)
+def _check_known_answer(lib, device, variant):
+    before, after, lam, m = _flying_cube_hits_the_cone(lib, device, variant)
     assert (lam[0::3] > 0).sum() == 2, lam                                 # the two lower outward corners pushed
     dv = after[7:10] - before[7:10]
     sl = (float(m.wall_r[2]) - float(m.wall_r[1])) / (float(m.wall_z[2]) - float(m.wall_z[1]))   # s / c of the segment the corners are on
@@ -117,17 +131,33 @@ def test_cube_corner_on_the_cone_gets_the_surface_normal_gpu(hip, variant):
     assert lo <= ratio <= hi, (ratio, lo, hi, sl)
     assert abs(ratio - sl) < 0.03 * sl                                     # = (s / c) |dv_x| to the corners' 1.5 % off-axis share
     # the same instantiation without the switch: the horizontal normal, no vertical impulse
-    b0, a0, _, _ = _flying_cube_hits_the_cone(hip, "cuda:0", variant, surface=False)
+    b0, a0, _, _ = _flying_cube_hits_the_cone(lib, device, variant, surface=False)
     assert abs(a0[9] - b0[9]) < 1e-6
 
 
+def test_cube_corner_on_the_cone_gets_the_surface_normal(oracle):
+    _check_known_answer(oracle, "cpu", None)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant", ["wide", "wide_helpers"])
+def test_cube_corner_on_the_cone_gets_the_surface_normal_gpu(hip, variant):
+    _check_known_answer(hip, "cuda:0", variant)
+
+
 # ---- fp64 restatement with the tilted cube-boundary rows -------------------------------------------------------------------------------
-def ref_substep_surface(q, qd, cube, tau, h, max_sweeps=50000, tol=1e-13):
+class NoFixedPoint(AssertionError):
+    """the fp64 Gauss-Seidel of ref_substep_surface did not settle: the state has no reference value"""
+
+
+def ref_substep_surface(q, qd, cube, tau, h, max_sweeps=50000, tol=1e-13, profile=None):
     """physics_ref.ref_substep with the cube-boundary rows of the SURFACE: directions (n, t, u) = ((c n_h, s), (-n_h1, n_h0, 0), (-s n_h, c)) and the
     gap (r(z) - rho) c for a corner above WALL_Z[0] (the ring's rows below it).  Every other row is the reference's own (its contact generation,
     its matrices); its cube-boundary rows - built just before the nine limit rows - are replaced, and the problem is solved to the fixed point again.
+    `profile`: knots (wall_z, wall_r) other than the default model's.  Raises NoFixedPoint where the iteration does not settle.
     Returns (qd, cube v, cube w, number of cube-boundary corners that push)."""
-    det = PR.ref_substep(q, qd, cube, tau, h, max_sweeps=1)[3]
+    wz0 = (profile[0] if profile is not None else PR.WALL_Z)[0]
+    det = PR.ref_substep(q, qd, cube, tau, h, max_sweeps=1, profile=profile)[3]
     rows, Minv, v_start = det["rows"], det["Minv"], det["v_start"]
     nw = 3 * det["n_wall"]
     head, limits = rows[:len(rows) - 9 - nw], rows[len(rows) - 9:]
@@ -150,8 +180,8 @@ def ref_substep_surface(q, qd, cube, tau, h, max_sweeps=50000, tol=1e-13):
             r = R @ yv
             P = cp + r
             rho = np.hypot(P[0], P[1])
-            wc, wsn = PR.wall_tilt(P[2]) if P[2] > PR.WALL_Z[0] else (1.0, 0.0)
-            gap = (PR.wall_radius_at(P[2]) - rho) * wc
+            wc, wsn = PR.wall_tilt(P[2], profile) if P[2] > wz0 else (1.0, 0.0)
+            gap = (PR.wall_radius_at(P[2], profile) - rho) * wc
             if not (gap < PR.MARGIN and rho > 1e-6):
                 continue
             nh = np.array([-P[0] / rho, -P[1] / rho])
@@ -194,13 +224,15 @@ def ref_substep_surface(q, qd, cube, tau, h, max_sweeps=50000, tol=1e-13):
                 change = max(change, abs(dl) * np.sqrt(d))
         if change < tol:
             break
-    assert sweeps < max_sweeps, "the reference did not reach its fixed point"
+    if sweeps >= max_sweeps:
+        raise NoFixedPoint("the reference did not reach its fixed point")
     return v[0:9].copy(), v[9:12].copy(), v[12:15].copy(), sum(r.lam > 0 for r in wall if r.kind == "normal")
 
 
-def product_substep_surface(lib, device, variant, q, qd, cube, tau, sweeps):
-    eng = T.engine(lib, device=device, model_edit=_surface, dt=H, substeps=1, solver_iterations=sweeps)
-    eng.kernel_variant = variant
+def product_substep_surface(lib, device, variant, q, qd, cube, tau, sweeps, low_ring=False):
+    eng = T.engine(lib, device=device, model_edit=lambda m: pu.surface_model(lib, low_ring=low_ring, base=m), dt=H, substeps=1, solver_iterations=sweeps)
+    if variant is not None:
+        eng.kernel_variant = variant
     f32 = dict(dtype=torch.float32, device=device)
     eng.q[:, 0] = torch.tensor(q, **f32)
     eng.qd[:, 0] = torch.tensor(qd, **f32)
@@ -212,23 +244,110 @@ def product_substep_surface(lib, device, variant, q, qd, cube, tau, sweeps):
     return st[9:18], st[25:28], st[28:31]
 
 
-@pytest.mark.gpu
-def test_surface_rows_agree_with_the_independent_solution_gpu(hip):
-    cases = [c for c in _boundary_cases(np.random.default_rng(77), 20) if np.hypot(c[2][0], c[2][1]) > 1e-6]     # the cube cases
-    errs, hits = {"wide": [], "wide_helpers": []}, 0
-    for q, qd, cube, tau in cases:
-        ref_qd, ref_v, ref_w, n_push = ref_substep_surface(q, qd, cube, tau, H)
-        hits += n_push > 0
+def _low_ring_cases(rng, n, m):
+    """cubes that lie on the floor of the low-ring model `m` (pu.surface_model: the vertical ring ends below the floor) and slide into the boundary:
+    any yaw, the nearest lower corner within -2 .. +3 mm of the profile at floor height - on the cone; the fingers at rest, far from the cube"""
+    out = []
+    hc = PR.CUBE_HALF
+    r0 = float(np.interp(0.0, list(m.wall_z), list(m.wall_r)))                     # the profile at the height of the lower corners
+    q_rest = np.array([0.0, 0.9, -1.7] * 3)
+    while len(out) < n:
+        phi, yaw, g0 = rng.uniform(0, 2 * np.pi), rng.uniform(0, 2 * np.pi), rng.uniform(-0.002, 0.003)
+        ed = np.array([np.cos(phi), np.sin(phi), 0.0])
+        cq = np.array([0.0, 0.0, np.sin(yaw / 2), np.cos(yaw / 2)])
+        corners = np.array([[sx, sy, -hc] for sx in (-hc, hc) for sy in (-hc, hc)]) @ PR.quat_rot(cq).T
+        lo, hi = 0.05, 0.30
+        for _ in range(50):
+            mid = 0.5 * (lo + hi)
+            far = max(np.hypot(*(mid * ed + c)[0:2]) for c in corners)
+            lo, hi = (mid, hi) if r0 - far > g0 else (lo, mid)
+        c = lo * ed + np.array([0.0, 0.0, hc])
+        v = ed * rng.uniform(0.2, 1.0) + np.append(rng.normal(size=2) * 0.1, 0.0)
+        out.append((q_rest.copy(), np.zeros(9), np.concatenate([c, cq, v, np.append(np.zeros(2), rng.uniform(-3, 3))]), np.zeros(9)))
+    return out
+
+
+LOW_RING_CASES, LOW_RING_MAX_SKIPPED = 8, 4
+
+
+def _check_surface_rows(lib, device, variants):
+    """the product with the switch on (each of `variants`) against ref_substep_surface at 8 and 1024 sweeps, cold start, in two groups: the cube
+    cases of _boundary_cases on the default profile (upper corners on the cone) and _low_ring_cases on the low-ring model (lower corners of a lying
+    cube).  The three tolerances (1024 sweeps: max 1e-3, median 2e-5; 8 sweeps: median 5e-3) hold for the default group alone, as before the
+    low-ring cases existed, and for both groups together.  The low-ring group alone meets the two converged ones - that is what says the rows are
+    right (measured on the oracle: max 8.0e-7, median 2.3e-7) - but not the 8-sweep median: 8 COLD sweeps on a lying cube (four floor corners
+    with friction plus the corners on the cone, the slow case of Gauss-Seidel: DESIGN.md section 2) leave median 1.8e-2, max 5.0e-2, a truncation
+    figure of the shipped sweep count and not of the surface rows.  For that group the 8-sweep bound is the one test_contact_lcp_reference._check
+    states for the shipped cold sweeps on resting contacts: max 0.3.
+
+    A lying cube has four floor corners besides the boundary's: eight floor friction rows for the three planar degrees of freedom, a redundant
+    (singular) friction problem whose impulses are not unique.  The fp64 Gauss-Seidel, whose stopping rule is on the impulse changes, then need not
+    settle: on some of these states it keeps moving impulses between the redundant rows while the clipped limits mu * lambda_n move with it (not a
+    matter of patience: 200 000 sweeps do not settle the first candidate either).  Such a state has no reference value and is left out, as in
+    test_contact_lcp_reference._run - measured on the reference alone: 3 of the first 11 candidates; more than LOW_RING_MAX_SKIPPED of 12 fails."""
+    m_low = pu.surface_model(lib, low_ring=True)
+    low_profile = ([float(z) for z in m_low.wall_z], [float(r) for r in m_low.wall_r])
+    cases = [(c, False) for c in _boundary_cases(np.random.default_rng(77), 20) if np.hypot(c[2][0], c[2][1]) > 1e-6]     # the cube cases
+    cases += [(c, True) for c in _low_ring_cases(np.random.default_rng(78), LOW_RING_CASES + LOW_RING_MAX_SKIPPED, m_low)]
+    errs, low_flags, hits, skipped = {v: [] for v in variants}, [], [], 0
+    for (q, qd, cube, tau), low in cases:
+        if low and sum(low_flags) == LOW_RING_CASES:
+            break
+        try:
+            ref_qd, ref_v, ref_w, n_push = ref_substep_surface(q, qd, cube, tau, H, profile=low_profile if low else None)
+        except NoFixedPoint:
+            assert low, "a default-profile case without a reference value"
+            skipped += 1
+            continue
+        low_flags.append(low)
+        hits.append(n_push > 0)
         for variant in errs:
-            errs[variant].append([scaled_error(product_substep_surface(hip, "cuda:0", variant, q, qd, cube, tau, k), (ref_qd, ref_v, ref_w))
+            errs[variant].append([scaled_error(product_substep_surface(lib, device, variant, q, qd, cube, tau, k, low_ring=low), (ref_qd, ref_v, ref_w))
                                   for k in (8, 1024)])
-    n = len(cases)
-    assert n >= 12 and hits >= n // 2, (hits, n)
+    low_flags, hits = np.array(low_flags), np.array(hits)
+    assert skipped <= LOW_RING_MAX_SKIPPED, skipped
+    groups = {"default profile": ~low_flags, "low ring": low_flags, "both": np.ones(len(hits), dtype=bool)}
+    assert groups["default profile"].sum() >= 12 and groups["low ring"].sum() == LOW_RING_CASES, (len(hits), low_flags.sum())
     for variant, e in errs.items():
         e = np.array(e)
-        print(f"\n{variant}: cube cases with a pushing corner on the cone {hits} of {n};  8 sweeps median {np.median(e[:, 0]):.2e} "
-              f"max {e[:, 0].max():.2e};  1024 sweeps median {np.median(e[:, 1]):.2e} max {e[:, 1].max():.2e}")
-        assert e[:, 1].max() < 1e-3 and np.median(e[:, 1]) < 2e-5 and np.median(e[:, 0]) < 5e-3, (variant, e)
+        for name, g in groups.items():
+            n, h, eg = int(g.sum()), int(hits[g].sum()), e[g]
+            print(f"\n{variant} {name}: cube cases with a pushing corner on the cone {h} of {n} ({skipped} low-ring states without a reference value);  "
+                  f"8 sweeps median {np.median(eg[:, 0]):.2e} max {eg[:, 0].max():.2e};  1024 sweeps median {np.median(eg[:, 1]):.2e} max {eg[:, 1].max():.2e}")
+        for name, g in groups.items():
+            n, h, eg = int(g.sum()), int(hits[g].sum()), e[g]
+            assert h >= n // 2, (variant, name, h, n)
+            assert eg[:, 1].max() < 1e-3 and np.median(eg[:, 1]) < 2e-5, (variant, name, eg)
+            if name == "low ring":
+                assert eg[:, 0].max() < 0.3, (variant, name, eg)
+            else:
+                assert np.median(eg[:, 0]) < 5e-3, (variant, name, eg)
+
+
+def test_surface_rows_agree_with_the_independent_solution(oracle):
+    _check_surface_rows(oracle, "cpu", [None])
+
+
+@pytest.mark.gpu
+def test_surface_rows_agree_with_the_independent_solution_gpu(hip):
+    _check_surface_rows(hip, "cuda:0", ["wide", "wide_helpers"])
+
+
+def test_low_ring_rollout_runs_the_surface_rows_on_the_oracle(oracle):
+    """A few hundred steps of the oracle alone with the switch on, on the low-ring model with every domain-randomisation feature (stage offsets,
+    per-body friction), cubes placed at the boundary: the rollout keeps corners on the cone (census of parity_util), stays finite and differs from
+    the same rollout with the switch off.  Also part of the selection of tests/test_oracle_sanitizer.py: the new indexing under ASan / UBSan."""
+    n, steps, cfg_name = 96, 300, "d4_domain_randomization_extended"
+    on = pu.rollout(oracle, "cpu", n, steps, cfg_name, episode_length=120, surface="low_ring", place=True)
+    m = pu.surface_model(oracle, low_ring=True)
+    hit, total, envs, changed = pu.census_summary([pu.cone_census(s["state"], m) for s in on])
+    print(f"\nlow-ring oracle rollout: {hit} of {total} env-steps with a corner on the cone, {envs} of {n} envs, {changed} envs with a change")
+    # (the placement ignores the env's stage offset of up to 20 mm and its cube size: not every cube arrives - half of them must)
+    assert hit > 0.03 * total and envs >= n // 2 and changed >= n // 2, (hit, total, envs, changed)
+    assert all(np.isfinite(s["state"]).all() and np.isfinite(s["obs"]).all() for s in on)
+    assert float(sum(s["info"][capi.INFO_NUM_NONFINITE] for s in on)) == 0.0
+    off = pu.rollout(oracle, "cpu", n, 20, cfg_name, episode_length=120, extra={"_model_edit": {"wall_z": m.wall_z}}, place=True)
+    assert np.array_equal(off[0]["state"], on[0]["state"]) and not np.array_equal(off[20]["state"], on[20]["state"])
 
 
 # ---- on the vertical ring the two models coincide, bit for bit ---------------------------------------------------------------------------
@@ -242,26 +361,12 @@ def _cone_event(st, m, dt):
     every step (_ring_parity), each with the corner speed bound |v| + 2 h_c |w| of its own state, doubled, over the whole control step (two
     substeps), plus 5 mm - a corner that crosses it within one step has to be faster than both end states say by more than a factor of two.  The
     rollout is deterministic (fixed seed and actions), so the window cannot make the test flaky: an env it missed would fail on every run."""
-    dr = st[capi.S_DR:capi.S_DR + capi.TF_NUM_DR]
-    hc = float(m.cube_half) * dr[1]                                               # cube size of the env (1 without randomisation)
-    cp = st[capi.S_CUBE_P:capi.S_CUBE_P + 3]
-    cp = cp - np.concatenate([dr[capi.DR_STAGE_POS:capi.DR_STAGE_POS + 2], np.zeros((1, cp.shape[1]))])      # relative to the stage centre
-    q = st[capi.S_CUBE_Q:capi.S_CUBE_Q + 4].T
+    px, py, pz, hc = pu.cube_corner_positions(st, m)                               # (8, N) each, relative to the stage centre
     speed = np.linalg.norm(st[capi.S_CUBE_V:capi.S_CUBE_V + 3], axis=0) + np.linalg.norm(st[capi.S_CUBE_W:capi.S_CUBE_W + 3], axis=0) * hc * 2.0
     reach = float(m.contact_slack) + 0.005 + 2.0 * speed * dt
     wz, wr = np.array(m.wall_z[:], dtype=np.float64), np.array(m.wall_r[:], dtype=np.float64)
-    ev = np.zeros(cp.shape[1], dtype=bool)
-    for s in np.array([[sx, sy, sz] for sx in (-1, 1) for sy in (-1, 1) for sz in (-1, 1)], dtype=np.float64):
-        x, y, z, w = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
-        loc = s[:, None] * hc                                                     # (3, N)
-        # rotate by the unit quaternion (x, y, z, w)
-        tx = 2 * (y * loc[2] - z * loc[1]); ty = 2 * (z * loc[0] - x * loc[2]); tz = 2 * (x * loc[1] - y * loc[0])
-        px = cp[0] + loc[0] + w * tx + (y * tz - z * ty)
-        py = cp[1] + loc[1] + w * ty + (z * tx - x * tz)
-        pz = cp[2] + loc[2] + w * tz + (x * ty - y * tx)
-        gap = np.interp(pz, wz, wr) - np.hypot(px, py)
-        ev |= (pz > wz[0] - reach) & (gap < reach)
-    return ev
+    gap = np.interp(pz, wz, wr) - np.hypot(px, py)
+    return ((pz > wz[0] - reach) & (gap < reach)).any(axis=0)
 
 
 def _ring_parity(hip, oracle, cfg_name, n=4096, steps=200, seed=3):
