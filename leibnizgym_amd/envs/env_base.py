@@ -80,6 +80,13 @@ class IsaacEnvBase:
         self._validate_sim_config()
         # the native engine (buffers + handle) is created by the task
         self._engine = self._create_engine()
+        # the offscreen renderer of the collision model (leibnizgym_amd/render.py): only with visualize=True, only on a cuda device
+        self._renderer = None
+        self._render_cfg = None
+        self._render_camera = None
+        self._frame_index = 0
+        if self.visualize:
+            self._create_renderer()
         self.seed(self.config["seed"])
 
     # ------------------------------------------------------------------------------------------
@@ -106,8 +113,27 @@ class IsaacEnvBase:
     def get_sim_params(self) -> dict:
         return self.config["sim"]
 
+    def _create_renderer(self):
+        """`native.render` = {width, height, envs: [ids], fov_deg, record_dir, shading} (all optional; ValueError on a bad value).  The module is
+        imported here and nowhere else: an env with visualize=False never loads it."""
+        from .. import render as tfr
+        rc = tfr.parse_render_config((self.config.get("native") or {}).get("render"), self.num_instances)
+        self._render_cfg = rc
+        self._render_camera = (tfr.DEFAULT_EYE, tfr.DEFAULT_TARGET)
+        if self._engine.device.type != "cuda":          # the injected CPU library of the tests: no kernel to draw with
+            return
+        self._renderer = tfr.SceneRenderer(self._engine.cfg.model, width=rc["width"], height=rc["height"], max_views=len(rc["envs"]),
+                                           device=self._engine.device, shading=rc["shading"])
+        self._renderer.set_views(rc["envs"], self._engine.num_envs)
+        self._renderer.set_camera(*self._render_camera, rc["fov_deg"])
+
     def set_camera_lookat(self, pos, target):
-        pass  # no viewer (headless only)
+        """Camera of the rendered views (reference env_base.py:599-612 moves the viewer's): eye `pos`, looking at `target`, z up."""
+        if self._render_cfg is None:
+            return  # visualize=False: nothing to look with
+        self._render_camera = (tuple(float(x) for x in pos), tuple(float(x) for x in target))
+        if self._renderer is not None:
+            self._renderer.set_camera(*self._render_camera, self._render_cfg["fov_deg"])
 
     # ---- shapes -------------------------------------------------------------------------------
     def get_state_shape(self) -> torch.Size:
@@ -247,10 +273,28 @@ class IsaacEnvBase:
         self._step_info = dict(self._info_items)
 
     def render(self):
-        if self.visualize:
+        """With visualize=True on a cuda device: render the configured views of the collision model from the resident state and return the colour
+        tensor uint8 [V, H, W, 4] (owned by the renderer, valid until the next call).  The reference draws into a GUI window and returns None
+        (env_base.py:403-427); returning the frame is the headless equivalent, an extension of this backend.  With `native.render.record_dir`
+        every call also writes the mosaic of the views as frame_%06d.png - one device-to-host copy per call, the "viewer sync" of this backend.
+        visualize=False: does nothing, returns None."""
+        if not self.visualize:
+            return None
+        if self._renderer is None:
             print_warn("render(): the HIP environment is headless; no viewer is available.")
+            return None
+        color = self._renderer.render(self._engine.state)["color"]
+        record_dir = self._render_cfg["record_dir"]
+        if record_dir is not None:
+            from .. import render as tfr
+            tfr.write_png(os.path.join(record_dir, "frame_%06d.png" % self._frame_index), tfr.mosaic(color))
+        self._frame_index += 1
+        return color
 
     def close(self):
+        if getattr(self, "_renderer", None) is not None:
+            self._renderer.close()
+            self._renderer = None
         if getattr(self, "_engine", None) is not None:
             self._engine.close()
 

@@ -71,7 +71,8 @@ class TrifingerEnv(IsaacEnvBase):
         Args:
             config: configuration dictionary (merged over TRIFINGER_DEFAULT_CONFIG_DICT and the base defaults).
             device: torch device of every buffer; must be a 'cuda:N' device (MI355X).
-            verbose / visualize: as in the reference (visualize is accepted; the env is headless).
+            verbose / visualize: as in the reference; visualize=True makes `render()` draw the collision model offscreen and return the frames
+                (`native.render` section: IsaacEnvBase._create_renderer; there is no window).
             lib: TEST HOOK - an already loaded C-ABI library to run on instead of the HIP product library.
             env_id_offset / global_num_instances: position of this shard when envs are split over GPUs
                 (the in-kernel RNG is keyed by global env id, reward schedules by global env-steps).

@@ -322,6 +322,10 @@ def run_rlg(runner_factory=None):
     print_notify(f"Seed          : {agent_cfg_train['seed']}")
     cli_args.logdir = logdir
     vargs["logdir"] = logdir
+    if not getattr(cli_args, "headless", True):
+        # args.headless=False arrives at the task as visualize=True: the frames of its render() calls go under the run directory (the pinned
+        # config tables know no `native.render`; it is inserted here, at launch time, unless the caller set a directory of their own)
+        task_cfg.setdefault("native", {}).setdefault("render", {}).setdefault("record_dir", os.path.join(logdir, "frames"))
     set_seed(agent_cfg_train["seed"])
     if cli_args.verbose:
         print_info("Agent training configuration: ")

@@ -4,6 +4,9 @@
     python scripts/rlg_hydra.py gym=trifinger_difficulty_4 args.num_envs=65536 args.headless=True
     python scripts/rlg_hydra.py gym=trifinger_difficulty_4 args.num_envs=8192 args.play=True args.checkpoint=<run>/nn/trifinger.pth
 
+    python scripts/rlg_hydra.py gym=trifinger_difficulty_4 args.num_envs=512 args.headless=False args.play=True args.checkpoint=...
+        # args.headless=False: the first four envs are rendered before every step (the collision model, offscreen) into <run>/frames/frame_%06d.png
+
 Composes the same configuration (leibnizgym_amd/config.py) and hands it to `run_rlg_hydra`
 (leibnizgym_amd/utils/rlg_train.py): time-stamped run directory with `agent_config.yaml` / `env_config.yaml`, the env-info
 observer, then RL-Games' `Runner` when `rl_games` is installed and the in-repo PPO runner otherwise.  `rollout=N` runs a

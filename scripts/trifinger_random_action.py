@@ -4,7 +4,10 @@ env from a plain config dict (8192 instances, torque mode, decimation 1), reset,
 
     python scripts/trifinger_random_action.py [steps]      # the reference loops forever; here `steps` bounds the run
                                                            # (default 2000) and the rate is printed every 500 steps
+    python scripts/trifinger_random_action.py 100 --record frames/    # also render the first four envs (the collision model,
+                                                           # leibnizgym_amd/render.py) and write frames/frame_%06d.png every step
 """
+import argparse
 import os
 import sys
 import time
@@ -17,7 +20,7 @@ from leibnizgym_amd.envs import TrifingerEnv  # noqa: E402
 from leibnizgym_amd.utils.helpers import print_info  # noqa: E402
 
 
-def main(steps):
+def main(steps, record=None):
     # the reference's dict; the `sim` block selects PhysX pipelines there and has no counterpart here (it is accepted
     # and ignored by the config merge, like every other simulator-only key)
     env_config = {
@@ -27,7 +30,9 @@ def main(steps):
         "command_mode": "torque",
         "sim": {"use_gpu_pipeline": True, "physx": {"use_gpu": False}},
     }
-    env = TrifingerEnv(config=env_config, device="cuda:0", verbose=True, visualize=False)
+    if record is not None:
+        env_config["native"] = {"render": {"record_dir": record}}
+    env = TrifingerEnv(config=env_config, device="cuda:0", verbose=True, visualize=record is not None)
     env.reset()
     print_info("Trifinger environment creation successful.")
     n = env.get_num_instances()
@@ -45,4 +50,8 @@ def main(steps):
 
 
 if __name__ == "__main__":
-    main(int(sys.argv[1]) if len(sys.argv) > 1 else 2000)
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("steps", nargs="?", type=int, default=2000)
+    ap.add_argument("--record", metavar="DIR", default=None, help="render every step and write DIR/frame_%%06d.png")
+    a = ap.parse_args()
+    main(a.steps, a.record)
