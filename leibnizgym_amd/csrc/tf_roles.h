@@ -106,6 +106,10 @@ struct Ctx {
 #define LDST(row) __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ST_RSRC(), (unsigned)cx.i * 4u, (row) * P.N * 4, 0))
 #define STST(row, val) do { if (cx.valid) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (float)(val)), ST_RSRC(), (unsigned)cx.i * 4u, (row) * P.N * 4, 0); } while (0)
 #define BAR() __syncthreads()
+// loads that must be in flight together: an empty statement that reads and writes all of them at once keeps the compiler from giving them one
+// register in turn (load, wait, use, load, ...).  It costs no instruction; the wait for the group sits in front of it.
+#define IN_FLIGHT3(a, b, c) asm volatile("" : "+v"(a), "+v"(b), "+v"(c))
+#define IN_FLIGHT4(a, b, c, d) asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d))
 
 // Developer instrumentation (libtrifinger_hip_timing.so, tools/phase_timing.py only): lane 0 of every wavefront writes
 // s_memtime stamps to scratch[(workgroup * 4 + role) * 64 + id].
@@ -689,13 +693,23 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
                 fc_link = (float)(code & 3);
 #pragma unroll
                 for (int j = 0; j < 3; ++j) lam_tf[j] = LDST(TF_S_LAM_TF + 3 * f + j);
+                // all rows of a group are requested before the first is looked at (IN_FLIGHT: left to itself the compiler loads, waits for and
+                // masks them one by one through a single register - four dependent round trips to rows the previous launch wrote)
                 if (__builtin_amdgcn_ballot_w64(fc_was) != 0ull) {
+                    float t[4];
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) { const float t = LDST(TF_S_LAM_FC + 4 * f + j); lam_fc[j] = fc_was ? t : 0.0f; }
+                    for (int j = 0; j < 4; ++j) t[j] = LDST(TF_S_LAM_FC + 4 * f + j);
+                    IN_FLIGHT4(t[0], t[1], t[2], t[3]);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) lam_fc[j] = fc_was ? t[j] : 0.0f;
                 }
                 if (__builtin_expect(__builtin_amdgcn_ballot_w64(tw_was) != 0ull, 0)) {
+                    float t[3];
 #pragma unroll
-                    for (int j = 0; j < 3; ++j) { const float t = LDST(TF_S_LAM_TW + 3 * f + j); lam_tw[j] = tw_was ? t : 0.0f; }
+                    for (int j = 0; j < 3; ++j) t[j] = LDST(TF_S_LAM_TW + 3 * f + j);
+                    IN_FLIGHT3(t[0], t[1], t[2]);
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) lam_tw[j] = tw_was ? t[j] : 0.0f;
                 }
             }
             // finger vs cube: the shape with the smallest gap holds the contact (TfLinkShape, include/trifinger.h): the distal body
