@@ -1,6 +1,6 @@
 // tf_env_kernels.hip - the fused TriFinger step kernel (roles: tf_roles.h) and the EnvUnit of ONE translation unit (tf_launch.h).
 //
-// Compiled once per unit of the Makefile's UNITS (-DTF_EXT=0|1|2 -DTF_WIDE=0|1|2, and -DTF_SURF=1 below): EXT 0 the headline kernels, 1 the extended domain
+// Compiled once per unit of the Makefile's UNITS (-DTF_EXT=0|1|2 -DTF_WIDE=0|1|2, and -DTF_SURF=1 / -DTF_DR=1 below): EXT 0 the headline kernels, 1 the extended domain
 // randomisation, 2 the general box object; WIDE 0 the 128-register instantiation (four workgroups per CU), 1 the 256-register one for populations of at
 // most 32768 envs, 2 the 256-register one with four helper wavefronts per workgroup (one workgroup per CU: at most 16384 envs; the launches that
 // simulate only - the others are served by the WIDE = 1 unit).
@@ -18,12 +18,27 @@
 #ifndef TF_SURF
 #define TF_SURF 0
 #endif
+// -DTF_DR=1: the EXT 0 and EXT 2 kernels with the base domain randomisation (cube mass and size, friction, motor strength, link mass, restitution; observation
+// noise and action repeat) as a run-time flag of the parameter block.  Their kernel (k_env_dr) and unit (tf_unit_d<EXT>_<WIDE>) have names of their own: the
+// plain EXT 0 and EXT 2 units are built WITHOUT domain randomisation (DR_RT false: the factors are constants, no TF_S_DR row, L_DR0 slot or previous torque is
+// touched, the noise blocks and their barriers are not in the code object) - dr_enable is fixed at tf_create, and the host picks the unit from it (unit_for).
+// The EXT 1 kernels (only ever launched with dr_enable set) and the surface-normal kernels keep the run-time flag under their own names.
+#ifndef TF_DR
+#define TF_DR 0
+#endif
+#if TF_DR && (TF_EXT == 1 || TF_SURF)
+#error "TF_DR: the EXT 0 and EXT 2 kernels without the surface normal only (-DTF_EXT=0|2 -DTF_WIDE=0|1|2)"
+#endif
+#define DR_RT (TF_DR || TF_EXT == 1 || TF_SURF)
 #if TF_SURF
 #if TF_EXT == 2 || TF_WIDE == 0
 #error "TF_SURF: the 256-register cube kernels only (-DTF_EXT=0|1 -DTF_WIDE=1|2)"
 #endif
 #define K_ENV k_env_surf
 #define TF_UNIT_PREFIX tf_unit_s
+#elif TF_DR
+#define K_ENV k_env_dr
+#define TF_UNIT_PREFIX tf_unit_d
 #else
 #define K_ENV k_env
 #define TF_UNIT_PREFIX tf_unit_
@@ -57,9 +72,9 @@ __global__ void __launch_bounds__(HELP ? NT_HELP : NT, HELP ? 1 : (WIDE ? 2 : 4)
     cx.valid = i_raw < P.N;
     cx.i = cx.valid ? i_raw : (P.N - 1);
     cx.n_valid = (P.N - cx.wave_first < WAVE) ? (P.N - cx.wave_first) : WAVE;
-    if (cx.role == 3) cube_role<A, IS_RESET, ASYM, MODE, EXT, WIDE, HELP, TF_SURF != 0>(P, sa, action, lds, cx);
-    else if (HELP && cx.role > 3) helper_role<ASYM, MODE, EXT>(P, sa, lds, cx);
-    else finger_role<A, IS_RESET, ASYM, MODE, EXT, WIDE, HELP>(P, sa, action, lds, cx);
+    if (cx.role == 3) cube_role<A, IS_RESET, ASYM, MODE, EXT, WIDE, HELP, TF_SURF != 0, DR_RT != 0>(P, sa, action, lds, cx);
+    else if (HELP && cx.role > 3) helper_role<ASYM, MODE, EXT, DR_RT != 0>(P, sa, lds, cx);
+    else finger_role<A, IS_RESET, ASYM, MODE, EXT, WIDE, HELP, DR_RT != 0>(P, sa, action, lds, cx);
 }
 
 

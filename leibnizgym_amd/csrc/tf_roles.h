@@ -403,9 +403,12 @@ struct TipContact {            // fingertip sphere against one feature of the ar
     float arm[3];             // contact point relative to the tip-link origin (fingertip wrench sensor)
 };
 
-template <int A, bool IS_RESET, bool ASYM, int MODE, int X, bool WIDE, bool HELP = false>
+template <int A, bool IS_RESET, bool ASYM, int MODE, int X, bool WIDE, bool HELP = false, bool DR = true>
 DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __restrict__ action, float* lds, const Ctx& cx) {
     static_assert(!HELP || WIDE, "helper wavefronts: 256-register kernels only");
+    // DR: domain randomisation is a run-time flag of the parameter block (P.dr_enable, P.dr_obs_noise, P.dr_action_repeat).  false (the headline units, which
+    // the host launches only for configs with dr_enable == 0): dr[] is the neutral constants, every such test is false at compile time, and no TF_S_DR row,
+    // L_DR0 slot or previous torque is touched.  x * 1.0f is exact: the same bits as the run-time flag gives with dr_enable == 0.
     constexpr bool EXT = X != 0;      // X: 0 the headline kernels, 1 extended domain randomisation, 2 the same with the general box object
     // WIDE: the 256-register instantiation (2 wavefronts per SIMD) launched for populations that never put more than two workgroups on a
     // CU (num_envs <= 32768): nothing is parked in LDS or re-read from the state rows between substeps.  Same arithmetic, bit for bit.
@@ -432,7 +435,7 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
         for (int j = 0; j < 3; ++j) tau[j] = LDST(TF_S_TAU + 3 * f + j);
     }
     float tau_prev[3] = {0.0f, 0.0f, 0.0f};                      // action repeat: the torque of the previous step, requested with the other loads of the prologue
-    if ((MODE & M_TORQUE) && !IS_RESET && P.dr_action_repeat > 0.0f) {
+    if (DR && (MODE & M_TORQUE) && !IS_RESET && P.dr_action_repeat > 0.0f) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) tau_prev[j] = LDST(TF_S_TAU + 3 * f + j);
     }
@@ -451,7 +454,7 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
     else if (MODE & (M_RESETS | M_TORQUE | M_POST)) coop_load_tile<A>((const float*)P.action_buf, lds, cx);
     BAR();                                                      // #1: action tile in LDS, flag loads have returned
 #pragma unroll
-    for (int j = 0; j < TF_NUM_DR; ++j) dr[j] = (j < NDR && P.dr_enable) ? LD(L_DR0 + j) : TF_DR_NEUTRAL(j);
+    for (int j = 0; j < TF_NUM_DR; ++j) dr[j] = (DR && j < NDR && P.dr_enable) ? LD(L_DR0 + j) : TF_DR_NEUTRAL(j);
     // L_DR0 aliases finger 1's record: in the fused modes barriers #2a / #2b stand between these reads and the first physics write; a launch
     // without them (the split path's tf_simulate / tf_post_step) closes the hand-over with a barrier of its own
     if (!(MODE & (M_ACT_IN | M_RESETS))) BAR();                 // #1b
@@ -464,7 +467,7 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
     const bool rflag = (MODE & M_RESETS) && (IS_RESET || fl_reset != 0);
     if (MODE & M_RESETS) {
         if (rflag) {
-            if (P.dr_enable) draw_dr<EXT>(P, gid, fl_count, dr);
+            if (DR && P.dr_enable) draw_dr<EXT>(P, gid, fl_count, dr);
             if (P.robot_reset_type == TF_RESET_DEFAULT) {
 #pragma unroll
                 for (int j = 0; j < 3; ++j) { q[j] = m.q_default[j]; qd[j] = 0.0f; }
@@ -537,7 +540,7 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
             }
             t[j] = tq * dr[3];                                  // domain randomisation of the motor strength (1.0 when off)
         }
-        if (!IS_RESET && P.dr_action_repeat > 0.0f) {           // build-defined action repeat: keep the previous step's torque
+        if (DR && !IS_RESET && P.dr_action_repeat > 0.0f) {           // build-defined action repeat: keep the previous step's torque
             float u[4];
             rng4(P, gid, sa.frame0, RNG_ACT_REPEAT, u);
             const bool keep = u[0] < P.dr_action_repeat;
@@ -613,7 +616,7 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
                 }
             } else {
 #pragma unroll
-                for (int j = 0; j < TF_NUM_DR; ++j) drs[j] = (j < NDR && P.dr_enable) ? LDST(TF_S_DR + j) : TF_DR_NEUTRAL(j);
+                for (int j = 0; j < TF_NUM_DR; ++j) drs[j] = (DR && j < NDR && P.dr_enable) ? LDST(TF_S_DR + j) : TF_DR_NEUTRAL(j);
 #pragma unroll
                 for (int j = 0; j < 3; ++j) taus[j] = LD(L_PARK(f) + PK_TAU + j);
 #pragma unroll
@@ -675,7 +678,7 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
 #pragma unroll
                 for (int j = 0; j < 6; ++j) LD(pb + P_MINV + j) = k.Minv[j];
                 LD(pb + P_S1) = k.s1; LD(pb + P_C1) = k.c1;
-                if (HELP) LD(L_HELP_DR + f) = dr[5];
+                if (HELP && DR) LD(L_HELP_DR + f) = dr[5];
             }
             STAMP(sb_ + 0);
             BAR();                                              // S1: free motion of every role published
@@ -1224,7 +1227,7 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
         tip_state(m, yw, pk, q, qd, tips);
         float boff_p[3];                                       // robot base offset of the episode (cold through the physics: re-read)
 #pragma unroll
-        for (int j = 0; j < 3; ++j) { boff_p[j] = (EXT && P.dr_enable) ? LDST(TF_S_DR + TF_DR_BASE_POS + j) : 0.0f; if (EXT) tips[j] = tips[j] + boff_p[j]; }   // robot frame -> world
+        for (int j = 0; j < 3; ++j) { boff_p[j] = (DR && EXT && P.dr_enable) ? LDST(TF_S_DR + TF_DR_BASE_POS + j) : 0.0f; if (EXT) tips[j] = tips[j] + boff_p[j]; }   // robot frame -> world
         float tip_prev[3], tau_p[3], act_p[AJ], ft[6];
 #pragma unroll
         for (int j = 0; j < 3; ++j) { tip_prev[j] = LDST(TF_S_TIP_P + 3 * f + j); tau_p[j] = LDST(TF_S_TAU + 3 * f + j); }
@@ -1302,7 +1305,7 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
             BAR();                                              // P3: states tile complete
             STAMP(34);
             coop_store_tile<SD, NT_F>(P.states, lds, cx);
-            if (P.dr_obs_noise > 0.0f) {
+            if (DR && P.dr_obs_noise > 0.0f) {
                 BAR();                                          // P4: states tile stored; obs noise goes on top of slots 0..24
                 float nz[28];
 #pragma unroll
@@ -1322,7 +1325,7 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
             }
             coop_store_tile_strided<OD, SD, NT_F>(P.obs, lds, cx);
         } else {
-            if (P.dr_obs_noise > 0.0f) {
+            if (DR && P.dr_obs_noise > 0.0f) {
                 float nz[28];
 #pragma unroll
                 for (int b = 0; b < 28; ++b) nz[b] = 0.0f;
@@ -1403,7 +1406,7 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
 // formulation of them (the middle frame rebuilt from what finger fm publishes: the lines of cube_role's block, the same bits) and posts the velocity
 // changes; the finger roles add them behind S1b in the listed order exactly as they add the ones they computed themselves.  Apart from that the role
 // only keeps the workgroup's barriers company - every BAR() of the other roles has its twin here, in the same order under the same conditions.
-template <bool ASYM, int MODE, int X>
+template <bool ASYM, int MODE, int X, bool DR = true>
 DEV void helper_role(const DevParams& P, const StepArgs& sa, float* lds, const Ctx& cx) {
     constexpr bool BOXK = X == 2;
     const DevModel& m = P.m;
@@ -1427,7 +1430,7 @@ DEV void helper_role(const DevParams& P, const StepArgs& sa, float* lds, const C
                 // wavefront that has nothing else to do: what the fingers published is read once, the geometry of the three pairs (closest points,
                 // Jacobians, M^-1 J^T - independent of each other) is built side by side, and only the three velocity updates, each of which sees the
                 // one before it, run in turn, on registers; L_VQFF is written once at the end.  Same operations on the same operands: the same bits.
-                const float rest_ff = m.restitution_ff * LD(L_HELP_DR);
+                const float rest_ff = m.restitution_ff * (DR ? LD(L_HELP_DR) : TF_DR_NEUTRAL(5));
                 float Aw_[3][3], Bw_[3][3], vel[3][3];
                 FingerPubRegs pp[3];
 #pragma unroll
@@ -1492,7 +1495,7 @@ DEV void helper_role(const DevParams& P, const StepArgs& sa, float* lds, const C
                     for (int j = 0; j < 3; ++j) LD(L_VQFF + 3 * f + j) = vel[f][j];
                 }
             } else if (m.ff_middle_pairs != 0) {
-                const float rest_ff = m.restitution_ff * LD(L_HELP_DR + fm);
+                const float rest_ff = m.restitution_ff * (DR ? LD(L_HELP_DR + fm) : TF_DR_NEUTRAL(5));
                 FingerPubRegs pm;
                 read_pub(lds, lane, fm, pm);
                 const float ex[3] = {pm.k.c1, 0.0f, -pm.k.s1};
@@ -1590,7 +1593,7 @@ DEV void helper_role(const DevParams& P, const StepArgs& sa, float* lds, const C
     if (MODE & M_POST) {
         BAR();                                                  // P1
         BAR();                                                  // P3
-        if (ASYM && P.dr_obs_noise > 0.0f) { BAR(); BAR(); }    // P4, P5
+        if (DR && ASYM && P.dr_obs_noise > 0.0f) { BAR(); BAR(); }    // P4, P5
     }
 }
 
@@ -1711,7 +1714,7 @@ DEV void wall_arms(bool box, const float* lds, int lane, const float r[3], const
     }
 }
 
-template <int A, bool IS_RESET, bool ASYM, int MODE, int X, bool WIDE, bool HELP = false, bool SURF = false>
+template <int A, bool IS_RESET, bool ASYM, int MODE, int X, bool WIDE, bool HELP = false, bool SURF = false, bool DR = true>
 DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restrict__ action, float* lds, const Ctx& cx) {
     constexpr bool EXT = X != 0;
     constexpr bool BOXK = X == 2;
@@ -1734,7 +1737,7 @@ DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restri
 #pragma unroll
     for (int j = 0; j < 4; ++j) cq[j] = LDST(TF_S_CUBE_Q + j);
 #pragma unroll
-    for (int j = 0; j < TF_NUM_DR; ++j) dr[j] = (j < NDR && P.dr_enable) ? LDST(TF_S_DR + j) : TF_DR_NEUTRAL(j);   // rows are read only when the feature is on
+    for (int j = 0; j < TF_NUM_DR; ++j) dr[j] = (DR && j < NDR && P.dr_enable) ? LDST(TF_S_DR + j) : TF_DR_NEUTRAL(j);   // rows are read only when the feature is on
     if (MODE & (M_RESETS | M_POST | M_FINISH)) {
         fl_reset = P.reset_buf[(unsigned)cx.i];
         fl_goal_reset = P.goal_reset_buf[(unsigned)cx.i];
@@ -1745,7 +1748,7 @@ DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restri
     if (MODE & M_ACT_RAND) draw_action_tile<A>(P, sa, lds, cx);
     else if (MODE & M_ACT_IN) coop_load_tile<A>(action, lds, cx);
     else if (MODE & (M_RESETS | M_TORQUE | M_POST)) coop_load_tile<A>((const float*)P.action_buf, lds, cx);
-    if (P.dr_enable) {                                          // the env's domain-randomisation rows for the finger roles (L_DR0)
+    if (DR && P.dr_enable) {                                    // the env's domain-randomisation rows for the finger roles (L_DR0)
 #pragma unroll
         for (int j = 0; j < NDR; ++j) LD(L_DR0 + j) = dr[j];
     }
@@ -1790,7 +1793,7 @@ DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restri
         }
         const bool draw_now = __builtin_amdgcn_ballot_w64(rflag && !have) != 0ull;      // wave-uniform: some lane's reset has no stored samples
         if (rflag) {
-            if (P.dr_enable) draw_dr<EXT>(P, gid, count, dr);
+            if (DR && P.dr_enable) draw_dr<EXT>(P, gid, count, dr);
             if (P.object_reset_type == TF_RESET_DEFAULT) {
                 cp[0] = EXT ? 0.0f + dr[TF_DR_STAGE_POS] : 0.0f; cp[1] = EXT ? 0.0f + dr[TF_DR_STAGE_POS + 1] : 0.0f; cp[2] = m.obj_min_height * dr[1];
                 cq[0] = 0.0f; cq[1] = 0.0f; cq[2] = 0.0f; cq[3] = 1.0f;
@@ -1835,7 +1838,7 @@ DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restri
             if (gflag) P.goal_reset_buf[(unsigned)cx.i] = 0;
             if (rflag || gflag) P.reset_count[(unsigned)cx.i] = count;
         }
-        if (rflag && P.dr_enable) {
+        if (DR && rflag && P.dr_enable) {
 #pragma unroll
             for (int j = 0; j < NDR; ++j) STST(TF_S_DR + j, dr[j]);
         }
@@ -1884,7 +1887,7 @@ DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restri
             (void)sb_;
             float drs[TF_NUM_DR];                               // cold through the sweeps: re-read for every substep but the first
 #pragma unroll
-            for (int j = 0; j < TF_NUM_DR; ++j) drs[j] = (WIDE || j >= NDR || s == 0 || !P.dr_enable) ? dr[j] : LDST(TF_S_DR + j);
+            for (int j = 0; j < TF_NUM_DR; ++j) drs[j] = (!DR || WIDE || j >= NDR || s == 0 || !P.dr_enable) ? dr[j] : LDST(TF_S_DR + j);
             const float* dr = drs;
             const float cube_mass = m.cube_mass * dr[0];
             const float cube_inertia = m.cube_inertia * dr[0] * dr[1] * dr[1];
@@ -2613,7 +2616,7 @@ DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restri
 #pragma unroll
             for (int jj = 18; jj < 25; ++jj) row[jj] = f_clamp(FMA(P.dr_obs_noise, 2.0f * nz[jj] - 1.0f, row[jj]), -co, co);
         };
-        if (!ASYM && P.dr_obs_noise > 0.0f) add_noise();
+        if (DR && !ASYM && P.dr_obs_noise > 0.0f) add_noise();
         STAMP(33);
         BAR();                                                  // P3: tile complete, fingertip exchange published
         STAMP(34);
@@ -2676,7 +2679,7 @@ DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restri
         STAMP(36);
         stats_begin(P, st, lane, tk);
         STAMP(37);
-        if (ASYM && P.dr_obs_noise > 0.0f) {                    // (the tiles themselves leave through the three finger wavefronts: NT_F)
+        if (DR && ASYM && P.dr_obs_noise > 0.0f) {              // (the tiles themselves leave through the three finger wavefronts: NT_F)
             BAR();                                              // P4
             add_noise();
             BAR();                                              // P5

@@ -141,20 +141,26 @@ static int resolve_width(const TfConfig& c, int variant) {
     if (!c.model.cube_wall_surface && c.num_envs > TF_WIDE_MAX_ENVS) return 0;
     return c.num_envs <= TF_HELPERS_MAX_ENVS ? 2 : 1;
 }
-// The unit that carries launch mode lm, from [surf][ext][width]; nullptr where none is built - the one place that decides which combinations exist.  The
+// The unit that carries launch mode lm, from [dr][surf][ext][width]; nullptr where none is built - the one place that decides which combinations exist.  The
 // launches that simulate use the handle's own width and surface normal; the other hooks (split path) the plain unit of at most 256 registers, which is
 // built wherever the handle's fused step is: tf_create and tf_set_kernel_variant admit a (config, width) only if unit_for(.., TF_LM_STEP) is.
 static const EnvUnit* unit_for(const TfConfig& c, int width, int lm) {
 #if defined(TF_DEV_MIN)      // developer builds (tools/ab_bench.py, tools/variant_sweep.py): the headline kernels, fused launches of A = 9 only
-    static const EnvUnit* const units[2][3][3] = {{{&tf_unit_0_0, &tf_unit_0_1, &tf_unit_0_2}}};
+    // (no domain randomisation at all: tf_unit_0_* are built without it)
+    static const EnvUnit* const units[2][2][3][3] = {{{{&tf_unit_0_0, &tf_unit_0_1, &tf_unit_0_2}}}};
 #else
-    static const EnvUnit* const units[2][3][3] = {
-        {{&tf_unit_0_0, &tf_unit_0_1, &tf_unit_0_2}, {&tf_unit_1_0, &tf_unit_1_1, &tf_unit_1_2}, {&tf_unit_2_0, &tf_unit_2_1, &tf_unit_2_2}},
-        {{nullptr, &tf_unit_s0_1, &tf_unit_s0_2}, {nullptr, &tf_unit_s1_1, &tf_unit_s1_2}, {nullptr, nullptr, nullptr}},
+    // dr = cfg.dr_enable: the plain EXT 0 and EXT 2 units are built without domain randomisation, tf_unit_d0_* / d2_* are the same kernels with it as a
+    // run-time flag; the surface-normal units keep the run-time flag and serve both (EXT 1 is only ever asked for with dr_enable set: ext_kind)
+    static const EnvUnit* const units[2][2][3][3] = {
+        {{{&tf_unit_0_0, &tf_unit_0_1, &tf_unit_0_2}, {nullptr, nullptr, nullptr}, {&tf_unit_2_0, &tf_unit_2_1, &tf_unit_2_2}},
+         {{nullptr, &tf_unit_s0_1, &tf_unit_s0_2}, {nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}}},
+        {{{&tf_unit_d0_0, &tf_unit_d0_1, &tf_unit_d0_2}, {&tf_unit_1_0, &tf_unit_1_1, &tf_unit_1_2}, {&tf_unit_d2_0, &tf_unit_d2_1, &tf_unit_d2_2}},
+         {{nullptr, &tf_unit_s0_1, &tf_unit_s0_2}, {nullptr, &tf_unit_s1_1, &tf_unit_s1_2}, {nullptr, nullptr, nullptr}}},
     };
 #endif
     const bool sim = lm == TF_LM_STEP || lm == TF_LM_STEP_RAND || lm == TF_LM_RESET || lm == TF_LM_SIM;
-    return sim ? units[c.model.cube_wall_surface][ext_kind(c)][width] : units[0][ext_kind(c)][width < 1 ? width : 1];
+    const int dr = c.dr_enable != 0;
+    return sim ? units[dr][c.model.cube_wall_surface][ext_kind(c)][width] : units[dr][0][ext_kind(c)][width < 1 ? width : 1];
 }
 
 static thread_local char g_err[512] = "";

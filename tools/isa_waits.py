@@ -334,6 +334,8 @@ def max_run(chain):
 
 
 def run(unit="0_0", kernel=HEADLINE, dev_min=True, asm=None, keep=None):
+    if unit.startswith("d") and kernel.startswith("k_envI"):      # the d0_* and d2_* units (domain randomisation as a run-time flag): the same kernels, named k_env_dr
+        kernel = "k_env_dr" + kernel[len("k_env"):]
     text = open(asm).read() if asm else compile_unit(unit, dev_min, keep)
     name, ins, meta = extract_kernel(text, kernel)
     waits, single, chains, counts, loops = analyse(ins)
@@ -343,7 +345,7 @@ def run(unit="0_0", kernel=HEADLINE, dev_min=True, asm=None, keep=None):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--unit", default="0_0", help="translation unit of the Makefile (0_0, 1_2, s0_1, ...)")
+    ap.add_argument("--unit", default="0_0", help="translation unit of the Makefile (0_0, d0_0, 1_2, s0_1, ...)")
     ap.add_argument("--kernel", default=HEADLINE, help="substring of the mangled kernel name (default: the headline launch)")
     ap.add_argument("--no-min", action="store_true", help="compile without -DTF_DEV_MIN (every instantiation of the unit: slower)")
     ap.add_argument("--asm", help="read this ISA file instead of compiling")
