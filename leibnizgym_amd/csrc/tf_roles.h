@@ -2299,21 +2299,69 @@ DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restri
                     for (int j = 0; j < 9; ++j) { rDir[(9 * f + j) % NRR] = LD(L_REC(f) + R_DIR + j); rRxd[(9 * f + j) % NRR] = LD(L_REC(f) + R_RXD + j); }
                 }
             }
+            // 128-register kernels: the finger-cube blocks of a lane run in the lane's own order, its live fingers first (ascending f: per env the
+            // same blocks in the same order as a loop over f).  A wavefront then runs as many passes per sweep as its busiest lane has live
+            // fingers, not one block per finger that is live in ANY of its 64 envs.  fc_ix[k]: where the record of the lane's k-th live finger starts
+            // (pass 2 can only be finger 2); cDinv / cbias / clam hold the 1/D, bias and impulses of that finger at 3 k / k / 3 k, and
+            // 1/D = 0 where the lane has no k-th live finger.
+            int fc_ix[3] = {L_REC(2) * WAVE + lane, L_REC(2) * WAVE + lane, L_REC(2) * WAVE + lane};
+#define FC_REC(k, slot) lds[fc_ix[k] + (slot) * WAVE]             // slot `slot` of the record of the lane's k-th live finger
+            if constexpr (!WIDE) {
+                // 1/D, bias and seeds of the three fingers: for the warm start, then each pass takes its finger's (selects: no per-lane address is needed here)
+                float sD[9], sb[3], sl[9];
 #pragma unroll
-            for (int f = 0; f < 3; ++f) {
-                const int rb = L_REC(f);
-                cbias[f] = LD(L_INIT + f);
+                for (int f = 0; f < 3; ++f) {
+                    sb[f] = LD(L_INIT + f);
 #pragma unroll
-                for (int d = 0; d < 3; ++d) { cDinv[3 * f + d] = LD(L_VQFF + 3 * f + d); clam[3 * f + d] = LD(rb + R_DL + d); }
-                if (cDinv[3 * f] > 0.0f) {                       // a live contact has 1/D > 0
+                    for (int d = 0; d < 3; ++d) { sD[3 * f + d] = LD(L_VQFF + 3 * f + d); sl[3 * f + d] = LD(L_REC(f) + R_DL + d); }
+                }
+#pragma unroll 1
+                for (int f = 0; f < 3; ++f) {                   // seeded impulses of the live contacts, the fingers in turn (one copy of the code; f is wave-uniform)
+                    const int rb = L_REC(f);
+                    if ((f == 0 ? sD[0] : (f == 1 ? sD[3] : sD[6])) > 0.0f) {      // a live contact has 1/D > 0
 #pragma unroll
-                    for (int d = 0; d < 3; ++d) {
-                        float dir[3], rxd[3];
+                        for (int d = 0; d < 3; ++d) {
+                            float dir[3], rxd[3];
 #pragma unroll
-                        for (int j = 0; j < 3; ++j) { dir[j] = WIDE ? rDir[(9 * f + 3 * d + j) % NRR] : LD(rb + R_DIR + 3 * d + j); rxd[j] = WIDE ? rRxd[(9 * f + 3 * d + j) % NRR] : LD(rb + R_RXD + 3 * d + j); }
-                        float sc = clam[3 * f + d] * inv_m, qq = clam[3 * f + d] * inv_I;
+                            for (int j = 0; j < 3; ++j) { dir[j] = LD(rb + R_DIR + 3 * d + j); rxd[j] = LD(rb + R_RXD + 3 * d + j); }
+                            const float l = f == 0 ? sl[d] : (f == 1 ? sl[3 + d] : sl[6 + d]);
+                            float sc = l * inv_m, qq = l * inv_I;
 #pragma unroll
-                        for (int j = 0; j < 3; ++j) { v[j] = FMA(-dir[j], sc, v[j]); w[j] = FMA(-rxd[j], qq, w[j]); }
+                            for (int j = 0; j < 3; ++j) { v[j] = FMA(-dir[j], sc, v[j]); w[j] = FMA(-rxd[j], qq, w[j]); }
+                        }
+                    }
+                }
+                const bool l0 = sD[0] > 0.0f, l1 = sD[3] > 0.0f, l01 = l0 && l1;
+                fc_ix[0] = (l0 ? L_REC(0) : (l1 ? L_REC(1) : L_REC(2))) * WAVE + lane;      // the lane's first live finger (2: also "none") ...
+                fc_ix[1] = (l01 ? L_REC(1) : L_REC(2)) * WAVE + lane;                       // ... and its second
+                cbias[0] = l0 ? sb[0] : (l1 ? sb[1] : sb[2]); cbias[1] = l01 ? sb[1] : sb[2]; cbias[2] = sb[2];
+#pragma unroll
+                for (int d = 0; d < 3; ++d) {
+                    cDinv[d] = l0 ? sD[d] : (l1 ? sD[3 + d] : sD[6 + d]); cDinv[3 + d] = l01 ? sD[3 + d] : sD[6 + d]; cDinv[6 + d] = sD[6 + d];
+                    clam[d] = l0 ? sl[d] : (l1 ? sl[3 + d] : sl[6 + d]); clam[3 + d] = l01 ? sl[3 + d] : sl[6 + d]; clam[6 + d] = sl[6 + d];
+                }
+                cDinv[3] = (l0 || l1) ? cDinv[3] : 0.0f;        // finger 2 alone: pass 0 has it
+                cDinv[6] = l01 ? sD[6] : 0.0f;                  // a third live finger: all three
+                if (cDinv[6] > 0.0f) {                          // (few lanes ever have one: its bias and impulses stay in LDS, the impulses in R_A + 3..5 from the start)
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) LD(L_REC(2) + R_A + 3 + d) = clam[6 + d];
+                }
+            } else {                                            // 256-register box kernels: finger order, everything in registers
+#pragma unroll
+                for (int f = 0; f < 3; ++f) {
+                    const int rb = L_REC(f);
+                    cbias[f] = LD(L_INIT + f);
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) { cDinv[3 * f + d] = LD(L_VQFF + 3 * f + d); clam[3 * f + d] = LD(rb + R_DL + d); }
+                    if (cDinv[3 * f] > 0.0f) {                   // a live contact has 1/D > 0
+#pragma unroll
+                        for (int d = 0; d < 3; ++d) {
+                            const float* dir = &rDir[(9 * f + 3 * d) % NRR];
+                            const float* rxd = &rRxd[(9 * f + 3 * d) % NRR];
+                            float sc = clam[3 * f + d] * inv_m, qq = clam[3 * f + d] * inv_I;
+#pragma unroll
+                            for (int j = 0; j < 3; ++j) { v[j] = FMA(-dir[j], sc, v[j]); w[j] = FMA(-rxd[j], qq, w[j]); }
+                        }
                     }
                 }
             }
@@ -2375,7 +2423,7 @@ DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restri
                     }
                 }
 #pragma unroll
-                for (int f = 0; f < 3; ++f) {                   // finger-cube rows in contact space
+                for (int f = 0; f < 3; ++f) {                   // finger-cube rows in contact space (128-register kernels: f is the pass, the finger is the lane's)
                     const int rb = L_REC(f);
                     if (cDinv[3 * f] > 0.0f) {
                         // The three rows of the block from the relative velocities at the INCOMING twist (independent of each other), the later
@@ -2383,11 +2431,16 @@ DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restri
                         // Gauss-Seidel form in exact arithmetic, with the twist updates off the dependency chain (oracle: same order).
                         float Km[3], u[3], dirs[9], rxds[9], vr[3], dl[3];
 #pragma unroll
-                        for (int j = 0; j < 3; ++j) { Km[j] = WIDE ? rA[(3 * f + j) % NRA] : LD(rb + R_A + j); u[j] = WIDE ? uu[3 * f + j] : LD(rb + R_U + j); }
+                        for (int j = 0; j < 3; ++j) { Km[j] = WIDE ? rA[(3 * f + j) % NRA] : FC_REC(f, R_A + j); u[j] = WIDE ? uu[3 * f + j] : FC_REC(f, R_U + j); }
 #pragma unroll
-                        for (int j = 0; j < 9; ++j) { dirs[j] = WIDE ? rDir[(9 * f + j) % NRR] : LD(rb + R_DIR + j); rxds[j] = WIDE ? rRxd[(9 * f + j) % NRR] : LD(rb + R_RXD + j); }
+                        for (int j = 0; j < 9; ++j) { dirs[j] = WIDE ? rDir[(9 * f + j) % NRR] : FC_REC(f, R_DIR + j); rxds[j] = WIDE ? rRxd[(9 * f + j) % NRR] : FC_REC(f, R_RXD + j); }
 #pragma unroll
                         for (int d = 0; d < 3; ++d) vr[d] = u[d] - (dot3(&dirs[3 * d], v) + dot3(&rxds[3 * d], w));
+                        if (!WIDE && f == 2) {
+                            cbias[2] = LD(L_INIT + 2);
+#pragma unroll
+                            for (int d = 0; d < 3; ++d) clam[6 + d] = LD(L_REC(2) + R_A + 3 + d);
+                        }
                         dl[0] = solve_normal(clam[3 * f], cDinv[3 * f], vr[0], cbias[f]);
                         vr[1] = FMA(Km[0], dl[0], vr[1]);
                         dl[1] = solve_tangent(clam[3 * f + 1], cDinv[3 * f + 1], vr[1], mu_fc * clam[3 * f]);
@@ -2395,7 +2448,8 @@ DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restri
                         dl[2] = solve_tangent(clam[3 * f + 2], cDinv[3 * f + 2], vr[2], mu_fc * clam[3 * f]);
 #pragma unroll
                         for (int d = 0; d < 3; ++d) {
-                            LD(rb + R_DL + d) = dl[d];
+                            if constexpr (WIDE) LD(rb + R_DL + d) = dl[d]; else FC_REC(f, R_DL + d) = dl[d];
+                            if (!WIDE && f == 2) LD(L_REC(2) + R_A + 3 + d) = clam[6 + d];
                             const float sc = dl[d] * inv_m, qq = dl[d] * inv_I;
 #pragma unroll
                             for (int j = 0; j < 3; ++j) { v[j] = FMA(-dirs[3 * d + j], sc, v[j]); w[j] = FMA(-rxds[3 * d + j], qq, w[j]); }
@@ -2479,15 +2533,46 @@ DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restri
                     }
                 }
                 }
-                if (last) {                                     // what the finger roles keep: normal impulse, world friction impulse, force (read behind W2)
+                // what the finger roles keep: normal impulse, world friction impulse, force (read behind W2)
+                if (!WIDE && last) {                            // from the per-lane order: the impulses go to R_A + 3..5 of their finger's record (free until
+#pragma unroll                                                  // now; pass 2's are there already), then the fingers in turn; a dead slot hands over its seed
+                    for (int k = 0; k < 2; ++k) {               // (R_DL: no sweep wrote there) and zeros
+                        if (cDinv[3 * k] > 0.0f) {
+#pragma unroll
+                            for (int d = 0; d < 3; ++d) FC_REC(k, R_A + 3 + d) = clam[3 * k + d];
+                        }
+                    }
+#pragma unroll
+                    for (int f = 0; f < 3; ++f) {
+                        const int rb = L_REC(f);
+                        float ftv[3] = {0.0f, 0.0f, 0.0f}, Fc[3] = {0.0f, 0.0f, 0.0f};
+                        float l0 = LD(rb + R_DL);
+                        if (LD(L_VQFF + 3 * f) > 0.0f) {
+                            float dirs[9], l[3];
+#pragma unroll
+                            for (int j = 0; j < 9; ++j) dirs[j] = LD(rb + R_DIR + j);
+#pragma unroll
+                            for (int d = 0; d < 3; ++d) l[d] = LD(rb + R_A + 3 + d);
+#pragma unroll
+                            for (int j = 0; j < 3; ++j) {
+                                ftv[j] = FMA(dirs[6 + j], l[2], dirs[3 + j] * l[1]);
+                                Fc[j] = FMA(dirs[j], l[0], ftv[j]) * inv_h;
+                            }
+                            l0 = l[0];
+                        }
+                        LD(L_INIT + f) = l0;
+#pragma unroll
+                        for (int j = 0; j < 3; ++j) { LD(rb + R_A + j) = ftv[j]; LD(rb + R_A + 3 + j) = Fc[j]; }
+                    }
+                }
+                if constexpr (WIDE) {
+                if (last) {                             // 256-register box kernels: the hand-over from the registers, finger order
 #pragma unroll
                     for (int f = 0; f < 3; ++f) {
                         const int rb = L_REC(f);
                         float ftv[3] = {0.0f, 0.0f, 0.0f}, Fc[3] = {0.0f, 0.0f, 0.0f};
                         if (cDinv[3 * f] > 0.0f) {
-                            float dirs[9];
-#pragma unroll
-                            for (int j = 0; j < 9; ++j) dirs[j] = WIDE ? rDir[(9 * f + j) % NRR] : LD(rb + R_DIR + j);
+                            const float* dirs = &rDir[(9 * f) % NRR];
 #pragma unroll
                             for (int j = 0; j < 3; ++j) {
                                 ftv[j] = FMA(dirs[6 + j], clam[3 * f + 2], dirs[3 + j] * clam[3 * f + 1]);
@@ -2499,12 +2584,14 @@ DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restri
                         for (int j = 0; j < 3; ++j) { LD(rb + R_A + j) = ftv[j]; LD(rb + R_A + 3 + j) = Fc[j]; }
                     }
                 }
+                }
                 { const uint32_t t0_ = NOW(); BAR(); t_wait += NOW() - t0_; }   // W2
             }
             STAMP(sb_ + 6);
             STAMPV(sb_ + 8, t_wait);
             STAMPV(sb_ + 10, t_fc);
             STAMPV(sb_ + 11, t_floor);
+#undef FC_REC
             }
             // ---- impulses kept for the next substep, integration ----
 #pragma unroll
