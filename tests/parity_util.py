@@ -232,3 +232,100 @@ def assert_bit_equal(a, b, what, skip_rows=None):
             raise AssertionError(
                 f"{what}: `{k}` differs at {len(bad)} element(s); first {i}: got={x[i]!r} want={y[i]!r}")
     np.testing.assert_allclose(a["info"], b["info"], rtol=2e-5, atol=2e-4, err_msg=f"{what}: info")
+
+
+# ---- the matrix of built step-kernel units (tests/test_parity_unit_matrix.py) ---------------------------------------------------------------
+# A family is the row (dr, surf, ext) of the host's table of units (unit_for in csrc/trifinger_hip.hip); the value is the prefix of its units' names.
+# (1, 1, 0) launches the same s0_* units as (0, 1, 0) - they keep domain randomisation as a run-time flag - with the flag set.
+MATRIX_FAMILIES = {(0, 0, 0): "0", (0, 0, 2): "2", (0, 1, 0): "s0", (1, 0, 0): "d0", (1, 0, 1): "1", (1, 0, 2): "d2", (1, 1, 0): "s0", (1, 1, 1): "s1"}
+MATRIX_N, MATRIX_STEPS, MATRIX_EPISODE, MATRIX_SEED = 130, 36, 12, 3     # two full wavefronts and a ragged one of 2 lanes; three episodes of 12 steps
+MATRIX_PLACE_FIRST = 65                                                  # the second and third wavefront start at the boundary
+MATRIX_BOX = ([0.02, 0.08, 0.02], 500.0)
+MATRIX_SUCCESS = {"activate": True, "bonus": 10.0, "position_tolerance": 0.08, "orientation_tolerance": 3.2}
+MATRIX_BASE_DR = dict(CONFIGS["d4_domain_randomization"]["domain_randomization"])            # action_repeat_prob 0.2 among it
+MATRIX_EXT_DR = dict(CONFIGS["d4_domain_randomization_extended"]["domain_randomization"], action_repeat_prob=0.2)
+MATRIX_SPLIT_SKIP_ROWS = [slice(66, 84), slice(157, 172)]   # rows 66.. (wrench accumulators) are written by the split path only, rows 157.. (samples of
+                                                            # the next reset) by the fused step only; info[9] (number of resets) is counted by the fused step only
+
+
+def matrix_model(lib, family):
+    """the collision model that selects `family`: the general box (ext 2), the low-ring model with the surface normal (surf), else the default"""
+    _, surf, ext = family
+    if ext == 2:
+        return lib.box_model(*MATRIX_BOX)
+    return surface_model(lib, low_ring=True) if surf else lib.default_model()
+
+
+def matrix_engine(lib, device, family, a, asym, variant=None):
+    """one engine of the matrix cell (family, A = `a`, ASYM = `asym`), not yet reset; `variant` is forced and must be accepted"""
+    dr, _, ext = family
+    kw = dict(command_mode={9: "torque", 18: "position_impedance"}[a], asymmetric_obs=bool(asym), task_difficulty=4, reward_terms=D4_REWARDS,
+              robot_reset="random", dof_pos_stddev=0.6, dof_vel_stddev=0.3, success=MATRIX_SUCCESS, model=matrix_model(lib, family))
+    if dr:
+        kw["domain_randomization"] = MATRIX_EXT_DR if ext == 1 else MATRIX_BASE_DR
+    eng = TrifingerEngine(make_config(lib, MATRIX_N, seed=MATRIX_SEED, episode_length=MATRIX_EPISODE, **kw), device=device, lib=lib)
+    assert eng.action_dim == a
+    if variant is not None:
+        eng.kernel_variant = variant
+        assert eng.kernel_variant == variant
+    return eng
+
+
+def matrix_rollout(lib, device, family, a, asym, path, variant=None):
+    """The rollout of one matrix cell: the snapshot after the reset (cube families: with the cubes of envs 65.. placed at the boundary) and after each
+    of the 36 steps.  `path`: "step" (tf_step with actions_for), "rand" (tf_step_random) or "split" (the five entries of the split path, same actions
+    as "step")."""
+    assert path in ("step", "rand", "split"), path
+    eng = matrix_engine(lib, device, family, a, asym, variant)
+    eng.reset()
+    if family[2] != 2:                               # the box families are not placed
+        place_cubes_at_the_boundary(eng, eng.cfg.model, first=MATRIX_PLACE_FIRST)
+    snaps = [snapshot(eng)]
+    for t in range(MATRIX_STEPS):
+        if path == "rand":
+            eng.step_random()
+        else:
+            act = actions_for(t, MATRIX_N, a, MATRIX_SEED).to(device)
+            if path == "step":
+                eng.step(act)
+            else:
+                eng.action_buf.copy_(act)
+                eng.apply_resets()
+                eng.pre_step()
+                eng.simulate()
+                eng.post_step()
+                eng.finish_step()
+        snaps.append(snapshot(eng))                  # (the copies to the host synchronise)
+    eng.close()
+    return snaps
+
+
+def assert_split_equals_fused(split, fused, what):
+    """assert_bit_equal with the exceptions test_split_path_equals_fused documents (MATRIX_SPLIT_SKIP_ROWS, info[9]); neither snapshot is changed"""
+    a, b = dict(split), dict(fused)
+    a["info"], b["info"] = a["info"].copy(), b["info"].copy()
+    a["info"][9] = b["info"][9] = 0.0
+    assert_bit_equal(a, b, what, skip_rows=MATRIX_SPLIT_SKIP_ROWS)
+
+
+def matrix_reach(snaps, family, m):
+    """What the rollout `snaps` of a matrix cell touched, counted from its snapshots (the one after the reset is the reference of the first
+    difference only): env-steps with a live finger-cube slot (TF_S_FC_LINK, low two bits), with at least two, with a boundary contact (TF_S_CW_FACE),
+    with live cone rows (cone_census on model `m`; surface families), time-outs (the env's step counter falls), goal resets, non-finite states
+    counted by the step; and for the families with domain randomisation whether the six factor rows ever leave 1.0 and the env-steps in which a
+    non-zero applied torque repeats that of the previous snapshot bit for bit (action repeat)."""
+    from leibnizgym_amd import _capi as capi
+    dr, surf, _ = family
+    st = np.stack([s["state"] for s in snaps])                                        # (1 + steps, rows, n)
+    live = ((st[1:, capi.S_FC_LINK:capi.S_FC_LINK + 3].astype(np.int64) & 3) != 0).sum(axis=1)
+    steps = np.stack([s["steps"] for s in snaps])
+    r = dict(live_fc=int((live >= 1).sum()), two_live=int((live >= 2).sum()), boundary=int((st[1:, capi.S_CW_FACE] != 0).sum()),
+             timeouts=int((steps[1:] < steps[:-1]).sum()), goal_resets=int(sum(s["goal_reset_buf"].sum() for s in snaps[1:])),
+             nonfinite=float(sum(s["info"][capi.INFO_NUM_NONFINITE] for s in snaps[1:])))
+    if surf:
+        r["cone"] = int(sum(cone_census(s, m).sum() for s in st[1:]))
+    if dr:
+        tau = st[:, capi.S_TAU:capi.S_TAU + 9].view(np.uint32)
+        r["factors_drawn"] = bool((st[1:, capi.S_DR:capi.S_DR + 6] != 1.0).any())
+        r["tau_repeats"] = int(((tau[1:] == tau[:-1]).all(axis=1) & (st[1:, capi.S_TAU:capi.S_TAU + 9] != 0).any(axis=1)).sum())
+    return r

@@ -131,27 +131,34 @@ def test_link_mass_and_restitution_effects(backend):
     eng.close()
 
 
-def test_observation_noise(backend):
+@pytest.mark.parametrize("asymmetric_obs", [True, False], ids=["asym", "sym"])
+def test_observation_noise(backend, asymmetric_obs):
     """obs slots 0..24 get a * U(-1, 1) on top of the clean value; goal, action and the states vector stay exact;
-    a different frame gives a different draw; the draw does not depend on the shard layout."""
-    kw = dict(seed=3, command_mode="torque", asymmetric_obs=True, task_difficulty=4, success={"activate": False})
+    a different frame gives a different draw; the draw does not depend on the shard layout - nor on the observation layout:
+    it is keyed by env, frame and slot, so symmetric and asymmetric observations carry the same noise bit for bit."""
+    kw = dict(seed=3, command_mode="torque", asymmetric_obs=asymmetric_obs, task_difficulty=4, success={"activate": False})
     n, a = 4096, 0.05
+    noise_on = dict(activate=True, obs_noise=a, **NEUTRAL)
     clean = TrifingerEngine(make_config(backend[0], n, domain_randomization=dict(activate=True, **NEUTRAL), **kw),
                             device=backend[1], lib=backend[0])
-    noisy = TrifingerEngine(make_config(backend[0], n, domain_randomization=dict(activate=True, obs_noise=a, **NEUTRAL), **kw),
+    noisy = TrifingerEngine(make_config(backend[0], n, domain_randomization=noise_on, **kw),
                             device=backend[1], lib=backend[0])
     shard = TrifingerEngine(make_config(backend[0], 1024, env_id_offset=2048, global_num_envs=n,
-                                        domain_randomization=dict(activate=True, obs_noise=a, **NEUTRAL), **kw),
+                                        domain_randomization=noise_on, **kw),
                             device=backend[1], lib=backend[0])
-    for e in (clean, noisy, shard):
+    other = TrifingerEngine(make_config(backend[0], n, domain_randomization=noise_on, **dict(kw, asymmetric_obs=not asymmetric_obs)),
+                            device=backend[1], lib=backend[0])      # the other observation layout: another role of the step adds the noise
+    assert (noisy.states_dim > 0) == asymmetric_obs and (other.states_dim > 0) != asymmetric_obs
+    for e in (clean, noisy, shard, other):
         e.reset()
     g = torch.Generator().manual_seed(0)
     prev = None
     for _ in range(3):
         act = (torch.rand(n, 9, generator=g) * 2 - 1).to(backend[1])
-        clean.step(act), noisy.step(act), shard.step(act[2048:3072])
+        clean.step(act), noisy.step(act), shard.step(act[2048:3072]), other.step(act)
         d = (noisy.obs - clean.obs).cpu().numpy()
         assert np.all(d[:, 25:] == 0.0) and torch.equal(noisy.states, clean.states)
+        assert torch.equal(noisy.obs[:, 25:], clean.obs[:, 25:])       # goal and action: the same bits
         assert torch.equal(noisy.state, clean.state) and torch.equal(noisy.reward, clean.reward)
         u = d[:, :25] / a
         assert np.abs(u).max() <= 1.0 + 1e-4
@@ -160,7 +167,9 @@ def test_observation_noise(backend):
         assert prev is None or not np.array_equal(prev, d)
         prev = d
         assert torch.equal(shard.obs, noisy.obs[2048:3072])
-    for e in (clean, noisy, shard):
+        assert torch.equal(other.state, noisy.state)                   # same rollout ...
+        assert torch.equal(other.obs[:, :25], noisy.obs[:, :25])       # ... same noisy slots, whichever role added the noise
+    for e in (clean, noisy, shard, other):
         e.close()
 
 
@@ -198,6 +207,39 @@ def test_action_repeat(backend):
         e1.step(torch.full((64, 9), 0.1, device=backend[1]))
         assert torch.all(e1.tau == 0)
     e1.close()
+    # A = 18 (position_impedance: a target and a stiffness per joint, so the torque depends on the env's joint state).  The reset leaves the stored
+    # torque at zero here too - the zero command of the reset's own simulate asks for stiffness 0 at joint velocity 0 (default robot reset) -, so on the
+    # first step the kept envs apply zero and every other env exactly what a twin without action repeat applies
+    base18 = dict(base, command_mode="position_impedance")
+    mk18 = lambda lib_n, prob, **kw: TrifingerEngine(make_config(backend[0], lib_n, domain_randomization=dict(   # noqa: E731
+        activate=True, action_repeat_prob=prob, **NEUTRAL), **base18, **kw), device=backend[1], lib=backend[0])
+    eng, twin, shard = mk18(n, p), mk18(n, 0.0), mk18(1024, p, env_id_offset=4096, global_num_envs=n)
+    assert eng.action_dim == 18
+    eng.reset(), twin.reset(), shard.reset()
+    assert torch.equal(eng.state, twin.state)
+    prev = eng.tau.clone()
+    assert torch.all(prev == 0)
+    fracs, g18 = [], torch.Generator().manual_seed(18)
+    for t in range(6):
+        # per-env joint targets within 0.3 rad of the middle of the joint ranges, stiffness 0.3 N m / rad: the torques stay off the 0.36 N m clamp,
+        # so a fresh torque never equals the previous one in all nine rows
+        act = torch.tensor([0.1, 0.8, -1.6] * 3 + [0.3] * 9).repeat(n, 1)
+        act[:, :9] += 0.3 * (2 * torch.rand(n, 9, generator=g18) - 1)
+        act = act.to(backend[1])
+        eng.step(act), shard.step(act[4096:5120])
+        tau = eng.tau
+        kept = torch.all(tau == prev, dim=0)
+        if t == 0:
+            twin.step(act)
+            assert torch.all(torch.any(twin.tau != 0, dim=0))           # a fresh torque is never all zero: `kept` is what it says
+            assert torch.all(tau[:, kept] == 0)
+            assert torch.equal(tau[:, ~kept].view(torch.int32), twin.tau[:, ~kept].view(torch.int32))       # bit for bit
+        fracs.append(float(kept.float().mean()))
+        assert torch.equal(eng.action_buf, act)
+        assert torch.equal(shard.tau, tau[:, 4096:5120])
+        prev = tau.clone()
+    assert all(abs(f - p) < 0.02 for f in fracs), fracs
+    eng.close(), twin.close(), shard.close()
 
 
 EXTENDED = dict(robot_base_position=(0.01, 0.02, 0.005), stage_position=(0.015, 0.01), friction_robot=(0.8, 1.2),
