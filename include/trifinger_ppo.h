@@ -124,6 +124,11 @@ int tfp_mlp_backward(const TfpMlp* nets, int32_t n_nets, int32_t M, void* stream
  * idx: int64 [rows] on the device */
 int tfp_gather_rows(const void* const* src, void* const* dst, const int32_t* widths, int32_t n, const void* idx, int32_t rows, void* stream);
 
+/* Input normalisation (`normalize_input` / `central_value_config.normalize_input` of asymm.yaml): tfp_moments, tfp_moments_part_doubles, tfp_norm_merge,
+ * tfp_gather_rows_norm and tfp_mlp_forward_norm (csrc/ppo_norm.hip; the statistics variant of the forward walk in csrc/ppo_mlp_walk.hip) are exported by the
+ * same library and declared, with their semantics, in include/trifinger_ppo_norm.h.  They were added without a new API number: no entry point of this
+ * header changed, tfp_mlp_forward launches the code it always did, and the binding finds the new ones by symbol. */
+
 #ifdef __cplusplus
 }
 #endif

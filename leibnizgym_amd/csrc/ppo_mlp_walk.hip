@@ -34,6 +34,7 @@
 #include <stdint.h>
 #include <string.h>
 #include "../../include/trifinger_ppo.h"
+#include "../../include/trifinger_ppo_norm.h"
 
 typedef float w4 __attribute__((ext_vector_type(4)));
 typedef float w4u __attribute__((ext_vector_type(4), aligned(4)));      // a dwordx4 load needs dword alignment only (rows of 41 / 113 floats)
@@ -398,9 +399,17 @@ __device__ __forceinline__ void walk_dispatch(const float* Xs, int px, const flo
 #undef WALK_CASE
 }
 
-// two workgroups of four wavefronts per CU: two wavefronts per SIMD, 256 registers each
-template <bool BWD>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) k_mlp_walk(const WalkArgs a) {
+// Input statistics of the forward walk (tfp_mlp_forward_norm; csrc/ppo_norm.hip holds the record they are published from): a network with mean != NULL
+// reads clamp((x - mean) * inv_std, -clip, clip) instead of x - formed where the row block's input is staged into LDS, so the rollout normalises the env's live
+// observation buffers without a launch or a copy of its own.  The statistics travel behind WalkArgs: the plain kernels keep their argument block.
+struct WalkNorm { const float* mean[2]; const float* inv[2]; float clip[2]; };
+struct WalkArgsNorm : WalkArgs { WalkNorm nm; };
+template <bool NORM> struct walk_args { typedef WalkArgs type; };
+template <> struct walk_args<true> { typedef WalkArgsNorm type; };
+
+// two workgroups of four wavefronts per CU: two wavefronts per SIMD, 256 registers each.  NORM (forward only): the staged input passes through a.nm
+template <bool BWD, bool NORM = false>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) k_mlp_walk(const typename walk_args<NORM>::type a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int ni = (int)blockIdx.x / a.blocks_per_net;
     if (ni >= a.n_nets) return;
@@ -425,6 +434,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
             for (int u = 0; u < 16; ++u) v[u] = src[min(c + 256 * u, total - 1)];
 #pragma unroll
             for (int u = 0; u < 16; ++u) {
+                if constexpr (NORM) {
+#pragma clang fp contract(off)                               // the difference and the product rounded separately: torch.clamp((x - mean) * inv_std, -clip, clip) bit for bit
+                    const gfloat* nmean = (const gfloat*)a.nm.mean[ni];
+                    if (nmean) {                                    // uniform: a network of the call may come without statistics
+                        const float hi = a.nm.clip[ni], lo = -hi;
+                        const float df = v[u] - nmean[col], y = df * ((const gfloat*)a.nm.inv[ni])[col];
+                        v[u] = y < lo ? lo : (y > hi ? hi : y);
+                    }
+                }
                 if (c + 256 * u < WALK_ROWS * D) P[row * px + col] = (c + 256 * u < total) ? v[u] : 0.0f;
                 col += dc; row += dr;
                 if (col >= D) { col -= D; row += 1; }
@@ -507,8 +525,16 @@ static int walk_prepare(WalkArgs& a, int M, bool bwd, size_t* lds_bytes) {
 
 extern "C" {
 
-static int walk_launch(const TfpMlp* nets, int32_t n_nets, int32_t M, bool bwd, void* stream) {
+static int walk_launch(const TfpMlp* nets, int32_t n_nets, int32_t M, bool bwd, void* stream, const TfpNorm* norm = nullptr) {
     if (!nets || n_nets < 1 || n_nets > 2 || M <= 0) return -1;
+    WalkNorm nm; memset(&nm, 0, sizeof(nm));
+    bool with_norm = false;
+    for (int ni = 0; norm && ni < n_nets; ++ni) {
+        if (!norm[ni].mean) continue;
+        if (bwd || !norm[ni].inv_std || !(norm[ni].clip > 0.0f)) return -1;
+        nm.mean[ni] = norm[ni].mean; nm.inv[ni] = norm[ni].inv_std; nm.clip[ni] = norm[ni].clip;
+        with_norm = true;
+    }
     WalkArgs a; memset(&a, 0, sizeof(a));
     a.n_nets = n_nets;
     for (int ni = 0; ni < n_nets; ++ni) {
@@ -523,15 +549,17 @@ static int walk_launch(const TfpMlp* nets, int32_t n_nets, int32_t M, bool bwd, 
     size_t lds = 0;
     const int rc = walk_prepare(a, M, bwd, &lds);
     if (rc) return rc;
-    static bool attr_set[2] = {false, false};
-    if (!attr_set[bwd ? 1 : 0]) {
-        const void* f = bwd ? (const void*)k_mlp_walk<true> : (const void*)k_mlp_walk<false>;
+    static bool attr_set[3] = {false, false, false};
+    const int which = with_norm ? 2 : (bwd ? 1 : 0);
+    if (!attr_set[which]) {
+        const void* f = with_norm ? (const void*)k_mlp_walk<false, true> : bwd ? (const void*)k_mlp_walk<true> : (const void*)k_mlp_walk<false>;
         if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess) return -2;
-        attr_set[bwd ? 1 : 0] = true;
+        attr_set[which] = true;
     }
     const dim3 grid(a.blocks_per_net * n_nets), block(256);
     hipStream_t s = (hipStream_t)stream;
-    if (bwd) hipLaunchKernelGGL(k_mlp_walk<true>, grid, block, lds, s, a);
+    if (with_norm) { WalkArgsNorm an; static_cast<WalkArgs&>(an) = a; an.nm = nm; hipLaunchKernelGGL((k_mlp_walk<false, true>), grid, block, lds, s, an); }
+    else if (bwd) hipLaunchKernelGGL(k_mlp_walk<true>, grid, block, lds, s, a);
     else hipLaunchKernelGGL(k_mlp_walk<false>, grid, block, lds, s, a);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
@@ -539,6 +567,10 @@ static int walk_launch(const TfpMlp* nets, int32_t n_nets, int32_t M, bool bwd, 
 // forward of n_nets <= 2 Linear / ELU stacks over the same M rows in ONE launch; -4: the shapes do not fit the walk (a layer wider than 416, LDS):
 // the caller runs the layers one by one (tfp_linear_fwd[_group])
 int tfp_mlp_forward(const TfpMlp* nets, int32_t n_nets, int32_t M, void* stream) { return walk_launch(nets, n_nets, M, false, stream); }
+// ... with optional input statistics per network (norm[i].mean == NULL: network i reads its input as it is; norm == NULL or no statistics at all: tfp_mlp_forward)
+int tfp_mlp_forward_norm(const TfpMlp* nets, const TfpNorm* norm, int32_t n_nets, int32_t M, void* stream) {
+    return walk_launch(nets, n_nets, M, false, stream, norm);
+}
 // the input-gradient chain of the same stacks in ONE launch: x = gradient of the network output, yin[l] = saved output of layer l, y[l] = dZ of layer l
 // (l < n_layers - 1; the dZ of the last layer is x itself)
 int tfp_mlp_backward(const TfpMlp* nets, int32_t n_nets, int32_t M, void* stream) { return walk_launch(nets, n_nets, M, true, stream); }

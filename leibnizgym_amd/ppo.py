@@ -11,6 +11,9 @@ variance scale / fan_in; biases zero).  `PPOConfig.from_rlg` reads all of it fro
 Checkpoints (`save` / `restore`: networks, optimiser moments, learning rates, frame and epoch counters), periodic and
 best-so-far saving and a deterministic `play` mode mirror what the reference gets from RL-Games (`args.checkpoint`,
 `args.play`, `save_frequency`, `save_best_after`).
+`normalize_input` (the actor's `obs`) and `central_value_config.normalize_input` (the value network's `states`) are honoured by running moments
+modelled on RL-Games' RunningMeanStd (`InputNorm`): fp64 {count, mean, M2} per input on the device, frozen for a whole epoch (rollout and every
+minibatch of the update that follows read the same record), updated ONCE at the end of `update()` with the moments of the epoch's raw rollout buffer.
 
 This is host-side training glue, NOT part of the measured hot path.  On a GPU the minibatch step runs on the hand-written kernels of
 csrc/ppo_kernels.hip (leibnizgym_amd/ppo_kernels.py): one gather launch, the Linear / ELU layers on fp32 MFMA, the objective with all
@@ -61,6 +64,8 @@ class PPOConfig:
     name: str = "trifinger"
     seed: int = 7
     fused_kernels: bool = True        # hand-written HIP kernel for the objective, forward and backward in one launch (GPU only)
+    normalize_input: bool = False     # params.config.normalize_input: running mean / std of `obs` in front of the actor (and of a critic that reads obs)
+    normalize_input_value: bool = False   # central_value_config.normalize_input: the same for `states` in front of the central value network
 
     @classmethod
     def from_rlg(cls, rlg: dict, num_envs: int = None, **overrides):
@@ -80,12 +85,12 @@ class PPOConfig:
                   actor_init=str(net["mlp"]["initializer"]["name"]),
                   save_frequency=int(c.get("save_frequency", 100)), save_best_after=int(c.get("save_best_after", 500)),
                   max_epochs=int(c.get("max_epochs", 100000)), name=str(c.get("name", "trifinger")),
-                  seed=int(rlg.get("seed", 7)))
+                  seed=int(rlg.get("seed", 7)), normalize_input=bool(c.get("normalize_input", False)))
         if cv:
             init = cv["network"]["mlp"]["initializer"]
             kw.update(lr_value=float(cv["lr"]), value_mini_epochs=int(cv["mini_epochs"]),
                       value_grad_norm=float(cv["grad_norm"]), value_init=str(init["name"]),
-                      value_init_scale=float(init.get("scale", 2.0)))
+                      value_init_scale=float(init.get("scale", 2.0)), normalize_input_value=bool(cv.get("normalize_input", False)))
         if num_envs:
             kw["minibatches"] = max(1, kw["horizon"] * int(num_envs) // int(c["minibatch_size"]))
         kw.update(overrides)
@@ -174,7 +179,88 @@ def variance_scaling_(w: torch.Tensor, scale: float) -> torch.Tensor:
     return nn.init.trunc_normal_(w, mean=0.0, std=std, a=-2.0 * std, b=2.0 * std)
 
 
+class InputNorm:
+    """Running statistics of one network input (`normalize_input`), modelled on RL-Games' RunningMeanStd.
+    State: ONE float64 vector `state` = [count, mean[D], M2[D]] on the device (M2 = sum of squared deviations; variance = M2 / count, population).
+    Published: `mean_f` = float(mean), `inv_std_f` = float(1 / sqrt(M2 / count + 1e-5)), float32 [D], updated IN PLACE (the kernels keep their addresses);
+    count 0 publishes mean 0 and variance 1.  `normalize(x)` = clamp((x - mean_f) * inv_std_f, -clip, clip) in float32 - the torch expression, which the
+    kernels reproduce bit for bit.  Nothing here moves by itself: `merge` is called by the trainer once per epoch.
+    `fused`: the merge and (for contiguous float32 rows on the GPU) the normaliser run on csrc/ppo_norm.hip; otherwise, and for anything the kernels
+    decline, plain torch of the same semantics (the merge may differ from the kernel's in the last bits of the float64 record)."""
+    EPS = 1e-5
+
+    def __init__(self, dim, device, clip=5.0, fused=False):
+        self.dim, self.clip, self.fused = int(dim), float(clip), bool(fused)
+        self.state = torch.zeros(1 + 2 * self.dim, dtype=torch.float64, device=device)
+        self.mean_f = torch.zeros(self.dim, dtype=torch.float32, device=device)
+        self.inv_std_f = torch.empty(self.dim, dtype=torch.float32, device=device)
+        self.publish()
+
+    count = property(lambda self: self.state[0])
+    mean = property(lambda self: self.state[1:1 + self.dim])
+    m2 = property(lambda self: self.state[1 + self.dim:])
+
+    def stats(self):
+        """what the kernels take: (mean_f, inv_std_f, clip)"""
+        return self.mean_f, self.inv_std_f, self.clip
+
+    def publish(self):
+        n = float(self.state[0])
+        var = self.m2 / n if n > 0 else torch.ones_like(self.m2)
+        self.mean_f.copy_(self.mean.float())
+        self.inv_std_f.copy_((1.0 / torch.sqrt(var + self.EPS)).float())
+
+    def normalize(self, x):
+        if self.fused and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous() and x.shape[1] == self.dim and not torch.is_grad_enabled():
+            from . import ppo_kernels as pk
+            return pk.normalize_rows(x, self.mean_f, self.inv_std_f, self.clip)
+        return torch.clamp((x - self.mean_f) * self.inv_std_f, -self.clip, self.clip)
+
+    @staticmethod
+    def batch_record(x):
+        """[count, mean, M2] of the rows of x, two passes in float64 (the reference form; the GPU path is ppo_kernels.moments)"""
+        xd = x.reshape(-1, x.shape[-1]).double()
+        mean = xd.mean(0)
+        return torch.cat([torch.tensor([float(xd.shape[0])], dtype=torch.float64, device=x.device), mean, ((xd - mean) ** 2).sum(0)])
+
+    def merge(self, records):
+        """Chan's pairwise merge of the batch records `records` [k, 1 + 2 D] (float64), in the order given, into the running record; publishes.
+        (torch form; the trainer's fused path merges all its inputs in one launch: ppo_kernels.norm_merge)"""
+        D = self.dim
+        na, ma, Ma = float(self.state[0]), self.mean.clone(), self.m2.clone()
+        for r in records.reshape(-1, 1 + 2 * D):
+            nb, mb, Mb = float(r[0]), r[1:1 + D], r[1 + D:]
+            if nb <= 0:
+                continue
+            if na <= 0:
+                na, ma, Ma = nb, mb.clone(), Mb.clone()
+                continue
+            n = na + nb
+            delta = mb - ma
+            ma = ma + delta * (nb / n)
+            Ma = (Ma + Mb) + (delta * delta) * (na * nb / n)
+            na = n
+        self.state[0] = na
+        self.state[1:1 + D] = ma
+        self.state[1 + D:] = Ma
+        self.publish()
+
+    def state_dict(self):
+        return {"state": self.state.clone(), "mean_f": self.mean_f.clone(), "inv_std_f": self.inv_std_f.clone()}
+
+    def check_state_dict(self, sd, what):
+        for k, t in (("state", self.state), ("mean_f", self.mean_f), ("inv_std_f", self.inv_std_f)):
+            if not isinstance(sd, dict) or k not in sd or tuple(sd[k].shape) != tuple(t.shape):
+                raise ValueError(f"checkpoint input_norm record '{what}': '{k}' missing or of another width (this trainer: {self.dim} columns)")
+
+    def load_state_dict(self, sd):
+        self.state.copy_(sd["state"]); self.mean_f.copy_(sd["mean_f"]); self.inv_std_f.copy_(sd["inv_std_f"])   # the published bits as they were saved
+
+
 class ActorCritic(nn.Module):
+    obs_norm = None            # InputNorm of `obs` / of `states` (plain attributes, not modules: the model's state_dict keeps its keys); set by the trainer
+    state_norm = None
+
     def __init__(self, obs_dim, state_dim, act_dim, units, cfg: "PPOConfig" = None):
         super().__init__()
         self.actor = mlp(obs_dim, units, act_dim)
@@ -201,23 +287,34 @@ class ActorCritic(nn.Module):
     def critic_parameters(self):
         return list(self.critic.parameters())
 
+    def critic_norm(self):
+        """the record in front of the critic: the central value network's own; without one the critic reads `obs` and shares the actor's"""
+        return self.state_norm if self.central else self.obs_norm
+
     def value(self, obs, states):
-        return self.critic(states if self.central else obs).squeeze(-1)
+        x, nm = (states if self.central else obs), self.critic_norm()
+        return self.critic(nm.normalize(x) if nm is not None else x).squeeze(-1)
 
     def dist(self, obs):
-        mu = self.actor(obs)
+        mu = self.actor(self.obs_norm.normalize(obs) if self.obs_norm is not None else obs)
         return mu, self.log_std.expand_as(mu)
 
     def dist_and_value(self, obs, states):
         """(mu, log_std, value) of one batch: on the hand-written kernels and without autograd (the rollout) layer k of the two networks is ONE launch
         (ppo_kernels.mlp_forward_pair: four launches instead of eight per environment step)"""
         xc = states if self.central else obs
+        na, nc = self.obs_norm, self.critic_norm()
         if self.actor.mfma and self.critic.mfma and obs.is_cuda and obs.dtype == torch.float32 and not torch.is_grad_enabled():
             from . import ppo_kernels as pk
-            ya, yc = pk.mlp_forward_pair(obs.contiguous(), self.actor.layer_list(), xc.contiguous(), self.critic.layer_list(), store_hidden=False)
+            if na is None and nc is None:
+                ya, yc = pk.mlp_forward_pair(obs.contiguous(), self.actor.layer_list(), xc.contiguous(), self.critic.layer_list(), store_hidden=False)
+            else:                              # raw rows in, normalised where the walk stages them: no launch of its own
+                ya, yc = pk.mlp_forward_pair(obs.contiguous(), self.actor.layer_list(), xc.contiguous(), self.critic.layer_list(), store_hidden=False,
+                                             norms=(na.stats() if na is not None else None, nc.stats() if nc is not None else None))
             mu, v = ya[-1], yc[-1].squeeze(-1)
         else:
-            mu, v = self.actor(obs), self.critic(xc).squeeze(-1)
+            mu = self.actor(na.normalize(obs) if na is not None else obs)
+            v = self.critic(nc.normalize(xc) if nc is not None else xc).squeeze(-1)
         return mu, self.log_std.expand_as(mu), v
 
 
@@ -250,8 +347,15 @@ class PPOTrainer:
         self.lr = c.lr
         self.fused_loss = fused and c.fused_kernels        # hand-written objective kernel (GPU only)
         self.net.actor.mfma = self.net.critic.mfma = bool(fused and c.fused_kernels)   # ... and the MFMA linear layers
+        # normalize_input / central_value_config.normalize_input: one record per normalised input, frozen during an epoch (module docstring)
+        fk = bool(fused and c.fused_kernels)
+        if c.normalize_input:
+            self.net.obs_norm = InputNorm(obs_dim, self.device, fused=fk)
+        if c.normalize_input_value and self.net.central:
+            self.net.state_norm = InputNorm(state_dim, self.device, fused=fk)
         self.dist_on = False
         self.n_grad_allreduce = self.n_kl_allreduce = 0       # collectives issued so far (what a test of the distributed path counts)
+        self.n_norm_allgather = 0
         rank = 0
         try:
             import torch.distributed as dist
@@ -382,9 +486,22 @@ class PPOTrainer:
                         "exp_avg_sq": (v[n].to(p.device).clone().view_as(p) if n in v else torch.zeros_like(p))}
                 g["lr"] = lr_actor if (gi == 0 or not self.net.central) else (lr_value if lr_value is not None else g["lr"])
 
+    def _norm_records(self):
+        """{"obs": InputNorm, "states": InputNorm} of the inputs that are normalised (empty: normalisation is off)"""
+        out = {}
+        if self.net.obs_norm is not None:
+            out["obs"] = self.net.obs_norm
+        if self.net.state_norm is not None:
+            out["states"] = self.net.state_norm
+        return out
+
     def state_dict(self):
-        return {"model": self.net.state_dict(), "optimizer": self._optimizer_state(), "lr": self.lr, "frames": self.frames,
-                "epoch": self.epoch, "best_reward": self.best_reward, "config": dict(self.cfg.__dict__)}
+        sd = {"model": self.net.state_dict(), "optimizer": self._optimizer_state(), "lr": self.lr, "frames": self.frames,
+              "epoch": self.epoch, "best_reward": self.best_reward, "config": dict(self.cfg.__dict__)}
+        recs = self._norm_records()
+        if recs:                                                     # the key exists only when normalisation is on
+            sd["input_norm"] = {k: r.state_dict() for k, r in recs.items()}
+        return sd
 
     def save(self, path: str):
         import os
@@ -399,11 +516,19 @@ class PPOTrainer:
         for k, t in mine.items():
             if k not in ck["model"] or tuple(ck["model"][k].shape) != tuple(t.shape):
                 raise ValueError(f"checkpoint model entry '{k}' missing or of another shape")
+        recs, ck_recs = self._norm_records(), ck.get("input_norm") or {}
+        if sorted(recs) != sorted(ck_recs):
+            raise ValueError(f"checkpoint normalises {sorted(ck_recs) or 'no input'}, this trainer {sorted(recs) or 'no input'} "
+                             "(normalize_input / central_value_config.normalize_input differ)")
+        for k, r in recs.items():
+            r.check_state_dict(ck_recs[k], k)
         if "optimizer" in ck:
             parsed = self._parse_optimizer_state(ck["optimizer"])
         with torch.no_grad():                                        # in place: the parameters may be views of a flat buffer
             for k, v in self.net.state_dict().items():
                 v.copy_(ck["model"][k])
+            for k, r in recs.items():
+                r.load_state_dict(ck_recs[k])
             if "optimizer" in ck:
                 self._load_optimizer_state(ck["optimizer"], ck.get("lr"), parsed)
         self.lr = float(ck.get("lr", self.lr))
@@ -533,7 +658,12 @@ class PPOTrainer:
         from . import ppo_kernels as pk
         c = self.cfg
         srcs = [d["obs"], d["act"], d["old_nlp"], d["adv"], d["ret"], d["old_mu"]] + ([d["states"]] if d["states"] is not None else [])
-        g = pk.gather_rows(srcs, idx)
+        na, ns = self.net.obs_norm, self.net.state_norm
+        if na is None and ns is None:
+            g = pk.gather_rows(srcs, idx)
+        else:                                      # the same launch writes obs / states normalised: what the forward AND the first layers' weight gradients read
+            nm = [na.stats() if na is not None else None] + [None] * 5 + ([ns.stats() if ns is not None else None] if d["states"] is not None else [])
+            g = pk.gather_rows(srcs, idx, norm=nm)
         obs, act, old_nlp, adv, ret, old_mu = g[:6]
         states = g[6] if d["states"] is not None else None
         for p in self.net.parameters():
@@ -639,11 +769,48 @@ class PPOTrainer:
                     self.flat_opt.set_lr(1, self.lr)
             for g in (self.opt.param_groups[:1] if self.net.central else self.opt.param_groups):
                 g["lr"] = self.lr
+        self._update_input_norm(src)
         for k in ("loss", "a_loss", "c_loss"):
             stats[k] = float(acc[k]) / max(count, 1)
         stats["lr"] = self.lr
         stats["mean_reward"] = float(buf["rew"].mean() / c.reward_scale)
         return stats
+
+    @torch.no_grad()
+    def _update_input_norm(self, src):
+        """the end of an epoch: the moments of its RAW rollout buffer (T n rows) merged into the running records, which then serve the next epoch.
+        One pass over the buffer (ppo_kernels.moments: both inputs in one call) and one merge launch; a distributed run gathers every rank's batch vector
+        [1 + 2 Do (+ 1 + 2 Ds)] (float64) with ONE all_gather and merges them in rank order, so that all ranks keep the same record bit for bit."""
+        recs = self._norm_records()
+        if not recs:
+            return
+        keys = list(recs)                                            # "obs" before "states"
+        xs = [src[k] for k in keys]
+        fused = self.fused_loss and all(x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() for x in xs)
+        vec = None
+        if fused:
+            from . import ppo_kernels as pk
+            vec = pk.moments(xs)                                     # None: declined (a row wider than 256)
+        if vec is None:
+            vec = torch.cat([InputNorm.batch_record(x) for x in xs])
+        L, k = vec.numel(), 1
+        if self.dist_on:
+            k = self.dist.get_world_size(self.group)
+            parts = [torch.empty_like(vec) for _ in range(k)]
+            self.n_norm_allgather += 1
+            self.dist.all_gather(parts, vec, group=self.group)
+            vec = torch.cat(parts)
+        offs, off = [], 0
+        for key in keys:
+            offs.append(off)
+            off += 1 + 2 * recs[key].dim
+        if fused:
+            pk.norm_merge([recs[key].state for key in keys], [vec[o:] for o in offs], k, L, [recs[key].mean_f for key in keys],
+                          [recs[key].inv_std_f for key in keys])
+        else:
+            rows = vec.view(k, L)
+            for key, o in zip(keys, offs):
+                recs[key].merge(rows[:, o:o + 1 + 2 * recs[key].dim])
 
     def train(self, epochs, log=None, checkpoint_dir=None):
         """`epochs` PPO iterations.  With `checkpoint_dir` (rank 0 only): `<name>.pth` every `save_frequency` epochs and

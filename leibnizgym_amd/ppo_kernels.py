@@ -68,6 +68,17 @@ def load():
         for name in ("tfp_mlp_forward", "tfp_mlp_backward"):
             getattr(lib, name).restype = C.c_int
             getattr(lib, name).argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+        # input normalisation (csrc/ppo_norm.hip and the walk variant): bound by symbol - a library built before them fails HERE, not with a fall-back
+        lib.tfp_moments_part_doubles.restype = C.c_int64
+        lib.tfp_moments_part_doubles.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        lib.tfp_moments.restype = C.c_int
+        lib.tfp_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        lib.tfp_norm_merge.restype = C.c_int
+        lib.tfp_norm_merge.argtypes = [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p] * 3
+        lib.tfp_gather_rows_norm.restype = C.c_int
+        lib.tfp_gather_rows_norm.argtypes = [C.c_void_p] * 6 + [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+        lib.tfp_mlp_forward_norm.restype = C.c_int
+        lib.tfp_mlp_forward_norm.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
         _LIB = lib
     return _LIB
 
@@ -255,8 +266,12 @@ def flush_partial_sums():
         _chk(load().tfp_sum_partials_multi(vp(0), vp(1), vp(2), ip(3), ip(4), ip(5), n, _stream(grp[0][0])), "tfp_sum_partials_multi")
 
 
-def gather_rows(srcs, idx, outs=None):
-    """[s[idx] for s in srcs] for up to 8 row-major float32 arrays (1-D arrays count as width 1) in ONE launch"""
+def gather_rows(srcs, idx, outs=None, norm=None):
+    """[s[idx] for s in srcs] for up to 8 row-major float32 arrays (1-D arrays count as width 1) in ONE launch.  `norm`: None, or one entry per array -
+    None (copied) or (mean_f, inv_std_f, clip): that array leaves as clamp((s[idx] - mean_f) * inv_std_f, -clip, clip) (tfp_gather_rows_norm), and `idx`
+    may then be None (every row in place: a plain normaliser)."""
+    if norm is not None and any(e is not None for e in norm):
+        return _gather_rows_norm(srcs, idx, outs, norm)
     assert 0 < len(srcs) <= 8 and idx.dtype == torch.long and idx.is_contiguous()
     rows = idx.numel()
     widths = [int(s[0].numel()) for s in srcs]
@@ -266,6 +281,65 @@ def gather_rows(srcs, idx, outs=None):
     _chk(load().tfp_gather_rows((C.c_void_p * n)(*[s.data_ptr() for s in srcs]), (C.c_void_p * n)(*[o.data_ptr() for o in outs]),
                                 (C.c_int32 * n)(*widths), n, idx.data_ptr(), rows, _stream(idx)), "tfp_gather_rows")
     return outs
+
+
+# ---- input normalisation (csrc/ppo_norm.hip; the holder of the records is ppo.InputNorm) -----------------------------------------------------
+def _norm_ok(e, width, dev):
+    mean, inv, clip = e
+    return (mean.dtype == torch.float32 and inv.dtype == torch.float32 and mean.is_contiguous() and inv.is_contiguous() and mean.device == dev
+            and inv.device == dev and mean.numel() == width and inv.numel() == width and float(clip) > 0.0)
+
+
+def _gather_rows_norm(srcs, idx, outs, norm):
+    assert 0 < len(srcs) <= 8 and len(norm) == len(srcs) and all(s.dtype == torch.float32 and s.is_contiguous() for s in srcs)
+    assert idx is None or (idx.dtype == torch.long and idx.is_contiguous())
+    rows = idx.numel() if idx is not None else srcs[0].shape[0]
+    assert idx is not None or all(s.shape[0] == rows for s in srcs)
+    widths = [int(s[0].numel()) for s in srcs]
+    assert all(e is None or _norm_ok(e, w, s.device) for e, w, s in zip(norm, widths, srcs)), "statistics of another width, type or device"
+    if outs is None:
+        outs = [torch.empty((rows,) + tuple(s.shape[1:]), device=s.device, dtype=torch.float32) for s in srcs]
+    n = len(srcs)
+    _chk(load().tfp_gather_rows_norm(_vp(srcs), _vp(outs), _ip(widths), _vp([e[0] if e is not None else None for e in norm]),
+                                     _vp([e[1] if e is not None else None for e in norm]),
+                                     (C.c_float * n)(*[float(e[2]) if e is not None else 0.0 for e in norm]), n,
+                                     idx.data_ptr() if idx is not None else None, rows, _stream(srcs[0])), "tfp_gather_rows_norm")
+    return outs
+
+
+def normalize_rows(x, mean_f, inv_std_f, clip):
+    """clamp((x - mean_f) * inv_std_f, -clip, clip) of a contiguous float32 [rows, D] in one launch (the gather with the identity index)"""
+    return _gather_rows_norm([x], None, None, [(mean_f, inv_std_f, clip)])[0]
+
+
+def moments(xs):
+    """the batch records {count, mean[D], M2[D]} (float64) of one or two contiguous float32 arrays [rows, D] over the same rows, concatenated into one vector
+    [1 + 2 D0 (+ 1 + 2 D1)], in two launches (tfp_moments: fp64, deterministic); None when the kernel declines the shapes (a row wider than 256)"""
+    assert 0 < len(xs) <= 2 and all(x.dim() == 2 and x.dtype == torch.float32 and x.is_contiguous() and x.shape[0] == xs[0].shape[0] for x in xs)
+    rows, D = xs[0].shape[0], [x.shape[1] for x in xs]
+    if rows <= 0 or rows >= 2 ** 31:
+        return None
+    lib = load()
+    need = int(lib.tfp_moments_part_doubles(_ip(D), len(xs), rows))
+    part = torch.empty(max(need, 1), device=xs[0].device, dtype=torch.float64)
+    out = torch.empty(sum(1 + 2 * d for d in D), device=xs[0].device, dtype=torch.float64)
+    rc = lib.tfp_moments(_vp(xs), _ip(D), len(xs), rows, part.data_ptr(), need, out.data_ptr(), _stream(xs[0]))
+    if rc == -4:
+        return None
+    _chk(rc, "tfp_moments")
+    return out
+
+
+def norm_merge(runs, batches, k, stride, mean_fs, inv_std_fs):
+    """merge, per record q (one or two), the k batch records batches[q][j * stride : ...], j = 0 .. k - 1 in this order, into the running record runs[q]
+    (float64 [1 + 2 D], in place) and publish mean_fs[q] / inv_std_fs[q] (float32 [D], in place); ONE launch.  `batches[q]` is a float64 view whose
+    first element is record 0 of input q - e.g. a slice of the gathered vectors of all ranks."""
+    n = len(runs)
+    assert 0 < n <= 2 and all(r.dtype == torch.float64 and r.is_contiguous() for r in runs)
+    D = [(r.numel() - 1) // 2 for r in runs]
+    assert all(b.dtype == torch.float64 and b.is_contiguous() and b.numel() >= (k - 1) * stride + 1 + 2 * d for b, d in zip(batches, D))
+    assert all(m.dtype == torch.float32 and m.numel() == d and i.dtype == torch.float32 and i.numel() == d for m, i, d in zip(mean_fs, inv_std_fs, D))
+    _chk(load().tfp_norm_merge(_vp(runs), _vp(batches), _ip(D), n, int(k), int(stride), _vp(mean_fs), _vp(inv_std_fs), _stream(runs[0])), "tfp_norm_merge")
 
 
 # ---- the rollout's bookkeeping (ppo.PPOTrainer.rollout) -----------------------------------------------------------------------------------
@@ -488,11 +562,21 @@ def _walkable(nets):
             and all(x.dim() == 2 and x.is_contiguous() and x.shape[0] == nets[0][0].shape[0] for x, _ in nets))
 
 
-def mlp_walk_forward(nets, store_hidden=True):
+class TfpNorm(C.Structure):
+    """include/trifinger_ppo_norm.h: TfpNorm"""
+    _fields_ = [("mean", C.c_void_p), ("inv_std", C.c_void_p), ("clip", C.c_float)]
+
+
+def mlp_walk_forward(nets, store_hidden=True, norms=None):
     """nets: [(x, layers)] for one or two Linear / ELU stacks over the same rows (`layers` as in mlp_forward).  ONE launch; returns the list of layer
     outputs per network (hidden outputs None with store_hidden = False: the rollout needs the network outputs only), or None when the shapes do not
-    fit the walk (the caller then runs the layers one by one)."""
+    fit the walk (the caller then runs the layers one by one).  `norms`: None, or per network None / (mean_f, inv_std_f, clip): that network reads
+    clamp((x - mean_f) * inv_std_f, -clip, clip), formed while the rows are staged (tfp_mlp_forward_norm) - the bits of the plain walk on normalize_rows(x)."""
     if not _walkable(nets):
+        return None
+    if norms is not None and not any(e is not None for e in norms):
+        norms = None
+    if norms is not None and not (len(norms) == len(nets) and all(e is None or _norm_ok(e, x.shape[1], x.device) for e, (x, _) in zip(norms, nets))):
         return None
     M = nets[0][0].shape[0]
     arr = (TfpMlp * len(nets))()
@@ -507,7 +591,14 @@ def mlp_walk_forward(nets, store_hidden=True):
             ys.append(y)
         arr[i] = m
         outs.append(ys)
-    rc = load().tfp_mlp_forward(C.cast(arr, C.c_void_p), len(nets), M, _stream(nets[0][0]))
+    if norms is not None:
+        nm = (TfpNorm * len(nets))()
+        for i, e in enumerate(norms):
+            if e is not None:
+                nm[i].mean, nm[i].inv_std, nm[i].clip = e[0].data_ptr(), e[1].data_ptr(), float(e[2])
+        rc = load().tfp_mlp_forward_norm(C.cast(arr, C.c_void_p), C.cast(nm, C.c_void_p), len(nets), M, _stream(nets[0][0]))
+    else:
+        rc = load().tfp_mlp_forward(C.cast(arr, C.c_void_p), len(nets), M, _stream(nets[0][0]))
     if rc == -4:
         return None
     _chk(rc, "tfp_mlp_forward")
@@ -549,12 +640,19 @@ def _pairable(la, lc):
     return len(la) == len(lc) and all(a[2] == c[2] for a, c in zip(la, lc))
 
 
-def mlp_forward_pair(xa, la, xc, lc, store_hidden=True):
-    """mlp_forward of two networks of the same depth and activations, one grouped launch per layer (4 launches instead of 8 for the trainer's MLPs)"""
+def mlp_forward_pair(xa, la, xc, lc, store_hidden=True, norms=None):
+    """mlp_forward of two networks of the same depth and activations, one grouped launch per layer (4 launches instead of 8 for the trainer's MLPs).
+    `norms` = (actor's, critic's), each None or (mean_f, inv_std_f, clip): the inputs are RAW and normalised on the way in - inside the walk, or by one
+    normalize_rows launch per network in front of the per-layer path."""
+    if norms is not None and not any(e is not None for e in norms):
+        norms = None
     if USE_WALK:
-        out = mlp_walk_forward([(xa, la), (xc, lc)], store_hidden)
+        out = mlp_walk_forward([(xa, la), (xc, lc)], store_hidden, norms)
         if out is not None:
             return out[0], out[1]
+    if norms is not None:
+        xa = normalize_rows(xa, *norms[0]) if norms[0] is not None else xa
+        xc = normalize_rows(xc, *norms[1]) if norms[1] is not None else xc
     if not _pairable(la, lc):
         return mlp_forward(xa, la), mlp_forward(xc, lc)
     ya, yc = [], []
