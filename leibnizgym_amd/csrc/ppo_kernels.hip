@@ -15,10 +15,15 @@
 //   ent     = sum_a (log sigma_a + 0.5 + 0.5 log 2 pi)
 //   loss    = a_loss + v_coef c_loss - ent_coef ent + bounds_coef b_loss
 //   kl      = mean_i sum_a 0.5 ((mu_ia - old_mu_ia) / sigma_a)^2          (statistic only)
+// tfp_ppo_loss_vclip (include/trifinger_ppo_value.h; `clip_value`) is the same kernel with the value term clipped around the rollout's value:
+//   vc_i    = old_v_i + clamp(v_i - old_v_i, -e, e);   L_u = (v_i - ret_i)^2,  L_c = (vc_i - ret_i)^2
+//   c_i     = L_u when |v_i - old_v_i| <= e or L_u >= L_c, else L_c  (= max(L_u, L_c) outside the range; inside it the two agree to rounding and L_u is taken)
+//   d c_i / d v_i = 2 (v_i - ret_i) on the first branch, 0 on the second
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include <stdint.h>
 #include <string.h>
+#include "../../include/trifinger_ppo_value.h"       // declares the value-side entry points (and trifinger_ppo.h): a definition that drifts fails here
 
 #define MAX_A 18
 
@@ -33,13 +38,14 @@ __device__ __forceinline__ float wave_sum(float x) {
 // One objective at a time per device (the trainer's single stream); results as before up to the order of the atomic sums.
 __device__ float g_loss_acc[24];
 __device__ unsigned g_loss_ticket;
-template <int A>
+template <int A, bool VCLIP>
 __global__ void __launch_bounds__(256) k_ppo_loss(const float* __restrict__ mu, const float* __restrict__ log_std, const float* __restrict__ act,
                                                   const float* __restrict__ old_nlp, const float* __restrict__ adv,
                                                   const float* __restrict__ old_mu, const float* __restrict__ v,
                                                   const float* __restrict__ ret, int B, float e_clip, float v_coef, float ent_coef,
                                                   float bounds_coef, float* __restrict__ d_mu, float* __restrict__ d_v,
-                                                  float* __restrict__ d_logstd, float* __restrict__ loss_out, float* __restrict__ stats) {
+                                                  float* __restrict__ d_logstd, float* __restrict__ loss_out, float* __restrict__ stats,
+                                                  const float* __restrict__ old_v) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const bool valid = i < B;
     const float invB = 1.0f / (float)B;
@@ -72,7 +78,16 @@ __global__ void __launch_bounds__(256) k_ppo_loss(const float* __restrict__ mu, 
         const float g_nlp = g_ratio * (-ratio) * invB;            // d loss / d nlp_i
         const float dv_ = v[i] - ret[i];
         c_term = dv_ * dv_;
-        d_v[i] = v_coef * 2.0f * dv_ * invB;
+        if constexpr (VCLIP) {
+            // the unclipped branch inside the range (both agree there) or when it is the larger one - the selection of the surrogate above
+            const float vo = old_v[i], dlt = v[i] - vo;
+            const float dc_ = (vo + fminf(fmaxf(dlt, -e_clip), e_clip)) - ret[i], lc = dc_ * dc_;
+            const bool unclipped = (dlt >= -e_clip && dlt <= e_clip) || c_term >= lc;
+            d_v[i] = unclipped ? v_coef * 2.0f * dv_ * invB : 0.0f;
+            c_term = unclipped ? c_term : lc;
+        } else {
+            d_v[i] = v_coef * 2.0f * dv_ * invB;
+        }
 #pragma unroll
         for (int a = 0; a < A; ++a) {
             const float hi = fmaxf(m[a] - 1.1f, 0.0f), lo = fmaxf(-1.1f - m[a], 0.0f);
@@ -208,12 +223,30 @@ int tfp_ppo_loss(const float* mu, const float* log_std, const float* act, const 
     if (B <= 0 || (A != 9 && A != 18)) return -1;
     hipStream_t s = (hipStream_t)stream;
     dim3 grid((B + 255) / 256), block(256);
+    const float* no_old_v = nullptr;
     if (A == 9)
-        hipLaunchKernelGGL((k_ppo_loss<9>), grid, block, 0, s, mu, log_std, act, old_nlp, adv, old_mu, v, ret, B, e_clip, v_coef, ent_coef,
-                           bounds_coef, d_mu, d_v, d_logstd, loss_out, stats);
+        hipLaunchKernelGGL((k_ppo_loss<9, false>), grid, block, 0, s, mu, log_std, act, old_nlp, adv, old_mu, v, ret, B, e_clip, v_coef, ent_coef,
+                           bounds_coef, d_mu, d_v, d_logstd, loss_out, stats, no_old_v);
     else
-        hipLaunchKernelGGL((k_ppo_loss<18>), grid, block, 0, s, mu, log_std, act, old_nlp, adv, old_mu, v, ret, B, e_clip, v_coef, ent_coef,
-                           bounds_coef, d_mu, d_v, d_logstd, loss_out, stats);
+        hipLaunchKernelGGL((k_ppo_loss<18, false>), grid, block, 0, s, mu, log_std, act, old_nlp, adv, old_mu, v, ret, B, e_clip, v_coef, ent_coef,
+                           bounds_coef, d_mu, d_v, d_logstd, loss_out, stats, no_old_v);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// include/trifinger_ppo_value.h: tfp_ppo_loss with the value term clipped around old_v [B] (the compile-time variant of the same kernel: its accumulators,
+// its ticket, its one-call-at-a-time contract - the two entry points count as the same call)
+int tfp_ppo_loss_vclip(const float* mu, const float* log_std, const float* act, const float* old_nlp, const float* adv, const float* old_mu,
+                       const float* v, const float* ret, const float* old_v, int32_t B, int32_t A, float e_clip, float v_coef, float ent_coef,
+                       float bounds_coef, float* d_mu, float* d_v, float* d_logstd, float* loss_out, float* stats, void* stream) {
+    if (B <= 0 || (A != 9 && A != 18) || !old_v) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid((B + 255) / 256), block(256);
+    if (A == 9)
+        hipLaunchKernelGGL((k_ppo_loss<9, true>), grid, block, 0, s, mu, log_std, act, old_nlp, adv, old_mu, v, ret, B, e_clip, v_coef, ent_coef,
+                           bounds_coef, d_mu, d_v, d_logstd, loss_out, stats, old_v);
+    else
+        hipLaunchKernelGGL((k_ppo_loss<18, true>), grid, block, 0, s, mu, log_std, act, old_nlp, adv, old_mu, v, ret, B, e_clip, v_coef, ent_coef,
+                           bounds_coef, d_mu, d_v, d_logstd, loss_out, stats, old_v);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
@@ -801,6 +834,35 @@ __global__ void __launch_bounds__(256) k_gae(const float* __restrict__ rew, cons
         ret[(size_t)t * n + i] = last + v0;
     }
 }
+// `normalize_value` (include/trifinger_ppo_value.h): k_gae on values the network emits in NORMALISED units.  y [T + 1, n] is its raw output; the value of
+// a step is v = clamp(y, -clip, clip) / inv_std + mean (quotient and sum rounded separately), GAE runs on v with the operations of k_gae in their order, and
+// next to adv and ret (reward units) the thread files what the minibatches regress on and clip around: ret_n = clamp((ret - mean) * inv_std, -clip, clip) and
+// v_old_n = clamp(y[t], -clip, clip).  mean / inv_std: the record's published floats, read from the device (no host value enters the launch).
+__device__ __forceinline__ float clampf_nan(float x, float c) { return x < -c ? -c : (x > c ? c : x); }     // torch.clamp: a NaN stays a NaN
+__global__ void __launch_bounds__(256) k_gae_vnorm(const float* __restrict__ rew, const float* __restrict__ done, const float* __restrict__ y,
+                                                   const float* __restrict__ mean_f, const float* __restrict__ inv_std_f, float clip, float gamma, float gamma_tau,
+                                                   int T, int n, float* __restrict__ adv, float* __restrict__ ret, float* __restrict__ ret_n, float* __restrict__ v_old_n) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float mean = mean_f[0], inv = inv_std_f[0];
+    float last = 0.0f;
+    const float yT = clampf_nan(y[(size_t)T * n + i], clip), qT = yT / inv;
+    float v1 = qT + mean;                                     // the value of step t + 1
+    for (int t = T - 1; t >= 0; --t) {
+        const float yc = clampf_nan(y[(size_t)t * n + i], clip), q = yc / inv, v0 = q + mean;
+        const float nd = 1.0f - done[(size_t)t * n + i];
+        const float gv = gamma * v1, gvn = gv * nd, s1 = rew[(size_t)t * n + i] + gvn, delta = s1 - v0;
+        const float gn = gamma_tau * nd, gl = gn * last;
+        last = delta + gl;
+        const float r = last + v0, rm = r - mean, rs = rm * inv;
+        adv[(size_t)t * n + i] = last;
+        ret[(size_t)t * n + i] = r;
+        ret_n[(size_t)t * n + i] = clampf_nan(rs, clip);
+        v_old_n[(size_t)t * n + i] = yc;
+        v1 = v0;
+    }
+}
 
 // ---- one launch for the chunk sums of every layer of a backward pass ----
 struct SumArgs { const float* part[8]; float* gw[8]; float* gb[8]; int splits[8]; int n1[8]; int n2[8]; int first[9]; int n; };
@@ -851,6 +913,13 @@ int tfp_rollout_reward(const float* r, const void* done_bytes, float scale, int3
 int tfp_gae(const float* rew, const float* done, const float* val, float gamma, float gamma_tau, int32_t T, int32_t n, float* adv, float* ret, void* stream) {
     if (n <= 0 || T <= 0) return -1;
     hipLaunchKernelGGL(k_gae, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rew, done, val, gamma, gamma_tau, T, n, adv, ret);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+int tfp_gae_vnorm(const float* rew, const float* done, const float* y, const float* mean_f, const float* inv_std_f, float clip, float gamma, float gamma_tau,
+                  int32_t T, int32_t n, float* adv, float* ret, float* ret_n, float* v_old_n, void* stream) {
+    if (n <= 0 || T <= 0 || !mean_f || !inv_std_f || !(clip > 0.0f)) return -1;
+    hipLaunchKernelGGL(k_gae_vnorm, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rew, done, y, mean_f, inv_std_f, clip, gamma, gamma_tau, T, n,
+                       adv, ret, ret_n, v_old_n);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 // the products of tfp_gemm_tn_partials summed for n <= 8 layers in one launch (fixed order over the chunks: deterministic)

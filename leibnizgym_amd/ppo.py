@@ -14,6 +14,16 @@ best-so-far saving and a deterministic `play` mode mirror what the reference get
 `normalize_input` (the actor's `obs`) and `central_value_config.normalize_input` (the value network's `states`) are honoured by running moments
 modelled on RL-Games' RunningMeanStd (`InputNorm`): fp64 {count, mean, M2} per input on the device, frozen for a whole epoch (rollout and every
 minibatch of the update that follows read the same record), updated ONCE at the end of `update()` with the moments of the epoch's raw rollout buffer.
+The value side of the tree: `clip_value` (the critic's, without a central value network) / `central_value_config.clip_value` (the central value network's)
+clip the value loss around the value recorded in the rollout with the surrogate's e_clip - c_i = (v - ret)^2 inside the range or where it is the larger
+term, (v_old + clamp(v - v_old, -e, e) - ret)^2 otherwise (`clipped_value_loss`: a `where`, so that the gradient is 2 (v - ret) or 0 and never halves on a
+tie as torch.max's does; the kernel makes the same selection).  `normalize_value` keeps ONE more `InputNorm(dim=1)`, of the returns: the value network's
+output is read as a NORMALISED value; rollout values enter GAE de-normalised, v = clamp(y, -5, 5) / inv_std_f + mean_f; the critic regresses on
+ret_n = clamp((ret - mean_f) * inv_std_f, -5, 5) and clips around clamp(y_old, -5, 5), so c_loss and its clip range are in normalised units; advantages,
+`mean_reward` and the KL statistic are what they were.  The record is frozen for the epoch like the input records and merged with them at the end of
+`update()` (the same single all_gather) with the moments of the epoch's de-normalised returns buf["ret"], T n samples.  Deliberately NOT RL-Games here:
+it merges values as well as returns, and before it normalises; its de-normalisation multiplies by sqrt(var + eps) where this divides by the published
+inv_std_f (no third published quantity).  `act()` / `play()` neither read nor move the record; `ActorCritic.value_denorm` gives a value in reward units.
 
 This is host-side training glue, NOT part of the measured hot path.  On a GPU the minibatch step runs on the hand-written kernels of
 csrc/ppo_kernels.hip (leibnizgym_amd/ppo_kernels.py): one gather launch, the Linear / ELU layers on fp32 MFMA, the objective with all
@@ -66,6 +76,9 @@ class PPOConfig:
     fused_kernels: bool = True        # hand-written HIP kernel for the objective, forward and backward in one launch (GPU only)
     normalize_input: bool = False     # params.config.normalize_input: running mean / std of `obs` in front of the actor (and of a critic that reads obs)
     normalize_input_value: bool = False   # central_value_config.normalize_input: the same for `states` in front of the central value network
+    clip_value: bool = False          # params.config.clip_value: the critic's value loss clipped around the rollout's value (no central value network)
+    clip_value_central: bool = False  # central_value_config.clip_value: the same for the central value network (when there is one)
+    normalize_value: bool = False     # params.config.normalize_value: running mean / std of the returns; the value network works in normalised units
 
     @classmethod
     def from_rlg(cls, rlg: dict, num_envs: int = None, **overrides):
@@ -85,12 +98,14 @@ class PPOConfig:
                   actor_init=str(net["mlp"]["initializer"]["name"]),
                   save_frequency=int(c.get("save_frequency", 100)), save_best_after=int(c.get("save_best_after", 500)),
                   max_epochs=int(c.get("max_epochs", 100000)), name=str(c.get("name", "trifinger")),
-                  seed=int(rlg.get("seed", 7)), normalize_input=bool(c.get("normalize_input", False)))
+                  seed=int(rlg.get("seed", 7)), normalize_input=bool(c.get("normalize_input", False)),
+                  clip_value=bool(c.get("clip_value", False)), normalize_value=bool(c.get("normalize_value", False)))
         if cv:
             init = cv["network"]["mlp"]["initializer"]
             kw.update(lr_value=float(cv["lr"]), value_mini_epochs=int(cv["mini_epochs"]),
                       value_grad_norm=float(cv["grad_norm"]), value_init=str(init["name"]),
-                      value_init_scale=float(init.get("scale", 2.0)), normalize_input_value=bool(cv.get("normalize_input", False)))
+                      value_init_scale=float(init.get("scale", 2.0)), normalize_input_value=bool(cv.get("normalize_input", False)),
+                      clip_value_central=bool(cv.get("clip_value", False)))
         if num_envs:
             kw["minibatches"] = max(1, kw["horizon"] * int(num_envs) // int(c["minibatch_size"]))
         kw.update(overrides)
@@ -248,18 +263,32 @@ class InputNorm:
     def state_dict(self):
         return {"state": self.state.clone(), "mean_f": self.mean_f.clone(), "inv_std_f": self.inv_std_f.clone()}
 
-    def check_state_dict(self, sd, what):
+    def check_state_dict(self, sd, what, kind="input_norm"):
         for k, t in (("state", self.state), ("mean_f", self.mean_f), ("inv_std_f", self.inv_std_f)):
             if not isinstance(sd, dict) or k not in sd or tuple(sd[k].shape) != tuple(t.shape):
-                raise ValueError(f"checkpoint input_norm record '{what}': '{k}' missing or of another width (this trainer: {self.dim} columns)")
+                raise ValueError(f"checkpoint {kind} record '{what}': '{k}' missing or of another width (this trainer: {self.dim} columns)")
 
     def load_state_dict(self, sd):
         self.state.copy_(sd["state"]); self.mean_f.copy_(sd["mean_f"]); self.inv_std_f.copy_(sd["inv_std_f"])   # the published bits as they were saved
 
 
+def clipped_value_loss(v, ret, old_v, e):
+    """per sample: (v - ret)^2 inside |v - old_v| <= e or where it is the larger term, (old_v + clamp(v - old_v, -e, e) - ret)^2 otherwise.  A `where`
+    on purpose: the gradient is 2 (v - ret) or 0, the selection of tfp_ppo_loss_vclip (torch.max would halve it on a tie)"""
+    lu = (v - ret).pow(2)
+    lc = (old_v + (v - old_v).clamp(-e, e) - ret).pow(2)
+    return torch.where(((v - old_v).abs() <= e) | (lu >= lc), lu, lc)
+
+
+def denormalize_value(y, rec: "InputNorm"):
+    """a normalised value -> reward units: clamp(y, -clip, clip) / inv_std_f + mean_f, float32, quotient and sum rounded separately"""
+    return torch.clamp(y, -rec.clip, rec.clip) / rec.inv_std_f + rec.mean_f
+
+
 class ActorCritic(nn.Module):
     obs_norm = None            # InputNorm of `obs` / of `states` (plain attributes, not modules: the model's state_dict keeps its keys); set by the trainer
     state_norm = None
+    value_norm = None          # InputNorm(1) of the returns (`normalize_value`): `value` then returns NORMALISED values, `value_denorm` reward units
 
     def __init__(self, obs_dim, state_dim, act_dim, units, cfg: "PPOConfig" = None):
         super().__init__()
@@ -294,6 +323,11 @@ class ActorCritic(nn.Module):
     def value(self, obs, states):
         x, nm = (states if self.central else obs), self.critic_norm()
         return self.critic(nm.normalize(x) if nm is not None else x).squeeze(-1)
+
+    def value_denorm(self, obs, states):
+        """the value in reward units, whether or not the network works in normalised ones"""
+        y = self.value(obs, states)
+        return denormalize_value(y, self.value_norm) if self.value_norm is not None else y
 
     def dist(self, obs):
         mu = self.actor(self.obs_norm.normalize(obs) if self.obs_norm is not None else obs)
@@ -353,6 +387,11 @@ class PPOTrainer:
             self.net.obs_norm = InputNorm(obs_dim, self.device, fused=fk)
         if c.normalize_input_value and self.net.central:
             self.net.state_norm = InputNorm(state_dim, self.device, fused=fk)
+        # the value side: which clip_value key applies depends on who is the critic; the returns' record exists only when normalize_value is on
+        self.clip_v = bool(c.clip_value_central if self.net.central else c.clip_value)
+        self.value_norm = None
+        if c.normalize_value:
+            self.value_norm = self.net.value_norm = InputNorm(1, self.device, fused=fk)
         self.dist_on = False
         self.n_grad_allreduce = self.n_kl_allreduce = 0       # collectives issued so far (what a test of the distributed path counts)
         self.n_norm_allgather = 0
@@ -501,6 +540,8 @@ class PPOTrainer:
         recs = self._norm_records()
         if recs:                                                     # the key exists only when normalisation is on
             sd["input_norm"] = {k: r.state_dict() for k, r in recs.items()}
+        if self.value_norm is not None:                              # likewise
+            sd["value_norm"] = self.value_norm.state_dict()
         return sd
 
     def save(self, path: str):
@@ -522,6 +563,11 @@ class PPOTrainer:
                              "(normalize_input / central_value_config.normalize_input differ)")
         for k, r in recs.items():
             r.check_state_dict(ck_recs[k], k)
+        if (ck.get("value_norm") is not None) != (self.value_norm is not None):
+            raise ValueError(f"checkpoint {'normalises' if ck.get('value_norm') is not None else 'does not normalise'} the value, this trainer "
+                             f"{'does' if self.value_norm is not None else 'does not'} (normalize_value differs)")
+        if self.value_norm is not None:
+            self.value_norm.check_state_dict(ck["value_norm"], "returns", kind="value_norm")
         if "optimizer" in ck:
             parsed = self._parse_optimizer_state(ck["optimizer"])
         with torch.no_grad():                                        # in place: the parameters may be views of a flat buffer
@@ -529,6 +575,8 @@ class PPOTrainer:
                 v.copy_(ck["model"][k])
             for k, r in recs.items():
                 r.load_state_dict(ck_recs[k])
+            if self.value_norm is not None:
+                self.value_norm.load_state_dict(ck["value_norm"])
             if "optimizer" in ck:
                 self._load_optimizer_state(ck["optimizer"], ck.get("lr"), parsed)
         self.lr = float(ck.get("lr", self.lr))
@@ -605,9 +653,17 @@ class PPOTrainer:
                 buf["done"][t] = d.to(dev).float()
         buf["val"][T] = self.net.value(obs, states)
         self.last = (obs, states)
-        if fused:
+        vn = self.value_norm
+        if vn is not None and fused:
+            # buf["val"] holds the network's raw output y, a NORMALISED value: GAE runs on v = clamp(y, -5, 5) / inv_std_f + mean_f (module docstring), which
+            # the kernel forms on the way - buf["val"] keeps y on this path, the torch form below replaces it by v
+            buf["adv"], buf["ret"], buf["ret_n"], buf["v_old_n"] = pk.gae_vnorm(buf["rew"], buf["done"], buf["val"], vn.mean_f, vn.inv_std_f, vn.clip, c.gamma, c.tau)
+        elif fused:
             buf["adv"], buf["ret"] = pk.gae(buf["rew"], buf["done"], buf["val"], c.gamma, c.tau)
         else:
+            if vn is not None:
+                buf["v_old_n"] = torch.clamp(buf["val"][:T], -vn.clip, vn.clip)
+                buf["val"] = denormalize_value(buf["val"], vn)
             adv = torch.zeros(T, n, device=dev)
             last = torch.zeros(n, device=dev)
             for t in reversed(range(T)):
@@ -617,6 +673,8 @@ class PPOTrainer:
                 adv[t] = last
             buf["ret"] = adv + buf["val"][:T]
             buf["adv"] = adv
+            if vn is not None:
+                buf["ret_n"] = torch.clamp((buf["ret"] - vn.mean_f) * vn.inv_std_f, -vn.clip, vn.clip)
         self.frames += T * n
         return buf
 
@@ -634,7 +692,10 @@ class PPOTrainer:
         a = d["adv"][idx]
         a_loss = torch.max(-a * ratio, -a * ratio.clamp(1 - c.e_clip, 1 + c.e_clip)).mean()
         v = self.net.value(obs, d["states"][idx] if d["states"] is not None else None)
-        c_loss = (v - d["ret"][idx]).pow(2).mean()
+        if self.clip_v:
+            c_loss = clipped_value_loss(v, d["ret"][idx], d["old_v"][idx], c.e_clip).mean()
+        else:
+            c_loss = (v - d["ret"][idx]).pow(2).mean()
         b_loss = ((mu - 1.1).clamp(min=0).pow(2) + (-1.1 - mu).clamp(min=0).pow(2)).sum(-1).mean()
         ent = (ls + 0.5 + 0.5 * math.log(2 * math.pi)).sum(-1).mean()
         # with a central value network RL-Games trains it on its own unweighted MSE and drops the critic term from the
@@ -650,22 +711,27 @@ class PPOTrainer:
             acc["loss"] += loss.detach(); acc["a_loss"] += a_loss.detach(); acc["c_loss"] += c_loss.detach()
 
     def _mb_backward_fused(self, d, idx, acc, obs):
-        """the same step on the hand-written kernels: one gather launch for the seven minibatch arrays, the MFMA layers, the objective
+        """the same step on the hand-written kernels: one gather launch for the seven minibatch arrays (eight with `clip_value`: old_v), the MFMA layers, the objective
         and its gradients in ONE launch (ppo_kernels.ppo_loss_and_grads), the backward pass started at the network outputs with those
         gradients (no loss node), the chunk sums of all weight gradients in one launch.  Every parameter gradient lands in its slot of
         the flat gradient buffer directly (the log-std gradient too), so that the optimiser reads nothing but that buffer; the
         statistics accumulate on the device in `acc["_fused"]` = (loss, a_loss, c_loss, kl)"""
         from . import ppo_kernels as pk
         c = self.cfg
-        srcs = [d["obs"], d["act"], d["old_nlp"], d["adv"], d["ret"], d["old_mu"]] + ([d["states"]] if d["states"] is not None else [])
+        srcs = [d["obs"], d["act"], d["old_nlp"], d["adv"], d["ret"], d["old_mu"]] + ([d["old_v"]] if self.clip_v else []) + \
+               ([d["states"]] if d["states"] is not None else [])
+        assert len(srcs) <= pk.GATHER_MAX                  # obs, act, old_nlp, adv, ret (or ret_n), old_mu, old_v, states: exactly one launch's worth
         na, ns = self.net.obs_norm, self.net.state_norm
         if na is None and ns is None:
             g = pk.gather_rows(srcs, idx)
         else:                                      # the same launch writes obs / states normalised: what the forward AND the first layers' weight gradients read
-            nm = [na.stats() if na is not None else None] + [None] * 5 + ([ns.stats() if ns is not None else None] if d["states"] is not None else [])
+            nm = [na.stats() if na is not None else None] + [None] * (len(srcs) - 1)
+            if d["states"] is not None:
+                nm[-1] = ns.stats() if ns is not None else None
             g = pk.gather_rows(srcs, idx, norm=nm)
         obs, act, old_nlp, adv, ret, old_mu = g[:6]
-        states = g[6] if d["states"] is not None else None
+        old_v = g[6] if self.clip_v else None
+        states = g[-1] if d["states"] is not None else None
         for p in self.net.parameters():
             p.grad = None
         # no autograd: the structure is fixed (two Linear / ELU stacks), so the step is a straight sequence of kernel launches from this
@@ -676,8 +742,9 @@ class PPOTrainer:
             ya, yc = pk.mlp_forward_pair(obs, la, xc, lc)        # layer k of both networks in one launch
             mu, v = ya[-1], yc[-1].squeeze(-1)
             v_coef = 1.0 if self.net.central else 0.5 * c.critic_coef
+            kw = {"old_v": old_v} if self.clip_v else {}
             _, d_mu, d_v, _ = pk.ppo_loss_and_grads(mu, self.net.log_std, v, act, old_nlp, adv, ret, old_mu, acc["_fused"], c.e_clip, v_coef,
-                                                    c.entropy_coef, c.bounds_loss_coef, d_ls_out=self.flat_opt.grad_view(self.net.log_std))
+                                                    c.entropy_coef, c.bounds_loss_coef, d_ls_out=self.flat_opt.grad_view(self.net.log_std), **kw)
             try:
                 pk.mlp_backward_pair(obs, ya, d_mu, la, xc, yc, d_v.unsqueeze(-1), lc)
                 pk.flush_partial_sums()
@@ -728,8 +795,11 @@ class PPOTrainer:
         adv = flat(buf["adv"])
         if c.normalize_advantage:
             adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+        vn = self.value_norm
         src = dict(obs=flat(buf["obs"]), states=flat(buf["states"]), act=flat(buf["act"]), old_nlp=flat(buf["nlp"]),
-                   ret=flat(buf["ret"]), adv=adv, old_mu=flat(buf["mu"]))
+                   ret=flat(buf["ret_n"] if vn is not None else buf["ret"]), adv=adv, old_mu=flat(buf["mu"]))
+        if self.clip_v:                            # the value the loss is clipped around, in the units the network works in
+            src["old_v"] = flat(buf["v_old_n"] if vn is not None else buf["val"][:T])
         total = T * n
         mb = max(1, total // c.minibatches)
         dev = src["obs"].device
@@ -769,7 +839,10 @@ class PPOTrainer:
                     self.flat_opt.set_lr(1, self.lr)
             for g in (self.opt.param_groups[:1] if self.net.central else self.opt.param_groups):
                 g["lr"] = self.lr
-        self._update_input_norm(src)
+        if vn is not None:
+            self._update_value_norm(src, buf)
+        else:
+            self._update_input_norm(src)
         for k in ("loss", "a_loss", "c_loss"):
             stats[k] = float(acc[k]) / max(count, 1)
         stats["lr"] = self.lr
@@ -777,22 +850,36 @@ class PPOTrainer:
         return stats
 
     @torch.no_grad()
-    def _update_input_norm(self, src):
+    def _update_value_norm(self, src, buf):
+        """`normalize_value`: the epoch's de-normalised returns buf["ret"] (T n samples) join the end-of-epoch merge of the input records - their moments
+        travel in the same vector, hence in the same all_gather"""
+        self._update_input_norm(src, returns=buf["ret"].reshape(-1, 1))
+
+    @torch.no_grad()
+    def _update_input_norm(self, src, returns=None):
         """the end of an epoch: the moments of its RAW rollout buffer (T n rows) merged into the running records, which then serve the next epoch.
         One pass over the buffer (ppo_kernels.moments: both inputs in one call) and one merge launch; a distributed run gathers every rank's batch vector
-        [1 + 2 Do (+ 1 + 2 Ds)] (float64) with ONE all_gather and merges them in rank order, so that all ranks keep the same record bit for bit."""
-        recs = self._norm_records()
+        [1 + 2 Do (+ 1 + 2 Ds)] (float64) with ONE all_gather and merges them in rank order, so that all ranks keep the same record bit for bit.
+        `returns` [T n, 1] (only from `_update_value_norm`): the returns' record [3] is appended to the vector - one more moments call and one more merge
+        launch (the kernels take up to two arrays per call), the same single all_gather."""
+        recs = dict(self._norm_records())
+        n_in = len(recs)
+        if returns is not None:
+            recs["returns"], src = self.value_norm, dict(src, returns=returns)
         if not recs:
             return
-        keys = list(recs)                                            # "obs" before "states"
+        keys = list(recs)                                            # "obs" before "states" before "returns"
         xs = [src[k] for k in keys]
         fused = self.fused_loss and all(x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() for x in xs)
-        vec = None
+        groups = [g for g in (keys[:n_in], keys[n_in:]) if g]        # one moments call / one merge launch each
         if fused:
             from . import ppo_kernels as pk
-            vec = pk.moments(xs)                                     # None: declined (a row wider than 256)
-        if vec is None:
-            vec = torch.cat([InputNorm.batch_record(x) for x in xs])
+        parts = []
+        for g in groups:
+            gx = [src[k] for k in g]
+            v = pk.moments(gx) if fused else None                    # None: declined (a row wider than 256)
+            parts.append(v if v is not None else torch.cat([InputNorm.batch_record(x) for x in gx]))
+        vec = parts[0] if len(parts) == 1 else torch.cat(parts)
         L, k = vec.numel(), 1
         if self.dist_on:
             k = self.dist.get_world_size(self.group)
@@ -805,8 +892,10 @@ class PPOTrainer:
             offs.append(off)
             off += 1 + 2 * recs[key].dim
         if fused:
-            pk.norm_merge([recs[key].state for key in keys], [vec[o:] for o in offs], k, L, [recs[key].mean_f for key in keys],
-                          [recs[key].inv_std_f for key in keys])
+            at = dict(zip(keys, offs))
+            for g in groups:
+                pk.norm_merge([recs[key].state for key in g], [vec[at[key]:] for key in g], k, L, [recs[key].mean_f for key in g],
+                              [recs[key].inv_std_f for key in g])
         else:
             rows = vec.view(k, L)
             for key, o in zip(keys, offs):

@@ -79,6 +79,11 @@ def load():
         lib.tfp_gather_rows_norm.argtypes = [C.c_void_p] * 6 + [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
         lib.tfp_mlp_forward_norm.restype = C.c_int
         lib.tfp_mlp_forward_norm.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+        # the value side (include/trifinger_ppo_value.h), bound by symbol like the normalisation
+        lib.tfp_ppo_loss_vclip.restype = C.c_int
+        lib.tfp_ppo_loss_vclip.argtypes = [C.c_void_p] * 9 + [C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float] + [C.c_void_p] * 6
+        lib.tfp_gae_vnorm.restype = C.c_int
+        lib.tfp_gae_vnorm.argtypes = [C.c_void_p] * 5 + [C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32] + [C.c_void_p] * 5
         _LIB = lib
     return _LIB
 
@@ -114,15 +119,22 @@ class _FusedPPOLoss(torch.autograd.Function):
         return d_mu * g, d_ls * g, d_v * g, None, None, None, None, None, None, None, None, None, None
 
 
-def ppo_loss_and_grads(mu, log_std, v, act, old_nlp, adv, ret, old_mu, stats, e_clip, v_coef, ent_coef, bounds_coef, d_ls_out=None):
+def ppo_loss_and_grads(mu, log_std, v, act, old_nlp, adv, ret, old_mu, stats, e_clip, v_coef, ent_coef, bounds_coef, d_ls_out=None, old_v=None):
     """(loss, d loss / d mu, d loss / d v, d loss / d log_std) straight from the kernel - for a caller that starts the backward pass at
-    the network outputs itself (`torch.autograd.backward((mu, v), (d_mu, d_v))`), without a loss node multiplying them by one"""
+    the network outputs itself (`torch.autograd.backward((mu, v), (d_mu, d_v))`), without a loss node multiplying them by one.
+    `old_v` [B] (the value recorded in the rollout): the value term is clipped around it with the surrogate's `e_clip` (tfp_ppo_loss_vclip: `clip_value`)"""
     lib = load()
     mu, v = mu.contiguous(), v.contiguous()
     B, A = mu.shape
     d_mu, d_v = torch.empty_like(mu), torch.empty_like(v)
     out = torch.empty(A + 1, device=mu.device, dtype=torch.float32)
     d_ls, loss = (out[:A] if d_ls_out is None else d_ls_out), out[A]      # d_ls_out: e.g. the parameter's slot of a flat gradient buffer
+    if old_v is not None:
+        assert old_v.dtype == torch.float32 and old_v.is_contiguous() and old_v.numel() == B and old_v.device == mu.device
+        _chk(lib.tfp_ppo_loss_vclip(mu.data_ptr(), log_std.data_ptr(), act.data_ptr(), old_nlp.data_ptr(), adv.data_ptr(), old_mu.data_ptr(),
+                                    v.data_ptr(), ret.data_ptr(), old_v.data_ptr(), B, A, float(e_clip), float(v_coef), float(ent_coef), float(bounds_coef),
+                                    d_mu.data_ptr(), d_v.data_ptr(), d_ls.data_ptr(), loss.data_ptr(), stats.data_ptr(), _stream(mu)), "tfp_ppo_loss_vclip")
+        return loss, d_mu, d_v, d_ls
     _chk(lib.tfp_ppo_loss(mu.data_ptr(), log_std.data_ptr(), act.data_ptr(), old_nlp.data_ptr(), adv.data_ptr(), old_mu.data_ptr(),
                           v.data_ptr(), ret.data_ptr(), B, A, float(e_clip), float(v_coef), float(ent_coef), float(bounds_coef),
                           d_mu.data_ptr(), d_v.data_ptr(), d_ls.data_ptr(), loss.data_ptr(), stats.data_ptr(), _stream(mu)), "tfp_ppo_loss")
@@ -266,13 +278,16 @@ def flush_partial_sums():
         _chk(load().tfp_sum_partials_multi(vp(0), vp(1), vp(2), ip(3), ip(4), ip(5), n, _stream(grp[0][0])), "tfp_sum_partials_multi")
 
 
+GATHER_MAX = 8        # arrays per tfp_gather_rows launch; the trainer's minibatch with every option on is exactly that many (ppo.PPOTrainer._mb_backward_fused)
+
+
 def gather_rows(srcs, idx, outs=None, norm=None):
     """[s[idx] for s in srcs] for up to 8 row-major float32 arrays (1-D arrays count as width 1) in ONE launch.  `norm`: None, or one entry per array -
     None (copied) or (mean_f, inv_std_f, clip): that array leaves as clamp((s[idx] - mean_f) * inv_std_f, -clip, clip) (tfp_gather_rows_norm), and `idx`
     may then be None (every row in place: a plain normaliser)."""
     if norm is not None and any(e is not None for e in norm):
         return _gather_rows_norm(srcs, idx, outs, norm)
-    assert 0 < len(srcs) <= 8 and idx.dtype == torch.long and idx.is_contiguous()
+    assert 0 < len(srcs) <= GATHER_MAX and idx.dtype == torch.long and idx.is_contiguous()
     rows = idx.numel()
     widths = [int(s[0].numel()) for s in srcs]
     if outs is None:
@@ -291,7 +306,7 @@ def _norm_ok(e, width, dev):
 
 
 def _gather_rows_norm(srcs, idx, outs, norm):
-    assert 0 < len(srcs) <= 8 and len(norm) == len(srcs) and all(s.dtype == torch.float32 and s.is_contiguous() for s in srcs)
+    assert 0 < len(srcs) <= GATHER_MAX and len(norm) == len(srcs) and all(s.dtype == torch.float32 and s.is_contiguous() for s in srcs)
     assert idx is None or (idx.dtype == torch.long and idx.is_contiguous())
     rows = idx.numel() if idx is not None else srcs[0].shape[0]
     assert idx is not None or all(s.shape[0] == rows for s in srcs)
@@ -369,6 +384,19 @@ def gae(rew, done, val, gamma, tau):
     adv, ret = torch.empty_like(rew), torch.empty_like(rew)
     _chk(load().tfp_gae(rew.data_ptr(), done.data_ptr(), val.data_ptr(), float(gamma), float(gamma * tau), T, n, adv.data_ptr(), ret.data_ptr(), _stream(rew)), "tfp_gae")
     return adv, ret
+
+
+def gae_vnorm(rew, done, y, mean_f, inv_std_f, clip, gamma, tau):
+    """(adv, ret, ret_n, v_old_n), each [T, n], in one launch for a value network whose raw output y [T + 1, n] is in normalised units (`normalize_value`):
+    v = clamp(y, -clip, clip) / inv_std_f + mean_f, `gae` on v, ret_n = clamp((ret - mean_f) * inv_std_f, -clip, clip), v_old_n = clamp(y[:T], -clip, clip);
+    mean_f / inv_std_f: the float32 [1] device tensors a ppo.InputNorm(1) publishes.  The bits of the torch expressions (tfp_gae_vnorm)."""
+    T, n = rew.shape
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.device == rew.device for t in (rew, done, y, mean_f, inv_std_f))
+    assert done.shape == (T, n) and y.shape == (T + 1, n) and mean_f.numel() == 1 and inv_std_f.numel() == 1 and float(clip) > 0.0
+    adv, ret, ret_n, v_old_n = (torch.empty_like(rew) for _ in range(4))
+    _chk(load().tfp_gae_vnorm(rew.data_ptr(), done.data_ptr(), y.data_ptr(), mean_f.data_ptr(), inv_std_f.data_ptr(), float(clip), float(gamma), float(gamma * tau),
+                              T, n, adv.data_ptr(), ret.data_ptr(), ret_n.data_ptr(), v_old_n.data_ptr(), _stream(rew)), "tfp_gae_vnorm")
+    return adv, ret, ret_n, v_old_n
 
 
 def gemm_tn_bias(a, b, y=None, chunk=256, out=None, defer=False):
