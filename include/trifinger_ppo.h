@@ -127,7 +127,9 @@ int tfp_gather_rows(const void* const* src, void* const* dst, const int32_t* wid
 /* Input normalisation (`normalize_input` / `central_value_config.normalize_input` of asymm.yaml): tfp_moments, tfp_moments_part_doubles, tfp_norm_merge,
  * tfp_gather_rows_norm and tfp_mlp_forward_norm (csrc/ppo_norm.hip; the statistics variant of the forward walk in csrc/ppo_mlp_walk.hip) are exported by the
  * same library and declared, with their semantics, in include/trifinger_ppo_norm.h.  They were added without a new API number: no entry point of this
- * header changed, tfp_mlp_forward launches the code it always did, and the binding finds the new ones by symbol. */
+ * header changed, tfp_mlp_forward launches the code it always did, and the binding finds the new ones by symbol.
+ * The network-shape keys (`network.mlp.activation`, `network.mlp.d2rl`): tfp_net_forward, tfp_net_backward and tfp_net_fits - the walk with activation codes
+ * 0 .. 6, the input concatenated behind the hidden outputs, optional statistics - are declared in include/trifinger_ppo_net.h, added the same way. */
 
 #ifdef __cplusplus
 }

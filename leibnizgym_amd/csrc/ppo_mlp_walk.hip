@@ -30,11 +30,20 @@
 // thread and K step of the NEXT layer (the buffer is that layer's A operand and stays intact throughout): 46 MB of stores per forward pass are spread
 // over the whole launch instead of arriving in bursts at the layer boundaries.  ELU is x > 0 ? x : exp(x) - 1 with exp on v_exp_f32 (the form torch's
 // kernel uses: exp - 1, not expm1; absolute error <= 1.2e-7).
+//
+// The extended walk (EXT; include/trifinger_ppo_net.h: tfp_net_forward / tfp_net_backward) is a compile-time variant of the same kernel, added the way
+// NORM was - the plain kernels keep their code and their argument block.  It knows the activation codes 0 .. 6 (the epilogue branches once per layer on
+// the wave-uniform code; backward: the derivative from the saved output) and d2rl: the operand of a hidden layer l >= 1 is [h | x], K = dim[l] + dim[0] -
+// the epilogue writes h as ever, the workgroup copies the row block's x columns behind it from the operand of the running layer, and the saved outputs go to
+// memory as these wide rows (the weight gradients stay plain products on them; rows of 441 / 513 floats miss StreamOut's dwordx4 path and leave at the layer
+// boundary).  The backward chain reads W with that leading dimension and N = dim[l], and the saved output with a row stride of its own.  The forward operands
+// of a d2rl walk are 110 KB at the trainer's shapes: that call may take the whole CU's LDS, one workgroup per CU.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
 #include "../../include/trifinger_ppo.h"
 #include "../../include/trifinger_ppo_norm.h"
+#include "../../include/trifinger_ppo_net.h"
 
 typedef float w4 __attribute__((ext_vector_type(4)));
 typedef float w4u __attribute__((ext_vector_type(4), aligned(4)));      // a dwordx4 load needs dword alignment only (rows of 41 / 113 floats)
@@ -72,6 +81,55 @@ __device__ __forceinline__ float elu_fast(float v) {
     // exp(v) - 1 for v <= 0 through v_exp_f32 (2^x): |error| <= 1.2e-7 absolute
     const float e = __builtin_amdgcn_exp2f(v * 1.44269504088896340736f) - 1.0f;
     return v > 0.0f ? v : e;
+}
+
+// The other activations of include/trifinger_ppo_net.h (the extended walk only: EXT).  CODE is a template argument: the epilogue branches ONCE per layer on
+// the wave-uniform code and runs a loop compiled for it.  exp / log through v_exp_f32 / v_log_f32 (2^x, log2), the quotients through v_rcp_f32 (1 ulp).
+#define WALK_SELU_L 1.0507009873554805f
+#define WALK_SELU_LA (1.0507009873554805f * 1.6732632423543772f)
+__device__ __forceinline__ float exp_fast(float v) { return __builtin_amdgcn_exp2f(v * 1.44269504088896340736f); }
+// tanh, intended to stay within a few ulp (the formula with exact exp and quotient: 2.5e-7 relative, tests/test_net_shape.py): 1 - 2 / (exp(2 |v|) + 1) with the sign of v from |v| = 0.625 on (exp = inf gives exactly 1, no NaN); below that the difference cancels
+// (an absolute 1e-7 on a result near 0 - which Adam, scale-free, turns into visibly different steps), so the odd polynomial v + v^3 P(v^2) of Cephes' tanhf
+__device__ __forceinline__ float tanh_fast(float v) {
+    const float a = __builtin_fabsf(v), z = v * v;
+    const float big = __builtin_copysignf(1.0f - 2.0f * __builtin_amdgcn_rcpf(exp_fast(2.0f * a) + 1.0f), v);
+    const float p = ((((-5.70498872745e-3f * z + 2.06390887954e-2f) * z - 5.37397155531e-2f) * z + 1.33314422036e-1f) * z - 3.33332819422e-1f) * z * v + v;
+    return a < 0.625f ? p : big;
+}
+template <int CODE>
+__device__ __forceinline__ float act_fwd(float v) {
+    if (CODE == TFP_ACT_ELU) return elu_fast(v);
+    if (CODE == TFP_ACT_RELU) return v > 0.0f ? v : 0.0f;
+    if (CODE == TFP_ACT_TANH) return tanh_fast(v);
+    if (CODE == TFP_ACT_SIGMOID) return __builtin_amdgcn_rcpf(1.0f + exp_fast(-v));                               // exp = inf: 0
+    if (CODE == TFP_ACT_SELU) return v > 0.0f ? WALK_SELU_L * v : WALK_SELU_LA * (exp_fast(v) - 1.0f);
+    if (CODE == TFP_ACT_SOFTPLUS) return v > 20.0f ? v : 0.69314718055994530942f * __builtin_amdgcn_logf(1.0f + exp_fast(v));
+    return v;
+}
+// the derivative from the saved OUTPUT y of the layer
+template <int CODE>
+__device__ __forceinline__ float act_der(float y) {
+    if (CODE == TFP_ACT_ELU) return y > 0.0f ? 1.0f : y + 1.0f;
+    if (CODE == TFP_ACT_RELU) return y > 0.0f ? 1.0f : 0.0f;
+    if (CODE == TFP_ACT_TANH) return 1.0f - y * y;
+    if (CODE == TFP_ACT_SIGMOID) return y * (1.0f - y);
+    if (CODE == TFP_ACT_SELU) return y > 0.0f ? WALK_SELU_L : y + WALK_SELU_LA;
+    if (CODE == TFP_ACT_SOFTPLUS) return 1.0f - exp_fast(-y);
+    return 1.0f;
+}
+template <int CODE, bool BWD, int NCT>
+__device__ __forceinline__ void act_tiles(w4 (&acc)[2][NCT], const float (&bv)[NCT], const w4 (&e)[2][BWD ? NCT : 1]) {
+#pragma unroll
+    for (int j = 0; j < NCT; ++j) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (BWD) acc[i][j][r] *= act_der<CODE>(e[i][BWD ? j : 0][r]);
+                else acc[i][j][r] = act_fwd<CODE>(acc[i][j][r] + bv[j]);
+            }
+        }
+    }
 }
 
 typedef unsigned u4 __attribute__((ext_vector_type(4)));
@@ -265,10 +323,12 @@ __device__ __forceinline__ void walk_layer(const float* Xs, int px, const float*
 // layer + epilogue for a wavefront with NCT column tiles.  Ys: LDS output [32][py] or nullptr (last product).  G: memory output [M, N], written here only
 // for the last product (the others leave through StreamOut during the next step).
 //   BWD = false: v = acc + bias, ELU when act;  BWD = true: v = acc * elu'(E[row, col]) when E (the saved output of the layer this is the dZ of)
-template <int NCT, bool BWD, bool SO>
-__device__ __forceinline__ void walk_run(const float* Xs, int px, const float* __restrict__ W, int K, int N, const float* __restrict__ bias, int act,
-                                         const float* __restrict__ E, float* Ys, int py, float* __restrict__ G, int row0, int M, int ct0, int nct,
-                                         StreamOut& so, int stamp) {
+//   EXT (the extended walk, include/trifinger_ppo_net.h): `act` is an activation code, forwards and backwards; ldw / lde are the leading dimensions of W and E
+//   (the plain walk passes BWD ? N : K and N); xcols: the columns of Ys behind N belong to the row block's input (d2rl) and are not written here.
+template <int NCT, bool BWD, bool SO, bool EXT>
+__device__ __forceinline__ void walk_run(const float* Xs, int px, const float* __restrict__ W, int ldw, int K, int N, const float* __restrict__ bias, int act,
+                                         const float* __restrict__ E, int lde, bool xcols, float* Ys, int py, float* __restrict__ G, int row0, int M, int ct0,
+                                         int nct, StreamOut& so, int stamp) {
     const int lane = threadIdx.x & 63, lr = lane & 15, kk = lane >> 4;
     const int colb = ct0 * 16 + lr;                                // + 16 j
     const int rowb = 4 * kk;                                       // + 16 i + r: C layout of the 16 x 16 forms, column = lane % 16, row = 4 (lane / 16) + register
@@ -285,7 +345,7 @@ __device__ __forceinline__ void walk_run(const float* Xs, int px, const float* _
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r) eoff[i][r] = (unsigned)min(row0 + rowb + 16 * i + r, M - 1) * (unsigned)N;
+                for (int r = 0; r < 4; ++r) eoff[i][r] = (unsigned)min(row0 + rowb + 16 * i + r, M - 1) * (unsigned)lde;
             }
         }
     } else {
@@ -318,10 +378,22 @@ __device__ __forceinline__ void walk_run(const float* Xs, int px, const float* _
         for (int j = 0; j < NCT; ++j) asm volatile("" : "+v"(acc[i][j]));       // the zeroing instructions stay in front of ...
     }
     asm volatile("s_nop 7" ::: "memory");                          // ... the wait states before the first MFMA reads an accumulator as srcC
-    walk_layer<NCT, BWD, SO>(Xs, px, W, BWD ? N : K, K, N, ct0, nct, so, acc, epi_load);
+    walk_layer<NCT, BWD, SO>(Xs, px, W, ldw, K, N, ct0, nct, so, acc, epi_load);
     walk_mfma_drain<NCT>(acc);
     WSTAMP(2 + 3 * stamp);
-    if (BWD) {
+    if (EXT) {
+        if (!BWD || E) {
+            switch (act) {                                          // uniform per layer
+                case TFP_ACT_ELU: act_tiles<TFP_ACT_ELU, BWD, NCT>(acc, bv, e); break;
+                case TFP_ACT_RELU: act_tiles<TFP_ACT_RELU, BWD, NCT>(acc, bv, e); break;
+                case TFP_ACT_TANH: act_tiles<TFP_ACT_TANH, BWD, NCT>(acc, bv, e); break;
+                case TFP_ACT_SIGMOID: act_tiles<TFP_ACT_SIGMOID, BWD, NCT>(acc, bv, e); break;
+                case TFP_ACT_SELU: act_tiles<TFP_ACT_SELU, BWD, NCT>(acc, bv, e); break;
+                case TFP_ACT_SOFTPLUS: act_tiles<TFP_ACT_SOFTPLUS, BWD, NCT>(acc, bv, e); break;
+                default: act_tiles<TFP_ACT_NONE, BWD, NCT>(acc, bv, e); break;
+            }
+        }
+    } else if (BWD) {
         if (E) {
 #pragma unroll
             for (int j = 0; j < NCT; ++j) {
@@ -350,6 +422,16 @@ __device__ __forceinline__ void walk_run(const float* Xs, int px, const float* _
             const bool full = (ct0 + j) * 16 + 16 <= N;            // uniform: the tile lies wholly inside the matrix (all but possibly the last one)
             if (Ys) {                                              // next step's A operand; zero in the padding columns
                 float* yp = Ys + rowb * py + col;
+                if (EXT && xcols) {                                 // the columns behind N hold the input: nothing is written there
+                    if (full || col < N) {
+#pragma unroll
+                        for (int i = 0; i < 2; ++i) {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) yp[(16 * i + r) * py] = acc[i][j][r];
+                        }
+                    }
+                    continue;
+                }
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
 #pragma unroll
@@ -377,16 +459,16 @@ __device__ __forceinline__ void walk_run(const float* Xs, int px, const float* _
 
 // this wavefront's share of a layer: all 32 rows and a quarter of the 16-column tiles (the first `nct_all % 4` wavefronts take one more); the tile count
 // selects the instantiation with exactly that many accumulator columns
-template <bool BWD>
-__device__ __forceinline__ void walk_dispatch(const float* Xs, int px, const float* __restrict__ W, int K, int N, const float* __restrict__ bias, int act,
-                                              const float* __restrict__ E, float* Ys, int py, float* __restrict__ G, int row0, int M, StreamOut& so,
-                                              bool has_so, int stamp) {
+template <bool BWD, bool EXT>
+__device__ __forceinline__ void walk_dispatch(const float* Xs, int px, const float* __restrict__ W, int ldw, int K, int N, const float* __restrict__ bias,
+                                              int act, const float* __restrict__ E, int lde, bool xcols, float* Ys, int py, float* __restrict__ G, int row0,
+                                              int M, StreamOut& so, bool has_so, int stamp) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nct_all = (N + 15) >> 4, base = nct_all >> 2, rem = nct_all & 3;
     const int nct = base + (wave < rem ? 1 : 0), ct0 = wave * base + min(wave, rem);
     if (nct <= 0) { if (has_so) so.flush(); return; }
-#define WALK_CASE(n_) do { if (has_so) walk_run<n_, BWD, true>(Xs, px, W, K, N, bias, act, E, Ys, py, G, row0, M, ct0, nct, so, stamp); \
-                           else walk_run<n_, BWD, false>(Xs, px, W, K, N, bias, act, E, Ys, py, G, row0, M, ct0, nct, so, stamp); } while (0)
+#define WALK_CASE(n_) do { if (has_so) walk_run<n_, BWD, true, EXT>(Xs, px, W, ldw, K, N, bias, act, E, lde, xcols, Ys, py, G, row0, M, ct0, nct, so, stamp); \
+                           else walk_run<n_, BWD, false, EXT>(Xs, px, W, ldw, K, N, bias, act, E, lde, xcols, Ys, py, G, row0, M, ct0, nct, so, stamp); } while (0)
     switch (nct) {
         case 1: WALK_CASE(1); break;
         case 2: WALK_CASE(2); break;
@@ -404,12 +486,20 @@ __device__ __forceinline__ void walk_dispatch(const float* Xs, int px, const flo
 // observation buffers without a launch or a copy of its own.  The statistics travel behind WalkArgs: the plain kernels keep their argument block.
 struct WalkNorm { const float* mean[2]; const float* inv[2]; float clip[2]; };
 struct WalkArgsNorm : WalkArgs { WalkNorm nm; };
-template <bool NORM> struct walk_args { typedef WalkArgs type; };
-template <> struct walk_args<true> { typedef WalkArgsNorm type; };
+// The extended walk (include/trifinger_ppo_net.h; EXT): activation codes in WalkNet.act, and kin[ni][l] = the width of layer l's INPUT OPERAND - dim[l], or
+// dim[l] + dim[0] where a d2rl network concatenates its input behind the hidden output (1 <= l <= nl - 2).  That width is the K of the forward product, the
+// leading dimension of W[l] and the row stride of the saved output yin[l - 1]; the backward chain reads the first dim[l] columns of each.  Like the statistics
+// it travels behind WalkArgs: the plain kernels keep their argument block and their code.
+struct WalkArgsExt : WalkArgsNorm { int kin[2][WALK_MAXL]; };
+template <bool NORM, bool EXT> struct walk_args { typedef WalkArgs type; };
+template <> struct walk_args<true, false> { typedef WalkArgsNorm type; };
+template <bool NORM> struct walk_args<NORM, true> { typedef WalkArgsExt type; };
 
-// two workgroups of four wavefronts per CU: two wavefronts per SIMD, 256 registers each.  NORM (forward only): the staged input passes through a.nm
-template <bool BWD, bool NORM = false>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) k_mlp_walk(const typename walk_args<NORM>::type a) {
+// two workgroups of four wavefronts per CU: two wavefronts per SIMD, 256 registers each.  NORM (forward only): the staged input passes through a.nm.
+// EXT forward is always NORM (a network without statistics has mean NULL); with the wide rows of a d2rl network its LDS may exceed half a CU's: then one
+// workgroup per CU runs, with the same code.
+template <bool BWD, bool NORM = false, bool EXT = false>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) k_mlp_walk(const typename walk_args<NORM, EXT>::type a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int ni = (int)blockIdx.x / a.blocks_per_net;
     if (ni >= a.n_nets) return;
@@ -462,10 +552,31 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
         // first layer's input gradient is not formed
         const int l = BWD ? nl - 1 - s : s;
         if (BWD && l == 0) break;
-        const int K = BWD ? net.dim[l + 1] : net.dim[l], N = BWD ? net.dim[l] : net.dim[l + 1];
-        const int px = pitch_of(K), py = pitch_of(N);
+        int K = BWD ? net.dim[l + 1] : net.dim[l];
+        const int N = BWD ? net.dim[l] : net.dim[l + 1];
+        int px = pitch_of(K), py = pitch_of(N), ldw = BWD ? N : K, lde = N;
         const bool lastp = BWD ? (l == 1) : (l == nl - 1);
         float* Ys = lastp ? nullptr : nxt;
+        bool xcols = false;
+        if constexpr (EXT) {
+            const int kin = a.kin[ni][l];
+            ldw = kin;
+            if (BWD) {
+                lde = kin;                                          // yin[l - 1] = [h_l | x] where the forward kept the operand of layer l
+            } else {
+                K = kin; px = pitch_of(K);
+                const int kn = lastp ? N : a.kin[ni][l + 1], D0 = kn - N;
+                if (D0 > 0) {
+                    // d2rl: the next operand is [h | x].  The input columns are copied from this step's operand (x itself, or [h' | x]), the epilogue below
+                    // writes the N columns in front of them; nxt was last read as the operand of the step before (a barrier ago)
+                    xcols = true;
+                    py = pitch_of(kn);
+                    const int xoff = K - D0, pad = py - 4 - kn;
+                    for (int e = threadIdx.x; e < WALK_ROWS * D0; e += 256) { const int r = e / D0, c = e - r * D0; nxt[r * py + N + c] = cur[r * px + xoff + c]; }
+                    for (int e = threadIdx.x; e < WALK_ROWS * pad; e += 256) { const int r = e / pad; nxt[r * py + kn + (e - r * pad)] = 0.0f; }
+                }
+            }
+        }
         StreamOut so;
         bool has_so = false;
         if (pend) {
@@ -486,9 +597,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
         }
         const float* E = BWD ? (net.act[l - 1] ? net.yin[l - 1] : nullptr) : nullptr;
         float* G = BWD ? net.y[l - 1] : net.y[l];
-        const int act = BWD ? 0 : net.act[l];
+        const int act = BWD ? (EXT ? net.act[l - 1] : 0) : net.act[l];
         const float* bias = BWD ? nullptr : net.b[l];
-        walk_dispatch<BWD>(cur, px, net.W[l], K, N, bias, act, E, Ys, py, G, row0, a.M, so, has_so, s);
+        walk_dispatch<BWD, EXT>(cur, px, net.W[l], ldw, K, N, bias, act, E, lde, xcols, Ys, py, G, row0, a.M, so, has_so, s);
         WSTAMP(3 + 3 * s);
         if (!lastp) __syncthreads();
         WSTAMP(4 + 3 * s);
@@ -497,19 +608,22 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
     }
 }
 
-static int walk_prepare(WalkArgs& a, int M, bool bwd, size_t* lds_bytes) {
+// kin (the extended walk): the operand widths of the forward walk, see WalkArgsExt; limit: the LDS a workgroup may take
+static int walk_prepare(WalkArgs& a, int M, bool bwd, size_t* lds_bytes, const int (*kin)[WALK_MAXL] = nullptr, size_t limit = 80 * 1024, bool shapes_only = false) {
     // the two LDS buffers are used alternately: the input and every second product in P, the others in Q
     int p = 0, q = 0;
     for (int ni = 0; ni < a.n_nets; ++ni) {
         const WalkNet& n = a.net[ni];
         if (n.nl < 1 || n.nl > WALK_MAXL) return -1;
         for (int l = 0; l <= n.nl; ++l) if (n.dim[l] <= 0) return -1;
-        for (int l = 0; l < n.nl; ++l) if (!n.W[l] && !(bwd && l == 0)) return -1;
-        if (!n.x) return -1;
+        if (!shapes_only) {
+            for (int l = 0; l < n.nl; ++l) if (!n.W[l] && !(bwd && l == 0)) return -1;
+            if (!n.x) return -1;
+        }
         for (int l = 1; l <= n.nl; ++l) if (n.dim[l] > 416) return -4;                 // 26 column tiles: 7 + 7 + 6 + 6 accumulator columns
         if (n.dim[0] > 416) return -4;
         int seq[WALK_MAXL + 1], cnt = 0;
-        if (!bwd) { for (int l = 0; l < n.nl; ++l) seq[cnt++] = n.dim[l]; }            // operands that live in LDS: input and all but the last output
+        if (!bwd) { for (int l = 0; l < n.nl; ++l) seq[cnt++] = kin ? kin[ni][l] : n.dim[l]; }   // operands that live in LDS: input and all but the last output
         else { for (int l = n.nl; l >= 2; --l) seq[cnt++] = n.dim[l]; if (n.nl == 1) seq[cnt++] = n.dim[1]; }
         for (int i = 0; i < cnt; ++i) {
             const int fl = WALK_ROWS * ((((seq[i] + 15) & ~15)) + 4);
@@ -520,7 +634,7 @@ static int walk_prepare(WalkArgs& a, int M, bool bwd, size_t* lds_bytes) {
     a.M = M;
     a.blocks_per_net = (M + WALK_ROWS - 1) / WALK_ROWS;
     *lds_bytes = (size_t)(p + q) * sizeof(float);
-    return *lds_bytes <= 80 * 1024 ? 0 : -4;                       // half a CU's LDS: two workgroups per CU
+    return *lds_bytes <= limit ? 0 : -4;                           // half a CU's LDS: two workgroups per CU (the forward walk of a d2rl network: up to all of it)
 }
 
 extern "C" {
@@ -574,6 +688,61 @@ int tfp_mlp_forward_norm(const TfpMlp* nets, const TfpNorm* norm, int32_t n_nets
 // the input-gradient chain of the same stacks in ONE launch: x = gradient of the network output, yin[l] = saved output of layer l, y[l] = dZ of layer l
 // (l < n_layers - 1; the dZ of the last layer is x itself)
 int tfp_mlp_backward(const TfpMlp* nets, int32_t n_nets, int32_t M, void* stream) { return walk_launch(nets, n_nets, M, true, stream); }
+
+// ---- the extended walk (include/trifinger_ppo_net.h): activation codes 0 .. 6, d2rl, optional statistics ----
+static int net_setup(const TfpNet* nets, int32_t n_nets, bool bwd, bool shapes_only, WalkArgsExt& a, bool* any_d2rl) {
+    if (!nets || n_nets < 1 || n_nets > 2) return -1;
+    memset(&a, 0, sizeof(a));
+    a.n_nets = n_nets;
+    *any_d2rl = false;
+    for (int ni = 0; ni < n_nets; ++ni) {
+        WalkNet& d = a.net[ni]; const TfpMlp& s = nets[ni].mlp;
+        if (s.n_layers < 1 || s.n_layers > WALK_MAXL) return -1;
+        d.x = s.x; d.nl = s.n_layers;
+        for (int l = 0; l < WALK_MAXL; ++l) { d.W[l] = s.W[l]; d.b[l] = s.b[l]; d.yin[l] = s.yin[l]; d.y[l] = s.y[l]; d.act[l] = s.act[l]; }
+        for (int l = 0; l <= WALK_MAXL; ++l) d.dim[l] = s.dim[l];
+        for (int l = 0; l < s.n_layers; ++l) {
+            if (s.dim[l] <= 0) return -1;
+            if (s.act[l] < TFP_ACT_NONE || s.act[l] > TFP_ACT_SOFTPLUS) return -1;
+            const bool wide = nets[ni].d2rl && l >= 1 && l <= s.n_layers - 2;
+            a.kin[ni][l] = s.dim[l] + (wide ? s.dim[0] : 0);
+            if (wide) *any_d2rl = true;
+        }
+        if (shapes_only) continue;
+        if (!bwd && !s.y[s.n_layers - 1]) return -1;
+        if (bwd) for (int l = 0; l + 1 < s.n_layers; ++l) { if (!s.y[l]) return -1; if (s.act[l] && !s.yin[l]) return -1; }
+        if (nets[ni].mean) {
+            if (bwd || !nets[ni].inv_std || !(nets[ni].clip > 0.0f)) return -1;
+            a.nm.mean[ni] = nets[ni].mean; a.nm.inv[ni] = nets[ni].inv_std; a.nm.clip[ni] = nets[ni].clip;
+        }
+    }
+    return 0;
+}
+static int net_launch(const TfpNet* nets, int32_t n_nets, int32_t M, bool bwd, void* stream, bool shapes_only) {
+    if (M <= 0) return -1;
+    WalkArgsExt a; bool d2rl = false;
+    int rc = net_setup(nets, n_nets, bwd, shapes_only, a, &d2rl);
+    if (rc) return rc;
+    // the wide operand rows of a d2rl network exist in the forward walk only (the backward chain runs over the hidden part): that call alone may take a whole CU
+    const size_t limit = (!bwd && d2rl) ? 160 * 1024 : 80 * 1024;
+    size_t lds = 0;
+    rc = walk_prepare(a, M, bwd, &lds, a.kin, limit, shapes_only);
+    if (rc || shapes_only) return rc;
+    static bool attr_set[2] = {false, false};
+    const void* f = bwd ? (const void*)k_mlp_walk<true, false, true> : (const void*)k_mlp_walk<false, true, true>;
+    if (!attr_set[bwd ? 1 : 0]) {
+        if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bwd ? 80 * 1024 : 160 * 1024) != hipSuccess) return -2;
+        attr_set[bwd ? 1 : 0] = true;
+    }
+    const dim3 grid(a.blocks_per_net * n_nets), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    if (bwd) hipLaunchKernelGGL((k_mlp_walk<true, false, true>), grid, block, lds, s, a);
+    else hipLaunchKernelGGL((k_mlp_walk<false, true, true>), grid, block, lds, s, a);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+int tfp_net_forward(const TfpNet* nets, int32_t n_nets, int32_t M, void* stream) { return net_launch(nets, n_nets, M, false, stream, false); }
+int tfp_net_backward(const TfpNet* nets, int32_t n_nets, int32_t M, void* stream) { return net_launch(nets, n_nets, M, true, stream, false); }
+int tfp_net_fits(const TfpNet* nets, int32_t n_nets, int32_t backward) { return net_launch(nets, n_nets, 1, backward != 0, nullptr, true); }
 
 #ifdef WALK_TIMING
 int tfp_walk_debug_read(unsigned long long* out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_walk_t), sizeof(unsigned long long) * 128) == hipSuccess ? 0 : -3; }

@@ -1,7 +1,7 @@
 """Minimal asymmetric-actor-critic PPO for the TriFinger env (BASELINE config 5 when `rl_games` is absent).
 
 Follows the agent configuration the reference ships for RL-Games (resources/config/rlg/asymm.yaml): continuous
-A2C/PPO, actor MLP [400, 200, 100] ELU on `obs`, central value MLP [400, 200, 100] ELU on `states`, state-independent
+A2C/PPO, actor MLP [400, 200, 100] ELU on `obs`, central value MLP [400, 200, 100] ELU on `states` (the defaults of `activation` / `d2rl`, below), state-independent
 log-std (`fixed_sigma`), horizon `steps_num` 32, 4 mini-epochs, minibatch = num_envs, gamma 0.99, GAE tau 0.95,
 actor lr 3e-4 adaptive on a KL threshold of 0.008, e_clip 0.2, reward scale 0.01, grad-norm 1.0, bounds loss 1e-4,
 normalised advantages; the central value network has its OWN optimiser state (asymm.yaml:70-90): lr 5e-4 constant, its
@@ -24,6 +24,19 @@ ret_n = clamp((ret - mean_f) * inv_std_f, -5, 5) and clips around clamp(y_old, -
 `update()` (the same single all_gather) with the moments of the epoch's de-normalised returns buf["ret"], T n samples.  Deliberately NOT RL-Games here:
 it merges values as well as returns, and before it normalises; its de-normalisation multiplies by sqrt(var + eps) where this divides by the published
 inv_std_f (no third published quantity).  `act()` / `play()` neither read nor move the record; `ActorCritic.value_denorm` gives a value in reward units.
+The shape of the networks follows the tree as well, per network (`params.network.mlp` for the actor, `central_value_config.network.mlp` for the central value
+network; without one the critic takes the actor's keys).  RL-Games is not installed here, so the definitions in this module ARE the specification; they follow
+RL-Games' network builder and D2RLNet as far as can be stated without it.  `activation`: relu, tanh, sigmoid, elu, selu, swish, gelu, softplus or None (`ACTIVATIONS`),
+behind every hidden layer and never behind the output layer; anything else raises a ValueError naming the key.  `d2rl: True` (`D2RLMLP`): h_1 = act(x W_1^T + b_1),
+h_l = act([h_{l-1} | x] W_l^T + b_l) with W_l [u_l, u_{l-1} + D0] (torch.cat([h, x], 1): the hidden output first), the output layer reads h_last alone, the
+concatenated x is the normalised one, the initialisers see the real fan-in; `d2rl: False` keeps FusedMLP and the state-dict keys checkpoints have.  On a GPU all of
+it runs on the network walk (one launch per direction for both networks: include/trifinger_ppo_net.h) - except swish and gelu, whose derivative cannot be formed from
+the layer output the backward walk keeps, and shapes the walk declines: such a trainer prints ONE message at construction and runs its whole update on plain torch,
+as with `fused_kernels=False` (the per-layer kernels are ELU only and are never applied to a network that asked for something else).
+`truncate_grads: False` / `central_value_config.truncate_grads: False`: no gradient-norm truncation for that optimiser.  `lr_schedule`: adaptive (the KL rule),
+identity / None (the actor's rate stays; the KL statistic is still logged), linear (1e-6 + (learning_rate - 1e-6) * max(0, max_epochs - epoch) / max_epochs, set once
+per epoch); the central value network's rate is constant throughout.  Not built and refused by name (ValueError): `fixed_sigma: False`, `mu_activation` /
+`sigma_activation` other than None.
 
 This is host-side training glue, NOT part of the measured hot path.  On a GPU the minibatch step runs on the hand-written kernels of
 csrc/ppo_kernels.hip (leibnizgym_amd/ppo_kernels.py): one gather launch, the Linear / ELU layers on fp32 MFMA, the objective with all
@@ -79,6 +92,13 @@ class PPOConfig:
     clip_value: bool = False          # params.config.clip_value: the critic's value loss clipped around the rollout's value (no central value network)
     clip_value_central: bool = False  # central_value_config.clip_value: the same for the central value network (when there is one)
     normalize_value: bool = False     # params.config.normalize_value: running mean / std of the returns; the value network works in normalised units
+    activation: str = "elu"           # params.network.mlp.activation: behind every hidden layer of the actor (ACTIVATIONS)
+    value_activation: str = ""        # central_value_config.network.mlp.activation; "" = the actor's
+    d2rl: bool = False                # params.network.mlp.d2rl: the input concatenated behind every hidden output but the last (D2RLMLP)
+    value_d2rl: bool = False          # central_value_config.network.mlp.d2rl
+    truncate_grads: bool = True       # params.config.truncate_grads: False = no gradient-norm truncation for the actor's optimiser
+    value_truncate_grads: bool = True     # central_value_config.truncate_grads: the same for the central value network's
+    lr_schedule: str = "adaptive"     # params.config.lr_schedule: adaptive | identity / None (constant) | linear (to 1e-6 at max_epochs, per epoch)
 
     @classmethod
     def from_rlg(cls, rlg: dict, num_envs: int = None, **overrides):
@@ -88,6 +108,14 @@ class PPOConfig:
         p = rlg["params"]
         c, net = p["config"], p["network"]
         cv = c.get("central_value_config", {})
+        # keys that are not built are refused by name, never ignored
+        cont = net.get("space", {}).get("continuous", {})
+        if not bool(cont.get("fixed_sigma", True)):
+            raise ValueError("params.network.space.continuous.fixed_sigma: False (a state-dependent sigma head) is not built; the in-repo PPO keeps a "
+                             "state-independent log-std")
+        for key in ("mu_activation", "sigma_activation"):
+            if cont.get(key, "None") not in (None, "None"):
+                raise ValueError(f"params.network.space.continuous.{key}: {cont[key]!r} is not built; only None")
         kw = dict(units=list(net["mlp"]["units"]), horizon=int(c["steps_num"]), mini_epochs=int(c["mini_epochs"]),
                   gamma=float(c["gamma"]), tau=float(c["tau"]), lr=float(c["learning_rate"]),
                   kl_threshold=float(c["lr_threshold"]), e_clip=float(c["e_clip"]), critic_coef=float(c["critic_coef"]),
@@ -99,8 +127,16 @@ class PPOConfig:
                   save_frequency=int(c.get("save_frequency", 100)), save_best_after=int(c.get("save_best_after", 500)),
                   max_epochs=int(c.get("max_epochs", 100000)), name=str(c.get("name", "trifinger")),
                   seed=int(rlg.get("seed", 7)), normalize_input=bool(c.get("normalize_input", False)),
-                  clip_value=bool(c.get("clip_value", False)), normalize_value=bool(c.get("normalize_value", False)))
+                  clip_value=bool(c.get("clip_value", False)), normalize_value=bool(c.get("normalize_value", False)),
+                  activation=activation_name(net["mlp"].get("activation", "elu"), "params.network.mlp.activation"),
+                  d2rl=bool(net["mlp"].get("d2rl", False)), truncate_grads=bool(c.get("truncate_grads", True)),
+                  lr_schedule=lr_schedule_name(c.get("lr_schedule", "adaptive")))
+        # without a central value network the critic takes the actor's keys
+        kw.update(value_activation=kw["activation"], value_d2rl=kw["d2rl"], value_truncate_grads=kw["truncate_grads"])
         if cv:
+            cmlp = cv["network"]["mlp"]
+            kw.update(value_activation=activation_name(cmlp.get("activation", "elu"), "central_value_config.network.mlp.activation"),
+                      value_d2rl=bool(cmlp.get("d2rl", False)), value_truncate_grads=bool(cv.get("truncate_grads", True)))
             init = cv["network"]["mlp"]["initializer"]
             kw.update(lr_value=float(cv["lr"]), value_mini_epochs=int(cv["mini_epochs"]),
                       value_grad_norm=float(cv["grad_norm"]), value_init=str(init["name"]),
@@ -144,20 +180,50 @@ class SplitKLinear(nn.Linear):
         return super().forward(x)
 
 
+# `network.mlp.activation`: name -> (module, activation code of include/trifinger_ppo_net.h; -1: no kernel - swish and gelu are not monotone, their derivative
+# cannot be formed from the saved output, which is all the backward walk reads).  RL-Games is not installed here: this table and D2RLMLP below ARE the
+# specification, following RL-Games' network builder and D2RLNet as far as can be stated without it.
+ACTIVATIONS = {"relu": (nn.ReLU, 2), "tanh": (nn.Tanh, 3), "sigmoid": (nn.Sigmoid, 4), "elu": (nn.ELU, 1), "selu": (nn.SELU, 5), "swish": (nn.SiLU, -1),
+               "gelu": (nn.GELU, -1), "softplus": (nn.Softplus, 6), "None": (nn.Identity, 0)}
+_ACT_CODE_OF = {mod: code for mod, code in ACTIVATIONS.values()}
+
+
+def activation_name(name, key="network.mlp.activation"):
+    """the canonical name of an activation key's value (None -> "None"); anything unknown raises a ValueError that names the key"""
+    name = "None" if name is None else str(name)
+    if name not in ACTIVATIONS:
+        raise ValueError(f"{key}: unknown activation {name!r}; accepted: {', '.join(ACTIVATIONS)}")
+    return name
+
+
+def lr_schedule_name(name, key="params.config.lr_schedule"):
+    name = "identity" if name in (None, "None", "identity") else str(name)
+    if name not in ("adaptive", "identity", "linear"):
+        raise ValueError(f"{key}: unknown schedule {name!r}; accepted: adaptive, identity, None, linear")
+    return name
+
+
 class FusedMLP(nn.Sequential):
-    """Linear / ELU stack (same modules and state-dict keys as the nn.Sequential it is).  With `mfma` set (the trainer does it on a
+    """Linear / activation stack (same modules and state-dict keys as the nn.Sequential it is).  With `mfma` set (the trainer does it on a
     GPU when `fused_kernels` is on) every layer runs on the hand-written fp32 MFMA kernels of csrc/ppo_kernels.hip: bias and ELU
     fused into the forward product, the ELU derivative formed in the operand loads of the two backward products, the bias gradient
-    as an extra column of the weight-gradient product."""
+    as an extra column of the weight-gradient product (those per-layer kernels know ELU only: any other activation runs as its torch module behind
+    a plain product)."""
     mfma = False
+    d2rl = False
 
     def layer_list(self):
-        """[(weight, bias, act, grad_out)] of the Linear layers, for ppo_kernels.mlp_forward / mlp_backward"""
-        mods, out = list(self), []
+        """[(weight, bias, act, grad_out)] of the Linear layers (a ppo_kernels.LayerList: it carries `d2rl`), act = the activation code behind the layer"""
+        from .ppo_kernels import LayerList
+        mods, out = list(self), LayerList()
+        out.d2rl = self.d2rl
+        other = False
         for i, m in enumerate(mods):
             if isinstance(m, nn.Linear):
-                act = 1 if (i + 1 < len(mods) and isinstance(mods[i + 1], nn.ELU)) else 0
+                act = _ACT_CODE_OF.get(type(mods[i + 1]), 0) if i + 1 < len(mods) else 0
+                other = other or act > 1 or act < 0
                 out.append((m.weight, m.bias, act, getattr(m, "_grad_out", None)))
+        out.ext = other or (self.d2rl and len(out) >= 3)            # what ppo_kernels.needs_net_walk() would find
         return out
 
     def forward(self, x):
@@ -178,13 +244,30 @@ class FusedMLP(nn.Sequential):
         return x
 
 
-def mlp(inp, units, out):
+class D2RLMLP(FusedMLP):
+    """`network.mlp.d2rl: True`: h_1 = act(x W_1^T + b_1), h_l = act([h_{l-1} | x] W_l^T + b_l) for l >= 2 (W_l: [u_l, u_{l-1} + D0], the hidden output first
+    and x behind it: torch.cat([h, x], dim=1)), the output layer reads h_last alone.  The same Sequential layout and state-dict keys as FusedMLP with wider
+    hidden weights; the forward is plain torch (the trainer's fused path runs the network on the walk, ppo_kernels.mlp_forward_pair)."""
+    d2rl = True
+
+    def forward(self, x):
+        lin = [m for m in self if isinstance(m, nn.Linear)]
+        acts = [m for m in self if not isinstance(m, nn.Linear)]
+        h = acts[0](lin[0](x))
+        for l in range(1, len(lin) - 1):
+            h = acts[l](lin[l](torch.cat([h, x], dim=-1)))
+        return lin[-1](h)
+
+
+def mlp(inp, units, out, activation="elu", d2rl=False):
+    """the stack `network.mlp` describes: the activation behind every hidden layer, never behind the output layer; d2rl: D2RLMLP"""
+    act = ACTIVATIONS[activation_name(activation)][0]
     layers, last = [], inp
-    for u in units:
-        layers += [SplitKLinear(last, u), nn.ELU()]
+    for i, u in enumerate(units):
+        layers += [SplitKLinear(last + (inp if (d2rl and i > 0) else 0), u), act()]
         last = u
     layers.append(SplitKLinear(last, out))
-    return FusedMLP(*layers)
+    return (D2RLMLP if d2rl else FusedMLP)(*layers)
 
 
 def variance_scaling_(w: torch.Tensor, scale: float) -> torch.Tensor:
@@ -292,10 +375,12 @@ class ActorCritic(nn.Module):
 
     def __init__(self, obs_dim, state_dim, act_dim, units, cfg: "PPOConfig" = None):
         super().__init__()
-        self.actor = mlp(obs_dim, units, act_dim)
-        self.critic = mlp(state_dim if state_dim > 0 else obs_dim, units, 1)
-        self.log_std = nn.Parameter(torch.zeros(act_dim))          # sigma_init const 0, fixed_sigma
         self.central = state_dim > 0
+        a_act, a_d2rl = (cfg.activation, cfg.d2rl) if cfg is not None else ("elu", False)
+        c_act, c_d2rl = ((cfg.value_activation or a_act, cfg.value_d2rl) if self.central else (a_act, a_d2rl)) if cfg is not None else ("elu", False)
+        self.actor = mlp(obs_dim, units, act_dim, a_act, a_d2rl)
+        self.critic = mlp(state_dim if state_dim > 0 else obs_dim, units, 1, c_act, c_d2rl)
+        self.log_std = nn.Parameter(torch.zeros(act_dim))          # sigma_init const 0, fixed_sigma
         if cfg is not None:
             self.init_like_rl_games(cfg)
 
@@ -367,6 +452,7 @@ class PPOTrainer:
         if state_dim > 0 and c.value_mini_epochs not in (0, c.mini_epochs):
             raise ValueError("central_value_config.mini_epochs must equal mini_epochs: actor and central value network "
                              "are updated in one fused pass over the same minibatches")
+        self.lr_schedule = lr_schedule_name(c.lr_schedule)
         torch.manual_seed(c.seed)              # identical initial weights on every rank (and a broadcast below)
         self.net = ActorCritic(obs_dim, state_dim, act_dim, c.units, c).to(self.device)
         # fused multi-tensor Adam on the GPU: the update is launch-bound (tiny MLPs), one kernel instead of ~60.
@@ -379,10 +465,18 @@ class PPOTrainer:
         kw = {"fused": True} if fused else {}
         self.opt = torch.optim.Adam(groups, eps=1e-8, **kw)
         self.lr = c.lr
-        self.fused_loss = fused and c.fused_kernels        # hand-written objective kernel (GPU only)
-        self.net.actor.mfma = self.net.critic.mfma = bool(fused and c.fused_kernels)   # ... and the MFMA linear layers
-        # normalize_input / central_value_config.normalize_input: one record per normalised input, frozen during an epoch (module docstring)
+        # The hand-written kernels serve a network the walk can run (module docstring): decided ONCE, here, with one message - otherwise the whole update
+        # runs on plain torch, as with fused_kernels=False; no ELU kernel is ever applied to a network that asked for something else
         fk = bool(fused and c.fused_kernels)
+        self.torch_path_reason = self._fused_refusal() if fk else None
+        if self.torch_path_reason:
+            print(f"[ppo] {self.torch_path_reason}: this trainer runs on the plain torch path (as with fused_kernels=False)", flush=True)
+            fk = False
+        self.fused_loss = fk                               # hand-written objective kernel (GPU only)
+        self.net.actor.mfma = self.net.critic.mfma = fk    # ... and the MFMA linear layers
+        # which optimiser truncates its gradient norm (`truncate_grads` / central_value_config.truncate_grads; one optimiser without a central value network)
+        self.trunc = (bool(c.truncate_grads), bool(c.value_truncate_grads if self.net.central else c.truncate_grads))
+        # normalize_input / central_value_config.normalize_input: one record per normalised input, frozen during an epoch (module docstring)
         if c.normalize_input:
             self.net.obs_norm = InputNorm(obs_dim, self.device, fused=fk)
         if c.normalize_input_value and self.net.central:
@@ -410,12 +504,16 @@ class PPOTrainer:
             rank = self.dist.get_rank(group)
         # GPU + fused kernels: truncation + Adam of both groups as two hand-written launches over one flat buffer
         self.flat_opt = None
-        if fused and c.fused_kernels:
+        if fk:
             from .ppo_kernels import FlatClipAdam
+            # no truncation = an infinite max_norm: the kernel's coefficient fminf(max_norm / (norm + 1e-6), 1) is then exactly 1 (inf / finite = inf; an
+            # overflowed norm gives inf / inf = NaN, and fminf returns its other operand), and g * 1.0f is g
+            inf = float("inf")
+            gn0 = c.grad_norm if self.trunc[0] else inf
             if self.net.central:
-                self.flat_opt = FlatClipAdam(self.net.actor_parameters(), self.net.critic_parameters(), c.lr, lr_v, c.grad_norm, c.value_grad_norm)
+                self.flat_opt = FlatClipAdam(self.net.actor_parameters(), self.net.critic_parameters(), c.lr, lr_v, gn0, c.value_grad_norm if self.trunc[1] else inf)
             else:
-                self.flat_opt = FlatClipAdam(list(self.net.parameters()), [], c.lr, c.lr, c.grad_norm, c.grad_norm)
+                self.flat_opt = FlatClipAdam(list(self.net.parameters()), [], c.lr, c.lr, gn0, gn0)
             for net in (self.net.actor, self.net.critic):      # the MFMA layers write dW / db straight into the flat gradient buffer
                 for m in net:
                     if isinstance(m, nn.Linear):
@@ -428,6 +526,34 @@ class PPOTrainer:
         self.epoch = 0
         self.last_info = {}
         self.best_reward = -float("inf")
+
+    def _fused_refusal(self):
+        """None, or why this network cannot run on the hand-written kernels: an activation without a kernel (swish, gelu), or a network only the extended
+        walk runs (another activation than ELU, d2rl) whose shapes the walk declines - the per-layer fallback is ELU only"""
+        from . import ppo_kernels as pk
+        la, lc = self.net.actor.layer_list(), self.net.critic.layer_list()
+        if any(l[2] == pk.ACT_NO_KERNEL for l in la + lc):
+            return ("network.mlp.activation: swish / gelu have no kernel (not monotone: the derivative cannot be formed from the layer output, which is all the "
+                    "backward walk keeps)")
+        if (pk.needs_net_walk(la) or pk.needs_net_walk(lc)) and not (pk.net_fits([la, lc], False) and pk.net_fits([la, lc], True)):
+            return ("network.mlp.activation / d2rl: the network walk declines these shapes (a layer wider than 416 or rows beyond the LDS of a CU) and the "
+                    "per-layer kernels know ELU only")
+        return None
+
+    def _set_actor_lr(self, lr):
+        """the actor's learning rate (the only one without a central value network) into whichever optimiser runs"""
+        self.lr = float(lr)
+        if self.flat_opt is not None:
+            self.flat_opt.set_lr(0, self.lr)
+            if not self.net.central:
+                self.flat_opt.set_lr(1, self.lr)
+        for g in (self.opt.param_groups[:1] if self.net.central else self.opt.param_groups):
+            g["lr"] = self.lr
+
+    def scheduled_lr(self, epoch):
+        """`lr_schedule: linear`: 1e-6 + (learning_rate - 1e-6) * max(0, max_epochs - epoch) / max_epochs"""
+        c = self.cfg
+        return 1e-6 + (c.lr - 1e-6) * max(0, c.max_epochs - epoch) / c.max_epochs
 
     # ---- checkpoints (what RL-Games' save / restore / `args.checkpoint` give the reference launcher) ----
     def _optimizer_state(self):
@@ -763,9 +889,11 @@ class PPOTrainer:
             self.flat_opt.step(gathered)
             return
         if self.net.central:                   # truncate_grads of each optimiser on its own network
-            nn.utils.clip_grad_norm_(self.net.actor_parameters(), self.cfg.grad_norm, foreach=True)
-            nn.utils.clip_grad_norm_(self.net.critic_parameters(), self.cfg.value_grad_norm, foreach=True)
-        else:
+            if self.trunc[0]:
+                nn.utils.clip_grad_norm_(self.net.actor_parameters(), self.cfg.grad_norm, foreach=True)
+            if self.trunc[1]:
+                nn.utils.clip_grad_norm_(self.net.critic_parameters(), self.cfg.value_grad_norm, foreach=True)
+        elif self.trunc[0]:
             nn.utils.clip_grad_norm_(self.net.parameters(), self.cfg.grad_norm, foreach=True)
         self.opt.step()
 
@@ -809,6 +937,8 @@ class PPOTrainer:
             v.zero_()
         stats = {"kl": 0.0}
         count = 0
+        if self.lr_schedule == "linear":           # once per epoch
+            self._set_actor_lr(self.scheduled_lr(self.epoch))
         for _ in range(c.mini_epochs):
             perm = torch.randperm(total, device=dev)
             acc["kl"].zero_()
@@ -829,16 +959,13 @@ class PPOTrainer:
                 kl /= self.dist.get_world_size(self.group)
             kl = float(kl)                     # the one host sync per mini-epoch (adaptive learning rate)
             stats["kl"] = kl
-            if kl > 2.0 * c.kl_threshold:      # rl_games AdaptiveScheduler
-                self.lr = max(self.lr / 1.5, 1e-6)
-            elif kl < 0.5 * c.kl_threshold:
-                self.lr = min(self.lr * 1.5, 1e-2)
-            if self.flat_opt is not None:
-                self.flat_opt.set_lr(0, self.lr)
-                if not self.net.central:
-                    self.flat_opt.set_lr(1, self.lr)
-            for g in (self.opt.param_groups[:1] if self.net.central else self.opt.param_groups):
-                g["lr"] = self.lr
+            if self.lr_schedule == "adaptive":      # rl_games AdaptiveScheduler; identity / linear: the statistic is logged, the rate is not moved here
+                lr = self.lr
+                if kl > 2.0 * c.kl_threshold:
+                    lr = max(lr / 1.5, 1e-6)
+                elif kl < 0.5 * c.kl_threshold:
+                    lr = min(lr * 1.5, 1e-2)
+                self._set_actor_lr(lr)
         if vn is not None:
             self._update_value_norm(src, buf)
         else:

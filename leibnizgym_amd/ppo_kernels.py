@@ -84,6 +84,12 @@ def load():
         lib.tfp_ppo_loss_vclip.argtypes = [C.c_void_p] * 9 + [C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float] + [C.c_void_p] * 6
         lib.tfp_gae_vnorm.restype = C.c_int
         lib.tfp_gae_vnorm.argtypes = [C.c_void_p] * 5 + [C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32] + [C.c_void_p] * 5
+        # the network-shape keys (include/trifinger_ppo_net.h: activation codes, d2rl), bound by symbol like the rest: a library built before them fails HERE
+        for name in ("tfp_net_forward", "tfp_net_backward"):
+            getattr(lib, name).restype = C.c_int
+            getattr(lib, name).argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+        lib.tfp_net_fits.restype = C.c_int
+        lib.tfp_net_fits.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
         _LIB = lib
     return _LIB
 
@@ -237,7 +243,9 @@ class FlatClipAdam:
 
 # ---- fp32 MFMA GEMMs of the two MLPs (csrc/ppo_kernels.hip: k_gemm) --------------------------------------------------------------
 def linear_fwd(x, w, b, act):
-    """act(x @ w.T + b) for contiguous float32 x [M, K], w [N, K], b [N]; act: 0 none, 1 ELU"""
+    """act(x @ w.T + b) for contiguous float32 x [M, K], w [N, K], b [N]; act: 0 none, 1 ELU (the per-layer launches know no other activation)"""
+    if int(act) not in (0, 1):
+        raise ValueError(f"the per-layer kernels apply ELU or nothing, not activation code {act}: such a network runs on the network walk or on torch")
     M, K = x.shape
     N = w.shape[0]
     y = torch.empty(M, N, device=x.device, dtype=torch.float32)
@@ -551,6 +559,8 @@ def mlp_backward(x, ys, gy, layers):
     # gy is the gradient of layer k's OUTPUT at the top of the walk and the dZ of layer k - already times elu'(ys[k]) - below it: every input-gradient
     # product leaves multiplied by the activation derivative of the layer it is the gradient of (tfp_gemm_nn_dz), so the two products that consume it
     # stage plain operands.  Same bits as multiplying in their operand loads (one fp32 product either way).
+    if needs_net_walk(layers):
+        raise ValueError("the per-layer kernels form ELU's derivative or none: a network with another activation or with d2rl runs on the network walk or on torch")
     is_dz = False
     for k in range(len(layers) - 1, -1, -1):
         w, _, act, grad_out = layers[k]
@@ -570,6 +580,76 @@ class TfpMlp(C.Structure):
     """include/trifinger_ppo.h: TfpMlp"""
     _fields_ = [("x", C.c_void_p), ("W", C.c_void_p * WALK_MAXL), ("b", C.c_void_p * WALK_MAXL), ("yin", C.c_void_p * WALK_MAXL),
                 ("y", C.c_void_p * WALK_MAXL), ("dim", C.c_int32 * (WALK_MAXL + 1)), ("act", C.c_int32 * WALK_MAXL), ("n_layers", C.c_int32)]
+
+
+# activation codes of include/trifinger_ppo_net.h (0 and 1 are the ones every kernel knows); swish and gelu have none (ACT_NO_KERNEL)
+ACT_CODES = {"none": 0, "elu": 1, "relu": 2, "tanh": 3, "sigmoid": 4, "selu": 5, "softplus": 6}
+ACT_NO_KERNEL = -1
+
+
+class LayerList(list):
+    """[(weight, bias, act, grad_out)] of a network's Linear layers, act an activation code.  `d2rl`: the input x is concatenated behind every hidden
+    output but the last - weight l is [out, in + D0] for 1 <= l <= len - 2 - and the walk keeps / expects the hidden outputs of those layers as the wide
+    rows [h | x] (include/trifinger_ppo_net.h).  `ext`: what needs_net_walk() answers, when the builder of the list already knows it (None: computed per call;
+    the trainer's lists carry it so that a minibatch step does not walk the layers again)"""
+    d2rl = False
+    ext = None
+
+
+def _d2rl(layers):
+    return bool(getattr(layers, "d2rl", False)) and len(layers) >= 3      # with one hidden layer there is no wide layer: the plain network
+
+
+def needs_net_walk(layers):
+    """True for a network only the extended walk (tfp_net_*) runs: an activation other than ELU / none, or d2rl"""
+    known = getattr(layers, "ext", None)
+    if known is not None:
+        return known
+    return _d2rl(layers) or any(int(l[2]) not in (0, 1) for l in layers)
+
+
+def _out_width(layers, l):
+    """columns of what the walk stores for layer l: [h | x] where the next layer of a d2rl network reads it"""
+    return layers[l][0].shape[0] + (layers[0][0].shape[1] if (_d2rl(layers) and l <= len(layers) - 3) else 0)
+
+
+class TfpNet(C.Structure):
+    """include/trifinger_ppo_net.h: TfpNet"""
+    _fields_ = [("mlp", TfpMlp), ("d2rl", C.c_int32), ("clip", C.c_float), ("mean", C.c_void_p), ("inv_std", C.c_void_p)]
+
+
+def _net_struct(m, layers, norm=None):
+    n = TfpNet()
+    n.mlp, n.d2rl = m, 1 if _d2rl(layers) else 0
+    if norm is not None:
+        n.mean, n.inv_std, n.clip = norm[0].data_ptr(), norm[1].data_ptr(), float(norm[2])
+    return n
+
+
+def _shape_struct(layers):
+    m = TfpMlp()
+    m.n_layers = len(layers)
+    m.dim[0] = layers[0][0].shape[1]
+    for l, (w, _, act, _) in enumerate(layers):
+        m.dim[l + 1] = w.shape[0]
+        m.act[l] = int(act)
+        if w.shape[1] != (_out_width(layers, l - 1) if l > 0 else m.dim[0]):
+            raise ValueError(f"weight of layer {l} has {w.shape[1]} columns, the network description gives {_out_width(layers, l - 1) if l > 0 else m.dim[0]}")
+    return m
+
+
+def net_fits(layer_lists, backward=False):
+    """whether the SHAPES of one or two networks (LayerLists; activation codes 0 .. 6) fit the network walk in the given direction: tfp_net_fits, no launch"""
+    if not (0 < len(layer_lists) <= 2) or any(not (0 < len(l) <= WALK_MAXL) or any(not (0 <= int(e[2]) <= 6) for e in l) for l in layer_lists):
+        return False
+    arr = (TfpNet * len(layer_lists))()
+    for i, layers in enumerate(layer_lists):
+        arr[i] = _net_struct(_shape_struct(layers), layers)
+    rc = load().tfp_net_fits(C.cast(arr, C.c_void_p), len(layer_lists), 1 if backward else 0)
+    if rc == -4:
+        return False
+    _chk(rc, "tfp_net_fits")
+    return True
 
 
 def _walk_struct(x, layers):
@@ -595,13 +675,17 @@ class TfpNorm(C.Structure):
     _fields_ = [("mean", C.c_void_p), ("inv_std", C.c_void_p), ("clip", C.c_float)]
 
 
-def mlp_walk_forward(nets, store_hidden=True, norms=None):
+def mlp_walk_forward(nets, store_hidden=True, norms=None, ext=None):
     """nets: [(x, layers)] for one or two Linear / ELU stacks over the same rows (`layers` as in mlp_forward).  ONE launch; returns the list of layer
     outputs per network (hidden outputs None with store_hidden = False: the rollout needs the network outputs only), or None when the shapes do not
     fit the walk (the caller then runs the layers one by one).  `norms`: None, or per network None / (mean_f, inv_std_f, clip): that network reads
-    clamp((x - mean_f) * inv_std_f, -clip, clip), formed while the rows are staged (tfp_mlp_forward_norm) - the bits of the plain walk on normalize_rows(x)."""
+    clamp((x - mean_f) * inv_std_f, -clip, clip), formed while the rows are staged (tfp_mlp_forward_norm) - the bits of the plain walk on normalize_rows(x).
+    A network with another activation than ELU / none or with d2rl (`layers` a LayerList) takes the call to tfp_net_forward (`ext` = True forces that entry
+    point, which for plain networks returns the same bits); of a d2rl network the outputs of the layers 0 .. len - 3 come back as the wide rows [h | x]."""
     if not _walkable(nets):
         return None
+    if ext is None:
+        ext = any(needs_net_walk(layers) for _, layers in nets)
     if norms is not None and not any(e is not None for e in norms):
         norms = None
     if norms is not None and not (len(norms) == len(nets) and all(e is None or _norm_ok(e, x.shape[1], x.device) for e, (x, _) in zip(norms, nets))):
@@ -614,12 +698,18 @@ def mlp_walk_forward(nets, store_hidden=True, norms=None):
         ys = []
         for l, (w, _, _, _) in enumerate(layers):
             keep = store_hidden or l == len(layers) - 1
-            y = torch.empty(M, w.shape[0], device=x.device, dtype=torch.float32) if keep else None
+            y = torch.empty(M, _out_width(layers, l) if ext else w.shape[0], device=x.device, dtype=torch.float32) if keep else None
             m.y[l] = y.data_ptr() if keep else None
             ys.append(y)
         arr[i] = m
         outs.append(ys)
-    if norms is not None:
+    if ext:
+        ea = (TfpNet * len(nets))()
+        for i, (_, layers) in enumerate(nets):
+            _shape_struct(layers)                                    # the width check
+            ea[i] = _net_struct(arr[i], layers, norms[i] if norms is not None else None)
+        rc = load().tfp_net_forward(C.cast(ea, C.c_void_p), len(nets), M, _stream(nets[0][0]))
+    elif norms is not None:
         nm = (TfpNorm * len(nets))()
         for i, e in enumerate(norms):
             if e is not None:
@@ -629,15 +719,17 @@ def mlp_walk_forward(nets, store_hidden=True, norms=None):
         rc = load().tfp_mlp_forward(C.cast(arr, C.c_void_p), len(nets), M, _stream(nets[0][0]))
     if rc == -4:
         return None
-    _chk(rc, "tfp_mlp_forward")
+    _chk(rc, "tfp_net_forward" if ext else ("tfp_mlp_forward_norm" if norms is not None else "tfp_mlp_forward"))
     return outs
 
 
-def mlp_walk_backward(nets):
+def mlp_walk_backward(nets, ext=None):
     """nets: [(gy, ys, layers)]: gy = gradient of the network output, ys = the layer outputs the forward kept.  ONE launch for the whole input-gradient
     chain; returns per network the list dz with dz[l] = gradient of layer l's pre-activation (dz[-1] is gy itself), or None when the shapes do not fit."""
     if not (0 < len(nets) <= 2) or any(len(layers) > WALK_MAXL or any(y is None for y in ys) for _, ys, layers in nets):
         return None
+    if ext is None:
+        ext = any(needs_net_walk(layers) for _, _, layers in nets)
     M = nets[0][0].shape[0]
     arr = (TfpMlp * len(nets))()
     outs = []
@@ -646,17 +738,29 @@ def mlp_walk_backward(nets):
         m = _walk_struct(gy, layers)
         dz = []
         for l in range(len(layers) - 1):
-            d = torch.empty_like(ys[l])
+            if not ext:
+                d = torch.empty_like(ys[l])
+            else:                                                    # dZ covers the hidden part only; ys[l] may be the wide rows [h | x]
+                if tuple(ys[l].shape) != (M, _out_width(layers, l)) or not ys[l].is_contiguous():
+                    raise ValueError(f"saved output of layer {l}: {tuple(ys[l].shape)}, contiguous {ys[l].is_contiguous()}; the walk stored and reads "
+                                     f"({M}, {_out_width(layers, l)}) contiguous")
+                d = torch.empty(M, layers[l][0].shape[0], device=gy.device, dtype=torch.float32)
             m.y[l] = d.data_ptr()
             m.yin[l] = ys[l].data_ptr()
             dz.append(d)
         dz.append(gy)
         arr[i] = m
         outs.append(dz)
-    rc = load().tfp_mlp_backward(C.cast(arr, C.c_void_p), len(nets), M, _stream(nets[0][0]))
+    if ext:
+        ea = (TfpNet * len(nets))()
+        for i, (_, _, layers) in enumerate(nets):
+            ea[i] = _net_struct(arr[i], layers)
+        rc = load().tfp_net_backward(C.cast(ea, C.c_void_p), len(nets), M, _stream(nets[0][0]))
+    else:
+        rc = load().tfp_mlp_backward(C.cast(arr, C.c_void_p), len(nets), M, _stream(nets[0][0]))
     if rc == -4:
         return None
-    _chk(rc, "tfp_mlp_backward")
+    _chk(rc, "tfp_net_backward" if ext else "tfp_mlp_backward")
     return outs
 
 
@@ -669,7 +773,8 @@ def _pairable(la, lc):
 
 
 def mlp_forward_pair(xa, la, xc, lc, store_hidden=True, norms=None):
-    """mlp_forward of two networks of the same depth and activations, one grouped launch per layer (4 launches instead of 8 for the trainer's MLPs).
+    """the forward of two networks over the same rows: ONE launch on the network walk (any activation code, d2rl: LayerLists), else - Linear / ELU stacks
+    of the same depth and activations only - one grouped launch per layer (4 launches instead of 8 for the trainer's MLPs).
     `norms` = (actor's, critic's), each None or (mean_f, inv_std_f, clip): the inputs are RAW and normalised on the way in - inside the walk, or by one
     normalize_rows launch per network in front of the per-layer path."""
     if norms is not None and not any(e is not None for e in norms):
@@ -678,6 +783,10 @@ def mlp_forward_pair(xa, la, xc, lc, store_hidden=True, norms=None):
         out = mlp_walk_forward([(xa, la), (xc, lc)], store_hidden, norms)
         if out is not None:
             return out[0], out[1]
+    if needs_net_walk(la) or needs_net_walk(lc):
+        # the per-layer launches are ELU / none stacks: never applied to a network that asked for something else (the trainer asks net_fits() once and runs
+        # such a network on torch when the walk declines it)
+        raise RuntimeError("a network with an activation other than ELU or with d2rl runs on the network walk only, and the walk declined these shapes")
     if norms is not None:
         xa = normalize_rows(xa, *norms[0]) if norms[0] is not None else xa
         xc = normalize_rows(xc, *norms[1]) if norms[1] is not None else xc
@@ -713,6 +822,8 @@ def mlp_backward_pair(xa, ya, gya, la, xc, yc, gyc, lc):
                     for g, x, o in zip(gys[sl], inps[sl], outs[sl]):
                         gemm_tn_bias(g, x, None, out=o, defer=True)
             return
+    if needs_net_walk(la) or needs_net_walk(lc):
+        raise RuntimeError("a network with an activation other than ELU or with d2rl runs on the network walk only, and the walk declined these shapes")
     if not _pairable(la, lc):
         mlp_backward(xa, ya, gya, la)
         mlp_backward(xc, yc, gyc, lc)
