@@ -91,6 +91,37 @@ def test_trainer_with_and_without_the_kernels(hip):
 
 
 @pytest.mark.gpu
+def test_trainer_without_a_central_value_network_with_and_without_the_kernels(hip):
+    """the same two epochs with `asymmetric_obs` off: no states, the critic reads `obs`, v_coef = 0.5 critic_coef, ONE optimiser group over the flat buffer"""
+    from leibnizgym_amd.config import gym_config
+    from leibnizgym_amd.envs import TrifingerEnv
+    from leibnizgym_amd.ppo import PPOTrainer
+    from leibnizgym_amd.utils.rlg_train import RlGamesGpuEnvAdapter
+    from leibnizgym_amd.wrappers import VecTaskPython
+
+    def run(fused):
+        cfg = gym_config("trifinger_difficulty_4")
+        cfg.update(num_instances=256, seed=1, physics_engine="physx", asymmetric_obs=False, episode_length=20)
+        env = TrifingerEnv(config=cfg, device="cuda:0", verbose=False)
+        ad = RlGamesGpuEnvAdapter("rlgpu", 256, env=VecTaskPython(env, rl_device="cuda:0"))
+        out = ad.reset()
+        assert not ad.use_global_obs and torch.is_tensor(out) and tuple(out.shape) == (256, 41)
+        tr = PPOTrainer(ad, 41, 0, 9, PPOConfig(horizon=8, minibatches=4, mini_epochs=2, fused_kernels=fused), device="cuda:0")
+        assert not tr.net.central and tr.fused_loss == fused
+        if fused:
+            assert tr.flat_opt.n0 == tr.flat_opt.n1 == tr.flat_opt.flat_p.numel()
+        torch.manual_seed(11)
+        stats = tr.train(2)
+        return [p.detach().clone() for p in tr.net.parameters()], stats
+    plain, s0 = run(False)
+    fused, s1 = run(True)
+    for a, b in zip(plain, fused):
+        assert torch.allclose(a, b, atol=3e-5, rtol=1e-3)
+    for k in ("loss", "a_loss", "c_loss", "kl"):
+        assert abs(s0[-1][k] - s1[-1][k]) < 1e-3 * max(1.0, abs(s0[-1][k])), (k, s0[-1][k], s1[-1][k])
+
+
+@pytest.mark.gpu
 def test_rollout_snapshots_the_observation_of_an_env_that_does_not_promise_stable_buffers(hip):
     """The fused rollout reads obs / states IN PLACE only from an env that declares `buffers_stable_until_next_step` (RlGamesGpuEnvAdapter: the engine's
     own tensors, overwritten by the next step on the same stream).  An env without the attribute may refresh its buffers whenever it likes: the trainer
