@@ -1,0 +1,183 @@
+// tf_eval.hip - episode statistics of a population of envs, one launch per env step behind the fused step (include/trifinger_ppo_eval.h), gfx950.
+//
+// One env per lane, 256-thread workgroups, grid = ceil(N / 256) (TF_MAX_ENVS gives at most 8192 workgroups: no grid-stride loop).  A lane reads its env's
+// cube and goal pose out of the SoA state (14 coalesced row loads: a wavefront reads one 256-byte line per row), the reward, the two flags and the step
+// count, and updates its four int32 of `env_acc` - about 100 bytes per env and step against the step's ~1.5 KB.  The final errors are formed by the step's
+// own device functions (tf_device_math.h) in the step's own expressions (tf_roles.h: o_dist / o_ang) and this unit is compiled with the step's
+// arithmetic flags, so the predicates are the step's bit for bit.
+//
+// A workgroup in which nobody ends an episode and no goal event falls (one __syncthreads_or) leaves after the per-env update.  Otherwise - and after a
+// reset of all envs EVERY env ends in the same launch, the burst is the normal case - the counters are popcounts of wavefront ballots, the sums 64-bit
+// shuffle reductions over the wavefront, both added over the four wavefronts through LDS; the two histograms are binned with LDS integer atomics; and the
+// workgroup issues ONE global 64-bit integer atomicAdd per non-zero quantity.  No float atomics, no hand-off between workgroups: nobody reads `acc`
+// before the stream is synchronised.  Everything in `acc` is an integer, so the order of the workgroups does not show in its bits.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "tf_device_math.h"
+#include "../../include/trifinger_ppo_eval.h"
+
+#define EV_THREADS 256
+#define EV_WAVES (EV_THREADS / 64)
+#define EV_SCALARS TFP_EVAL_HIST_POS            // counters and sums in front of the histograms
+#define EV_BINS (TFP_EVAL_POS_BINS + TFP_EVAL_ORI_BINS)
+
+typedef unsigned long long u64;
+
+struct EvalArgs {
+    const float* state; const float* reward; const uint8_t* reset_buf; const uint8_t* goal_reset_buf; const long long* steps;
+    int* env_acc; u64* acc;
+    int N; float pos_tol, ori_tol; int rule, cap;
+};
+
+// final position / orientation error of env i; `qfinite`: both quaternions are finite (quat_diff_rad clamps a non-finite product to pi)
+DEV void eval_errors(const float* __restrict__ state, int N, int i, float& e_p, float& e_o, bool& qfinite) {
+    float cp[3], cq[4], gp[3], gq[4];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { cp[j] = state[(size_t)(TF_S_CUBE_P + j) * N + i]; gp[j] = state[(size_t)(TF_S_GOAL_P + j) * N + i]; }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { cq[j] = state[(size_t)(TF_S_CUBE_Q + j) * N + i]; gq[j] = state[(size_t)(TF_S_GOAL_Q + j) * N + i]; }
+    const float dx = cp[0] - gp[0], dy = cp[1] - gp[1], dz = cp[2] - gp[2];       // norm3d(cp, gp) of tf_roles.h
+    e_p = f_sqrt(dx * dx + dy * dy + dz * dz);
+    e_o = quat_diff_rad(cq, gq);
+    float z = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) z = z + cq[j] * 0.0f + gq[j] * 0.0f;
+    qfinite = z == 0.0f;
+}
+
+DEV bool finite_f(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
+DEV int hist_bin(float x, int lo, int hi) {
+    const int q = (int)(__float_as_uint(x) >> 21);
+    return q < lo ? 0 : (q >= hi ? 1 + hi - lo : 1 + q - lo);
+}
+DEV long long wave_sum_ll(long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+DEV long long wave_count(bool p) { return (long long)__popcll(__ballot(p)); }
+
+__global__ void __launch_bounds__(EV_THREADS) k_eval_step(const EvalArgs a) {
+    __shared__ long long s_part[EV_WAVES][EV_SCALARS];
+    __shared__ int s_hist[EV_BINS];
+    const int t = threadIdx.x, i = (int)blockIdx.x * EV_THREADS + t, N = a.N;
+    const bool valid = i < N;
+    bool ends = false, goal_ev = false, counted = false, nonfin = false, complete = false, pos_ok = false, ori_ok = false, at_goal = false;
+    float ret = 0.0f, e_p = 0.0f, e_o = 0.0f;
+    int atg = 0, first = 0;
+    long long len = 0;
+    if (valid) {
+        bool qfinite;
+        eval_errors(a.state, N, i, e_p, e_o, qfinite);
+        pos_ok = e_p <= a.pos_tol;
+        ori_ok = e_o <= a.ori_tol;
+        at_goal = a.rule == 0 ? pos_ok : (a.rule == 1 ? (pos_ok && ori_ok) : ori_ok);
+        int* __restrict__ ea = a.env_acc;
+        ret = __int_as_float(ea[(size_t)TFP_EVAL_ENV_RETURN * N + i]) + a.reward[i];
+        atg = ea[(size_t)TFP_EVAL_ENV_AT_GOAL_STEPS * N + i] + (at_goal ? 1 : 0);
+        first = ea[(size_t)TFP_EVAL_ENV_FIRST_HIT * N + i];
+        const int eps = ea[(size_t)TFP_EVAL_ENV_EPISODES * N + i];
+        len = a.steps[i];
+        if (first == 0 && at_goal) first = (int)(len < 1 ? 1 : (len > 0x7FFFFFFF ? 0x7FFFFFFF : len));
+        const bool under = a.cap == 0 || eps < a.cap;
+        goal_ev = under && a.goal_reset_buf[i] != 0;
+        ends = a.reset_buf[i] != 0;
+        if (ends) {
+            const bool fin = finite_f(ret) && finite_f(e_p) && finite_f(e_o) && qfinite;
+            counted = under && fin;
+            nonfin = under && !fin;
+            complete = under && a.cap != 0 && eps + 1 == a.cap;
+            ea[(size_t)TFP_EVAL_ENV_RETURN * N + i] = 0;
+            ea[(size_t)TFP_EVAL_ENV_AT_GOAL_STEPS * N + i] = 0;
+            ea[(size_t)TFP_EVAL_ENV_FIRST_HIT * N + i] = 0;
+            if (under) ea[(size_t)TFP_EVAL_ENV_EPISODES * N + i] = eps + 1;
+        } else {
+            ea[(size_t)TFP_EVAL_ENV_RETURN * N + i] = __float_as_int(ret);
+            ea[(size_t)TFP_EVAL_ENV_AT_GOAL_STEPS * N + i] = atg;
+            ea[(size_t)TFP_EVAL_ENV_FIRST_HIT * N + i] = first;
+        }
+    }
+    if (t < EV_BINS) s_hist[t] = 0;
+    if (!__syncthreads_or((ends && (counted || nonfin)) || goal_ev)) return;      // the barrier also publishes the zeroed histogram
+
+    // ---- a workgroup with something to report: everything below is uniform control flow ----
+    const int wave = t >> 6, lane = t & 63;
+    long long v[EV_SCALARS];
+    v[TFP_EVAL_EPISODES] = wave_count(counted);
+    v[TFP_EVAL_NONFINITE] = wave_count(nonfin);
+    v[TFP_EVAL_POS_OK] = wave_count(counted && pos_ok);
+    v[TFP_EVAL_ORI_OK] = wave_count(counted && ori_ok);
+    v[TFP_EVAL_SUCCESS] = wave_count(counted && at_goal);
+    v[TFP_EVAL_REACHED] = wave_count(counted && first != 0);
+    v[TFP_EVAL_GOAL_EVENTS] = wave_count(goal_ev);
+    v[TFP_EVAL_ENVS_COMPLETE] = wave_count(complete);
+    long long q_ret = 0, q_pos = 0, q_ori = 0;
+    if (counted) {                                   // finite: the clamps see no NaN, the products are exact, the conversions defined
+        q_ret = __float2ll_rn(f_clamp(ret, -33554432.0f, 33554432.0f) * 65536.0f);
+        q_pos = __float2ll_rn(f_min(e_p, 1024.0f) * 1073741824.0f);
+        q_ori = __float2ll_rn(f_min(e_o, 4.0f) * 268435456.0f);
+        atomicAdd(&s_hist[hist_bin(e_p, TFP_EVAL_POS_Q_LO, TFP_EVAL_POS_Q_HI)], 1);
+        atomicAdd(&s_hist[TFP_EVAL_POS_BINS + hist_bin(e_o, TFP_EVAL_ORI_Q_LO, TFP_EVAL_ORI_Q_HI)], 1);
+    }
+    v[TFP_EVAL_SUM_LENGTH] = wave_sum_ll(counted ? len : 0);
+    v[TFP_EVAL_SUM_AT_GOAL_STEPS] = wave_sum_ll(counted ? (long long)atg : 0);
+    v[TFP_EVAL_SUM_FIRST_HIT] = wave_sum_ll(counted ? (long long)first : 0);
+    v[TFP_EVAL_SUM_RETURN] = wave_sum_ll(q_ret);
+    v[TFP_EVAL_SUM_POS_ERR] = wave_sum_ll(q_pos);
+    v[TFP_EVAL_SUM_ORI_ERR] = wave_sum_ll(q_ori);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < EV_SCALARS; ++k) s_part[wave][k] = v[k];
+    }
+    __syncthreads();
+    if (t < EV_SCALARS) {
+        long long s = 0;
+#pragma unroll
+        for (int w = 0; w < EV_WAVES; ++w) s += s_part[w][t];
+        if (s != 0) atomicAdd(&a.acc[t], (u64)s);                       // two's complement: a negative return sum adds as it should
+    } else if (t >= 64 && t < 64 + EV_BINS) {                           // another wavefront takes the bins
+        const int b = t - 64, c = s_hist[b];
+        if (c != 0) atomicAdd(&a.acc[TFP_EVAL_HIST_POS + b], (u64)c);
+    }
+}
+
+// the tests' window into the predicates: the device code above, counted
+__global__ void __launch_bounds__(EV_THREADS) k_eval_predicates(const float* __restrict__ state, int N, float pos_tol, float ori_tol, u64* __restrict__ out) {
+    const int i = (int)blockIdx.x * EV_THREADS + (int)threadIdx.x;
+    bool pos_ok = false, ori_ok = false;
+    if (i < N) {
+        float e_p, e_o;
+        bool qfinite;
+        eval_errors(state, N, i, e_p, e_o, qfinite);
+        pos_ok = e_p <= pos_tol;
+        ori_ok = e_o <= ori_tol;
+    }
+    const long long np = wave_count(pos_ok), no = wave_count(ori_ok);
+    if ((threadIdx.x & 63) == 0) {
+        if (np) atomicAdd(&out[0], (u64)np);
+        if (no) atomicAdd(&out[1], (u64)no);
+    }
+}
+
+extern "C" {
+
+int tfp_eval_step(const void* state, const void* reward, const void* reset_buf, const void* goal_reset_buf, const void* steps, void* env_acc, void* acc,
+                  int32_t N, float pos_tol, float ori_tol, int32_t rule, int32_t max_episodes_per_env, void* stream) {
+    if (!state || !reward || !reset_buf || !goal_reset_buf || !steps || !env_acc || !acc) return -1;
+    if (N < 1 || N > TF_MAX_ENVS || rule < 0 || rule > 2 || max_episodes_per_env < 0 || pos_tol != pos_tol || ori_tol != ori_tol) return -1;
+    EvalArgs a{};
+    a.state = (const float*)state; a.reward = (const float*)reward; a.reset_buf = (const uint8_t*)reset_buf; a.goal_reset_buf = (const uint8_t*)goal_reset_buf;
+    a.steps = (const long long*)steps; a.env_acc = (int*)env_acc; a.acc = (u64*)acc;
+    a.N = N; a.pos_tol = pos_tol; a.ori_tol = ori_tol; a.rule = rule; a.cap = max_episodes_per_env;
+    hipLaunchKernelGGL(k_eval_step, dim3((unsigned)((N + EV_THREADS - 1) / EV_THREADS)), dim3(EV_THREADS), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+int tfp_eval_test_predicates(const void* state, int32_t N, float pos_tol, float ori_tol, void* out, void* stream) {
+    if (!state || !out || N < 1 || N > TF_MAX_ENVS) return -1;
+    hipLaunchKernelGGL(k_eval_predicates, dim3((unsigned)((N + EV_THREADS - 1) / EV_THREADS)), dim3(EV_THREADS), 0, (hipStream_t)stream,
+                       (const float*)state, (int)N, pos_tol, ori_tol, (u64*)out);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+}  // extern "C"

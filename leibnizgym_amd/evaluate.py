@@ -1,0 +1,231 @@
+"""Episode statistics of a population of envs, accumulated on the device: what answers "how good is this checkpoint?".
+
+`EpisodeStats` binds to the buffers of a `TrifingerEngine` and is updated once per env step, behind the step, with no host synchronisation.  Episode ends
+are taken from the engine's own `reset_buf` (the public `dones` is `reset_buf & goal_reset_buf`, which the shipped configuration never sets although every
+env times out), the final errors from the state rows, which hold the final pose until the reset at the start of the next step.  On the GPU an update is one
+launch of csrc/tf_eval.hip (include/trifinger_ppo_eval.h has the definitions and the layout of the accumulator); the plain-torch form below has the same
+semantics, the same accumulator layout, the same bit-pattern bins and fixed-point conversions, and serves CPU tensors (the tests' oracle engines) and
+`fused=False`.  The accumulator holds integers only: integer sums commute, so the vector is bitwise the same on every run and after `merge` over ranks.
+"""
+import math
+import struct
+
+import torch
+
+from . import _capi as capi
+from .utils.torch_utils import quat_diff_rad
+
+# include/trifinger_ppo_eval.h
+ENV_RETURN, ENV_AT_GOAL_STEPS, ENV_FIRST_HIT, ENV_EPISODES, ENV_ROWS = 0, 1, 2, 3, 4
+POS_BINS, ORI_BINS = 50, 42
+POS_Q = (460, 508)            # bits >> 21 of 2^-12 m and of 1 m
+ORI_Q = (476, 516)            # ... of 2^-8 rad and of 4 rad
+(EPISODES, NONFINITE, POS_OK, ORI_OK, SUCCESS, REACHED, GOAL_EVENTS, ENVS_COMPLETE, SUM_LENGTH, SUM_AT_GOAL_STEPS, SUM_FIRST_HIT, SUM_RETURN, SUM_POS_ERR,
+ SUM_ORI_ERR, HIST_POS) = range(15)
+HIST_ORI = HIST_POS + POS_BINS
+ACC = HIST_ORI + ORI_BINS
+S_RETURN, S_POS_ERR, S_ORI_ERR = 2.0 ** 16, 2.0 ** 30, 2.0 ** 28
+RETURN_MAX, POS_ERR_MAX, ORI_ERR_MAX = 2.0 ** 25, 2.0 ** 10, 4.0
+
+_BUFFERS = ("state", "reward", "reset_buf", "goal_reset_buf", "steps")
+
+
+def engine_of(env):
+    """the TrifingerEngine behind an env: RlGamesGpuEnvAdapter (.env) -> VecTaskPython (._task) -> TrifingerEnv (._engine); an object that has the engine's
+    buffer attributes itself is returned as it is.  ValueError for an env without one."""
+    obj = env
+    for _ in range(8):
+        if all(hasattr(obj, k) for k in _BUFFERS):
+            return obj
+        nxt = next((getattr(obj, k) for k in ("_engine", "_task", "env") if getattr(obj, k, None) is not None), None)
+        if nxt is None:
+            break
+        obj = nxt
+    raise ValueError(f"{type(env).__name__}: no native engine behind this env (episode statistics are taken from the engine's buffers: "
+                     f"{', '.join(_BUFFERS)})")
+
+
+def rule_of_difficulty(d):
+    """which predicate is `at goal`: 0 position (difficulty < 4), 1 both (== 4), 2 orientation (> 4) - __check_termination of the reference"""
+    return 0 if d < 4 else (1 if d == 4 else 2)
+
+
+def bin_edge(q):
+    """the float32 with the bit pattern q << 21: the lower edge of the histogram bin that starts at q"""
+    return struct.unpack("<f", struct.pack("<I", q << 21))[0]
+
+
+def bin_bounds(b, q_lo, q_hi):
+    """(lower edge, upper edge) of bin b of a histogram with the bounds (q_lo, q_hi): bin 0 is [0, edge(q_lo)), the last one [edge(q_hi), inf)"""
+    if b == 0:
+        return 0.0, bin_edge(q_lo)
+    if b == 1 + q_hi - q_lo:
+        return bin_edge(q_hi), math.inf
+    return bin_edge(q_lo + b - 1), bin_edge(q_lo + b)
+
+
+def quantile_bin(hist, num, den, q_lo, q_hi):
+    """bounds of the bin that holds the ceil(num / den * n)-th smallest of the n samples of `hist` (integers); (nan, nan) without samples"""
+    n = int(sum(hist))
+    if n <= 0:
+        return math.nan, math.nan
+    k, c = max(1, -(-num * n // den)), 0
+    for b, h in enumerate(hist):
+        c += int(h)
+        if c >= k:
+            return bin_bounds(b, q_lo, q_hi)
+    raise AssertionError("unreachable: the bins sum to n")
+
+
+def _bins(x, q_lo, q_hi):
+    q = x.contiguous().view(torch.int32).to(torch.int64) >> 21          # x >= 0 where it is used: the pattern is a non-negative int32
+    return torch.where(q < q_lo, torch.zeros_like(q), torch.where(q >= q_hi, torch.full_like(q, 1 + q_hi - q_lo), 1 + q - q_lo))
+
+
+class EpisodeStats:
+    """Episode statistics of the envs of `engine` (a TrifingerEngine, or anything with its buffer attributes state / reward / reset_buf /
+    goal_reset_buf / steps): `reset()`, then `update()` after every env step - no host synchronisation -, `merge(group)` once in a distributed run,
+    `result()` for the one synchronising read.  Tolerances and the at-goal rule default to the engine's config.  `max_episodes_per_env`: an env that has
+    finished that many episodes goes on running, its further episodes are not counted (0: no cap).  `fused`: None = the kernel where the buffers live on
+    a GPU, plain torch otherwise."""
+
+    def __init__(self, engine, pos_tol=None, ori_tol=None, max_episodes_per_env=0, fused=None, rule=None):
+        self.engine = engine = engine_of(engine)
+        cfg = getattr(engine, "cfg", None)
+        if (pos_tol is None or ori_tol is None or rule is None) and cfg is None:
+            raise ValueError("an engine without a config needs pos_tol, ori_tol and rule")
+        self.pos_tol = float(cfg.position_tolerance if pos_tol is None else pos_tol)
+        self.ori_tol = float(cfg.orientation_tolerance if ori_tol is None else ori_tol)
+        self.rule = int(rule_of_difficulty(int(cfg.task_difficulty)) if rule is None else rule)
+        self.cap = int(max_episodes_per_env)
+        if self.rule not in (0, 1, 2) or self.cap < 0 or math.isnan(self.pos_tol) or math.isnan(self.ori_tol):
+            raise ValueError(f"rule {self.rule} (0, 1, 2), max_episodes_per_env {self.cap} (>= 0), tolerances {self.pos_tol}, {self.ori_tol}")
+        st = engine.state
+        self.num_envs = int(st.shape[1])
+        on_gpu = st.is_cuda
+        self.fused = on_gpu if fused is None else bool(fused)
+        if self.fused and not on_gpu:
+            raise ValueError("fused=True: the kernel reads device buffers, this engine lives on the CPU")
+        if self.fused:
+            for k in _BUFFERS:
+                t = getattr(engine, k)
+                if not (t.is_cuda and t.is_contiguous() and t.device == st.device):
+                    raise ValueError(f"engine buffer '{k}' is not a contiguous tensor on {st.device}")
+            if tuple(st.shape) != (capi.TF_STATE_ROWS, self.num_envs) or st.dtype != torch.float32:
+                raise ValueError("engine buffer 'state' of another layout than include/trifinger.h: float32 [TF_STATE_ROWS, N]")
+            # what the kernel reads them as: float reward, one-byte flags, int64 step counts, one element per env
+            for k, ok in (("reward", (torch.float32,)), ("reset_buf", (torch.bool, torch.uint8)), ("goal_reset_buf", (torch.bool, torch.uint8)), ("steps", (torch.int64,))):
+                t = getattr(engine, k)
+                if t.dtype not in ok or tuple(t.shape) != (self.num_envs,):
+                    raise ValueError(f"engine buffer '{k}': {t.dtype} {tuple(t.shape)}, the kernel reads {' / '.join(str(d) for d in ok)} [{self.num_envs}]")
+        self.env_acc = torch.zeros((ENV_ROWS, self.num_envs), dtype=torch.int32, device=st.device)
+        self.acc = torch.zeros((ACC,), dtype=torch.int64, device=st.device)
+        self.n_allreduce = 0
+
+    def reset(self):
+        self.env_acc.zero_()
+        self.acc.zero_()
+
+    def update(self):
+        """account for the env step that has just run (on the stream it ran on); no host synchronisation"""
+        e = self.engine
+        if self.fused:
+            from . import ppo_kernels as pk
+            dev = e.state.device
+            if torch.cuda.current_device() != dev.index:
+                with torch.cuda.device(dev):
+                    pk.eval_step(e.state, e.reward, e.reset_buf, e.goal_reset_buf, e.steps, self.env_acc, self.acc, self.pos_tol, self.ori_tol, self.rule, self.cap)
+            else:
+                pk.eval_step(e.state, e.reward, e.reset_buf, e.goal_reset_buf, e.steps, self.env_acc, self.acc, self.pos_tol, self.ori_tol, self.rule, self.cap)
+        else:
+            self._update_torch()
+
+    @torch.no_grad()
+    def _update_torch(self):
+        e, ea, acc = self.engine, self.env_acc, self.acc
+        st = e.state
+        cp, gp = st[capi.S_CUBE_P:capi.S_CUBE_P + 3], st[capi.S_GOAL_P:capi.S_GOAL_P + 3]
+        cq, gq = st[capi.S_CUBE_Q:capi.S_CUBE_Q + 4].t().contiguous(), st[capi.S_GOAL_Q:capi.S_GOAL_Q + 4].t().contiguous()
+        d = cp - gp
+        e_p = torch.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])
+        e_o = quat_diff_rad(cq, gq)
+        qfinite = torch.isfinite(cq).all(1) & torch.isfinite(gq).all(1)
+        pos_ok, ori_ok = e_p <= self.pos_tol, e_o <= self.ori_tol
+        at_goal = pos_ok if self.rule == 0 else ((pos_ok & ori_ok) if self.rule == 1 else ori_ok)
+        ret = ea[ENV_RETURN].view(torch.float32) + e.reward
+        atg = ea[ENV_AT_GOAL_STEPS] + at_goal.to(torch.int32)
+        length = e.steps.to(torch.int64)
+        first = torch.where((ea[ENV_FIRST_HIT] == 0) & at_goal, length.clamp(1, 2 ** 31 - 1).to(torch.int32), ea[ENV_FIRST_HIT])
+        eps = ea[ENV_EPISODES]
+        under = (eps < self.cap) if self.cap else torch.ones_like(at_goal)
+        ends = e.reset_buf.to(torch.bool)
+        fin = torch.isfinite(ret) & torch.isfinite(e_p) & torch.isfinite(e_o) & qfinite
+        counted, nonfin = ends & under & fin, ends & under & ~fin
+        i64 = torch.int64
+
+        def fixed(x, lo, hi, scale):
+            return torch.round(x.clamp(lo, hi) * scale).to(i64)
+        zero = torch.zeros_like(length)
+        acc[EPISODES] += counted.sum()
+        acc[NONFINITE] += nonfin.sum()
+        acc[POS_OK] += (counted & pos_ok).sum()
+        acc[ORI_OK] += (counted & ori_ok).sum()
+        acc[SUCCESS] += (counted & at_goal).sum()
+        acc[REACHED] += (counted & (first != 0)).sum()
+        acc[GOAL_EVENTS] += (under & e.goal_reset_buf.to(torch.bool)).sum()
+        if self.cap:
+            acc[ENVS_COMPLETE] += (ends & under & (eps + 1 == self.cap)).sum()
+        acc[SUM_LENGTH] += torch.where(counted, length, zero).sum()
+        acc[SUM_AT_GOAL_STEPS] += torch.where(counted, atg.to(i64), zero).sum()
+        acc[SUM_FIRST_HIT] += torch.where(counted, first.to(i64), zero).sum()
+        clean = torch.zeros_like(ret)                                      # a non-finite value never reaches a conversion
+        acc[SUM_RETURN] += fixed(torch.where(counted, ret, clean), -RETURN_MAX, RETURN_MAX, S_RETURN).sum()
+        acc[SUM_POS_ERR] += fixed(torch.where(counted, e_p, clean), 0.0, POS_ERR_MAX, S_POS_ERR).sum()
+        acc[SUM_ORI_ERR] += fixed(torch.where(counted, e_o, clean), 0.0, ORI_ERR_MAX, S_ORI_ERR).sum()
+        acc[HIST_POS:HIST_POS + POS_BINS] += torch.bincount(_bins(e_p, *POS_Q)[counted], minlength=POS_BINS)
+        acc[HIST_ORI:HIST_ORI + ORI_BINS] += torch.bincount(_bins(e_o, *ORI_Q)[counted], minlength=ORI_BINS)
+        izero = torch.zeros_like(atg)
+        ea[ENV_RETURN] = torch.where(ends, clean, ret).view(torch.int32)
+        ea[ENV_AT_GOAL_STEPS] = torch.where(ends, izero, atg)
+        ea[ENV_FIRST_HIT] = torch.where(ends, izero, first)
+        ea[ENV_EPISODES] = torch.where(ends & under, eps + 1, eps)
+
+    def envs_complete(self):
+        """the number of envs that have reached the cap; synchronises (one int64)"""
+        return int(self.acc[ENVS_COMPLETE])
+
+    def merge(self, group=None):
+        """sum the accumulator over the ranks of `group`: ONE all-reduce of the int64 vector, after which every rank holds the same bits"""
+        import torch.distributed as dist
+        dist.all_reduce(self.acc, op=dist.ReduceOp.SUM, group=group)
+        self.n_allreduce += 1
+
+    def result(self):
+        """the statistics as a dict of Python numbers (the one synchronising read); a rate or mean over zero episodes is nan"""
+        return summarize(self.acc.cpu().tolist())
+
+
+def summarize(raw):
+    """the result dict of an accumulator vector (a list of TFP_EVAL_ACC integers)"""
+    raw = [int(x) for x in raw]
+    if len(raw) != ACC:
+        raise ValueError(f"an accumulator has {ACC} entries, got {len(raw)}")
+    n = raw[EPISODES]
+
+    def per(x, d=n):
+        return x / d if d > 0 else math.nan
+    hp, ho = raw[HIST_POS:HIST_POS + POS_BINS], raw[HIST_ORI:HIST_ORI + ORI_BINS]
+    return {
+        "episodes": n, "nonfinite_episodes": raw[NONFINITE],
+        "success_rate": per(raw[SUCCESS]), "success_rate_position": per(raw[POS_OK]), "success_rate_orientation": per(raw[ORI_OK]),
+        "reached_goal_rate": per(raw[REACHED]),
+        "steps_to_goal_mean": per(raw[SUM_FIRST_HIT], raw[REACHED]),
+        "time_at_goal_fraction": per(raw[SUM_AT_GOAL_STEPS], raw[SUM_LENGTH]),
+        "goals_reached": raw[GOAL_EVENTS],
+        "episode_reward_mean": per(raw[SUM_RETURN] / S_RETURN), "episode_length_mean": per(raw[SUM_LENGTH]),
+        "final_position_error_mean": per(raw[SUM_POS_ERR] / S_POS_ERR), "final_orientation_error_mean": per(raw[SUM_ORI_ERR] / S_ORI_ERR),
+        "final_position_error_median": quantile_bin(hp, 1, 2, *POS_Q), "final_position_error_p90": quantile_bin(hp, 9, 10, *POS_Q),
+        "final_orientation_error_median": quantile_bin(ho, 1, 2, *ORI_Q), "final_orientation_error_p90": quantile_bin(ho, 9, 10, *ORI_Q),
+        "envs_complete": raw[ENVS_COMPLETE],
+        "raw": raw,
+    }

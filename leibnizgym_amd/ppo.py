@@ -436,6 +436,22 @@ class ActorCritic(nn.Module):
             v = self.critic(nc.normalize(xc) if nc is not None else xc).squeeze(-1)
         return mu, self.log_std.expand_as(mu), v
 
+    def mean_action(self, obs):
+        """the deterministic action: bit for bit the `mu` of dist_and_value.  On the hand-written kernels and without autograd it is ONE launch of the
+        network walk with the actor alone (no hidden output stored, the actor's input record applied where the walk stages its rows); a shape the walk
+        declines runs on the per-layer kernels; plain torch otherwise."""
+        na = self.obs_norm
+        if self.actor.mfma and obs.is_cuda and obs.dtype == torch.float32 and obs.dim() == 2 and not torch.is_grad_enabled():
+            from . import ppo_kernels as pk
+            x, layers = obs.contiguous(), self.actor.layer_list()
+            out = pk.mlp_walk_forward([(x, layers)], store_hidden=False, norms=[na.stats()] if na is not None else None) if pk.USE_WALK else None
+            if out is not None:
+                return out[0][-1]
+            if pk.needs_net_walk(layers):
+                raise RuntimeError("a network with an activation other than ELU or with d2rl runs on the network walk only, and the walk declined these shapes")
+            return pk.mlp_forward(pk.normalize_rows(x, *na.stats()) if na is not None else x, layers)[-1]
+        return self.actor(na.normalize(obs) if na is not None else obs)
+
 
 def neglogp(x, mu, log_std):
     return (0.5 * ((x - mu) / log_std.exp()).pow(2) + log_std + 0.5 * math.log(2 * math.pi)).sum(-1)
@@ -489,6 +505,7 @@ class PPOTrainer:
         self.dist_on = False
         self.n_grad_allreduce = self.n_kl_allreduce = 0       # collectives issued so far (what a test of the distributed path counts)
         self.n_norm_allgather = 0
+        self.n_eval_allreduce = 0
         rank = 0
         try:
             import torch.distributed as dist
@@ -728,6 +745,53 @@ class PPOTrainer:
                 info = extra[1]
         self.last = (obs, states)
         return total / max(steps, 1), info
+
+    @torch.no_grad()
+    def evaluate(self, episodes_per_env=1, deterministic=True, max_steps=None, pos_tol=None, ori_tol=None, check_every=32):
+        """Episode statistics of the current policy over `episodes_per_env` whole episodes of every env (leibnizgym_amd/evaluate.py: EpisodeStats, whose
+        result dict this returns, with the number of env steps taken as "steps").  The env is reset first - every env starts at step 0, there are no
+        partial episodes -, then stepped with the deterministic action (ActorCritic.mean_action) or with mu + sigma * randn, the statistics updated on the
+        device behind every step.  The host reads ONE counter every `check_every` steps and stops when every env has finished its episodes, at
+        episodes_per_env * episode_length steps (no episode is longer) or at `max_steps`, whichever comes first; an env without an episode length
+        needs `max_steps` (ValueError).  Tolerances default to the env's.  With a process group the accumulators of all ranks are summed in one
+        all-reduce (`n_eval_allreduce` counts them) and every rank returns the statistics of the whole population.
+        Nothing of the trainer moves: no weight, no normalisation record, no counter (frames, epoch).  The env does: at the end it is reset again and
+        `self.last` is that fresh observation - TRAINING CONTINUES FROM A RESET, not from where the last rollout stopped."""
+        from .evaluate import EpisodeStats, engine_of
+        k = int(episodes_per_env)
+        if k < 1:
+            raise ValueError(f"episodes_per_env = {episodes_per_env}: need at least one episode per env")
+        eng = engine_of(self.env)
+        ep_len = int(getattr(getattr(eng, "cfg", None), "episode_length", 0) or 0)
+        if ep_len <= 0 and max_steps is None:
+            raise ValueError("this env has no episode length (its episodes never time out): evaluate() needs max_steps")
+        limit = k * ep_len if ep_len > 0 else int(max_steps)
+        if max_steps is not None:
+            limit = min(limit, int(max_steps))
+        stats = EpisodeStats(eng, pos_tol=pos_tol, ori_tol=ori_tol, max_episodes_per_env=k)
+        live = getattr(self.env, "buffers_stable_until_next_step", False)      # the observation is consumed before the next step overwrites it
+
+        def obs_of(o):
+            o = o["obs"] if isinstance(o, dict) else o
+            return o if live else o.clone()
+        obs = obs_of(self.env.reset())
+        sigma = self.net.log_std.detach().exp()
+        every, steps = max(1, int(check_every)), 0
+        while steps < limit:
+            mu = self.net.mean_action(obs)
+            out = self.env.step(mu if deterministic else mu + sigma * torch.randn_like(mu))[0]
+            stats.update()
+            obs = obs_of(out)
+            steps += 1
+            if steps % every == 0 and steps < limit and stats.envs_complete() == stats.num_envs:
+                break
+        if self.dist_on:
+            stats.merge(self.group)
+            self.n_eval_allreduce += 1
+        res = stats.result()
+        res["steps"] = steps
+        self.last = self._unpack(self.env.reset())
+        return res
 
     @staticmethod
     def _unpack(o):

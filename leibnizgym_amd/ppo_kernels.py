@@ -90,6 +90,11 @@ def load():
             getattr(lib, name).argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
         lib.tfp_net_fits.restype = C.c_int
         lib.tfp_net_fits.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        # the checkpoint evaluator (include/trifinger_ppo_eval.h: csrc/tf_eval.hip), bound by symbol like the rest
+        lib.tfp_eval_step.restype = C.c_int
+        lib.tfp_eval_step.argtypes = [C.c_void_p] * 7 + [C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_void_p]
+        lib.tfp_eval_test_predicates.restype = C.c_int
+        lib.tfp_eval_test_predicates.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
         _LIB = lib
     return _LIB
 
@@ -378,6 +383,22 @@ def rollout_record(obs, states, mu, log_std, sigma, eps, val, buf, t):
                                    buf["states"][t].data_ptr() if states is not None else None, buf["act"][t].data_ptr(), buf["mu"][t].data_ptr(),
                                    buf["nlp"][t].data_ptr(), buf["val"][t].data_ptr(), _stream(mu)), "tfp_rollout_record")
     return buf["act"][t]
+
+
+def eval_step(state, reward, reset_buf, goal_reset_buf, steps, env_acc, acc, pos_tol, ori_tol, rule, max_episodes_per_env):
+    """one launch of the episode statistics behind an env step (include/trifinger_ppo_eval.h: tfp_eval_step) on torch's current stream: reads the env's
+    buffers, updates `env_acc` (int32 [4, N]) and `acc` (int64 [TFP_EVAL_ACC]) in place; no allocation, no synchronisation"""
+    _chk(load().tfp_eval_step(state.data_ptr(), reward.data_ptr(), reset_buf.data_ptr(), goal_reset_buf.data_ptr(), steps.data_ptr(), env_acc.data_ptr(),
+                              acc.data_ptr(), reward.shape[0], float(pos_tol), float(ori_tol), int(rule), int(max_episodes_per_env), _stream(state)),
+         "tfp_eval_step")
+
+
+def eval_test_predicates(state, pos_tol, ori_tol):
+    """int64 [2]: the number of envs with pos_ok / ori_ok from the evaluator's device code (tfp_eval_test_predicates: the tests' window into the predicates)"""
+    out = torch.zeros(2, dtype=torch.int64, device=state.device)
+    _chk(load().tfp_eval_test_predicates(state.data_ptr(), state.shape[1], float(pos_tol), float(ori_tol), out.data_ptr(), _stream(state)),
+         "tfp_eval_test_predicates")
+    return out
 
 
 def rollout_reward(r, d, scale, rew_t, done_t):
