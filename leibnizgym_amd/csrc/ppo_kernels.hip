@@ -19,11 +19,15 @@
 //   vc_i    = old_v_i + clamp(v_i - old_v_i, -e, e);   L_u = (v_i - ret_i)^2,  L_c = (vc_i - ret_i)^2
 //   c_i     = L_u when |v_i - old_v_i| <= e or L_u >= L_c, else L_c  (= max(L_u, L_c) outside the range; inside it the two agree to rounding and L_u is taken)
 //   d c_i / d v_i = 2 (v_i - ret_i) on the first branch, 0 on the second
+// tfp_ppo_loss_w / tfp_ppo_loss_vclip_w (include/trifinger_ppo_episode.h; `episode_ends`) are the same kernel again with a weight per sample: `adv` is then
+// [B, 2], (adv_i, w_i) interleaved, and the sample's surrogate, value, bounds and KL terms and its d_mu, d_v and share of d_logstd are multiplied by w_i -
+// as the LAST operation on each, so that w = 1 leaves every bit of the unweighted expression; the divisor stays B and the entropy term is untouched.
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include <stdint.h>
 #include <string.h>
 #include "../../include/trifinger_ppo_value.h"       // declares the value-side entry points (and trifinger_ppo.h): a definition that drifts fails here
+#include "../../include/trifinger_ppo_episode.h"     // ... and the episode-end entry points
 
 #define MAX_A 18
 
@@ -38,7 +42,7 @@ __device__ __forceinline__ float wave_sum(float x) {
 // One objective at a time per device (the trainer's single stream); results as before up to the order of the atomic sums.
 __device__ float g_loss_acc[24];
 __device__ unsigned g_loss_ticket;
-template <int A, bool VCLIP>
+template <int A, bool VCLIP, bool WGT>
 __global__ void __launch_bounds__(256) k_ppo_loss(const float* __restrict__ mu, const float* __restrict__ log_std, const float* __restrict__ act,
                                                   const float* __restrict__ old_nlp, const float* __restrict__ adv,
                                                   const float* __restrict__ old_mu, const float* __restrict__ v,
@@ -67,7 +71,9 @@ __global__ void __launch_bounds__(256) k_ppo_loss(const float* __restrict__ mu, 
             kl_term += 0.5f * dk * dk;
         }
         const float ratio = expf(old_nlp[i] - nlp);
-        const float ad = adv[i];
+        float ad, wi = 1.0f;
+        if constexpr (WGT) { const float2 aw = reinterpret_cast<const float2*>(adv)[i]; ad = aw.x; wi = aw.y; }   // (adv_i, w_i): one 8-byte load
+        else ad = adv[i];
         const float s1 = -ad * ratio;
         const float rc = fminf(fmaxf(ratio, 1.0f - e_clip), 1.0f + e_clip);
         const float s2 = -ad * rc;
@@ -83,19 +89,24 @@ __global__ void __launch_bounds__(256) k_ppo_loss(const float* __restrict__ mu, 
             const float vo = old_v[i], dlt = v[i] - vo;
             const float dc_ = (vo + fminf(fmaxf(dlt, -e_clip), e_clip)) - ret[i], lc = dc_ * dc_;
             const bool unclipped = (dlt >= -e_clip && dlt <= e_clip) || c_term >= lc;
-            d_v[i] = unclipped ? v_coef * 2.0f * dv_ * invB : 0.0f;
+            const float g_v = unclipped ? v_coef * 2.0f * dv_ * invB : 0.0f;
+            if constexpr (WGT) d_v[i] = g_v * wi; else d_v[i] = g_v;
             c_term = unclipped ? c_term : lc;
         } else {
-            d_v[i] = v_coef * 2.0f * dv_ * invB;
+            const float g_v = v_coef * 2.0f * dv_ * invB;
+            if constexpr (WGT) d_v[i] = g_v * wi; else d_v[i] = g_v;
         }
 #pragma unroll
         for (int a = 0; a < A; ++a) {
             const float hi = fmaxf(m[a] - 1.1f, 0.0f), lo = fmaxf(-1.1f - m[a], 0.0f);
             b_term += hi * hi + lo * lo;
             // d nlp / d mu = -(x - mu) / sigma^2 = -z / sigma ;  d nlp / d log sigma = 1 - z^2
-            d_mu[(size_t)i * A + a] = g_nlp * (-z[a] * inv_sig[a]) + bounds_coef * invB * 2.0f * (hi - lo);
-            dls[a] = g_nlp * (1.0f - z[a] * z[a]);
+            const float g_mu = g_nlp * (-z[a] * inv_sig[a]) + bounds_coef * invB * 2.0f * (hi - lo);
+            const float g_ls = g_nlp * (1.0f - z[a] * z[a]);
+            if constexpr (WGT) { d_mu[(size_t)i * A + a] = g_mu * wi; dls[a] = g_ls * wi; }
+            else { d_mu[(size_t)i * A + a] = g_mu; dls[a] = g_ls; }
         }
+        if constexpr (WGT) { a_term *= wi; c_term *= wi; b_term *= wi; kl_term *= wi; }
     }
     // reductions: wave shuffles, then the four waves of the block through LDS, ONE atomic per block and quantity (atomics on
     // the same address serialise at ~100 ns each: 128 waves on 14 addresses cost 13 us, 32 blocks cost 3)
@@ -225,10 +236,10 @@ int tfp_ppo_loss(const float* mu, const float* log_std, const float* act, const 
     dim3 grid((B + 255) / 256), block(256);
     const float* no_old_v = nullptr;
     if (A == 9)
-        hipLaunchKernelGGL((k_ppo_loss<9, false>), grid, block, 0, s, mu, log_std, act, old_nlp, adv, old_mu, v, ret, B, e_clip, v_coef, ent_coef,
+        hipLaunchKernelGGL((k_ppo_loss<9, false, false>), grid, block, 0, s, mu, log_std, act, old_nlp, adv, old_mu, v, ret, B, e_clip, v_coef, ent_coef,
                            bounds_coef, d_mu, d_v, d_logstd, loss_out, stats, no_old_v);
     else
-        hipLaunchKernelGGL((k_ppo_loss<18, false>), grid, block, 0, s, mu, log_std, act, old_nlp, adv, old_mu, v, ret, B, e_clip, v_coef, ent_coef,
+        hipLaunchKernelGGL((k_ppo_loss<18, false, false>), grid, block, 0, s, mu, log_std, act, old_nlp, adv, old_mu, v, ret, B, e_clip, v_coef, ent_coef,
                            bounds_coef, d_mu, d_v, d_logstd, loss_out, stats, no_old_v);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
@@ -242,10 +253,42 @@ int tfp_ppo_loss_vclip(const float* mu, const float* log_std, const float* act, 
     hipStream_t s = (hipStream_t)stream;
     dim3 grid((B + 255) / 256), block(256);
     if (A == 9)
-        hipLaunchKernelGGL((k_ppo_loss<9, true>), grid, block, 0, s, mu, log_std, act, old_nlp, adv, old_mu, v, ret, B, e_clip, v_coef, ent_coef,
+        hipLaunchKernelGGL((k_ppo_loss<9, true, false>), grid, block, 0, s, mu, log_std, act, old_nlp, adv, old_mu, v, ret, B, e_clip, v_coef, ent_coef,
                            bounds_coef, d_mu, d_v, d_logstd, loss_out, stats, old_v);
     else
-        hipLaunchKernelGGL((k_ppo_loss<18, true>), grid, block, 0, s, mu, log_std, act, old_nlp, adv, old_mu, v, ret, B, e_clip, v_coef, ent_coef,
+        hipLaunchKernelGGL((k_ppo_loss<18, true, false>), grid, block, 0, s, mu, log_std, act, old_nlp, adv, old_mu, v, ret, B, e_clip, v_coef, ent_coef,
+                           bounds_coef, d_mu, d_v, d_logstd, loss_out, stats, old_v);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// include/trifinger_ppo_episode.h: the two entry points above with a weight per sample, adv_w [B, 2] = (adv_i, w_i) interleaved (8-byte aligned: one load);
+// the compile-time variant WGT of the same kernel - its accumulators, its ticket, its one-call-at-a-time contract
+int tfp_ppo_loss_w(const float* mu, const float* log_std, const float* act, const float* old_nlp, const float* adv_w, const float* old_mu,
+                   const float* v, const float* ret, int32_t B, int32_t A, float e_clip, float v_coef, float ent_coef, float bounds_coef,
+                   float* d_mu, float* d_v, float* d_logstd, float* loss_out, float* stats, void* stream) {
+    if (B <= 0 || (A != 9 && A != 18) || !adv_w || ((uintptr_t)adv_w & 7) != 0) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid((B + 255) / 256), block(256);
+    const float* no_old_v = nullptr;
+    if (A == 9)
+        hipLaunchKernelGGL((k_ppo_loss<9, false, true>), grid, block, 0, s, mu, log_std, act, old_nlp, adv_w, old_mu, v, ret, B, e_clip, v_coef, ent_coef,
+                           bounds_coef, d_mu, d_v, d_logstd, loss_out, stats, no_old_v);
+    else
+        hipLaunchKernelGGL((k_ppo_loss<18, false, true>), grid, block, 0, s, mu, log_std, act, old_nlp, adv_w, old_mu, v, ret, B, e_clip, v_coef, ent_coef,
+                           bounds_coef, d_mu, d_v, d_logstd, loss_out, stats, no_old_v);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+int tfp_ppo_loss_vclip_w(const float* mu, const float* log_std, const float* act, const float* old_nlp, const float* adv_w, const float* old_mu,
+                         const float* v, const float* ret, const float* old_v, int32_t B, int32_t A, float e_clip, float v_coef, float ent_coef,
+                         float bounds_coef, float* d_mu, float* d_v, float* d_logstd, float* loss_out, float* stats, void* stream) {
+    if (B <= 0 || (A != 9 && A != 18) || !old_v || !adv_w || ((uintptr_t)adv_w & 7) != 0) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid((B + 255) / 256), block(256);
+    if (A == 9)
+        hipLaunchKernelGGL((k_ppo_loss<9, true, true>), grid, block, 0, s, mu, log_std, act, old_nlp, adv_w, old_mu, v, ret, B, e_clip, v_coef, ent_coef,
+                           bounds_coef, d_mu, d_v, d_logstd, loss_out, stats, old_v);
+    else
+        hipLaunchKernelGGL((k_ppo_loss<18, true, true>), grid, block, 0, s, mu, log_std, act, old_nlp, adv_w, old_mu, v, ret, B, e_clip, v_coef, ent_coef,
                            bounds_coef, d_mu, d_v, d_logstd, loss_out, stats, old_v);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
@@ -864,6 +907,65 @@ __global__ void __launch_bounds__(256) k_gae_vnorm(const float* __restrict__ rew
     }
 }
 
+// ---- `episode_ends` (include/trifinger_ppo_episode.h): the rollout sees the engine's episode ends ----
+// k_rollout_reward with the engine's own buffers in place of the public `done`: rew[t] = r * scale, end[t] = float(reset_buf != 0),
+// tout[t] = float(episode_length > 0 and steps >= episode_length).  reset_buf: one byte per env; steps: int64.  The engine's buffers are only read.
+__global__ void __launch_bounds__(256) k_rollout_flags(const float* __restrict__ r, const unsigned char* __restrict__ reset_buf, const long long* __restrict__ steps,
+                                                       float scale, long long episode_length, int n, float* __restrict__ b_rew, float* __restrict__ b_end,
+                                                       float* __restrict__ b_tout) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    b_rew[i] = r[i] * scale;
+    b_end[i] = reset_buf[i] ? 1.0f : 0.0f;
+    b_tout[i] = (episode_length > 0 && steps[i] >= episode_length) ? 1.0f : 0.0f;
+}
+// k_gae / k_gae_vnorm with episode ends, one thread per env, every operation rounded separately in the order of ppo.gae_with_ends:
+//   term = end (1 - tout) with BOOT, end otherwise;  w[t] = 1 - end[t-1], w[0] = 1 - last_end
+//   cont = 1 - end;  boot = 1 - term;  delta = (rew + (gamma val[t+1]) boot) - val[t];  last = delta + ((gamma tau) cont) last
+//   adv = last w;  ret = adv + val[t]
+// With end = 0 and last_end = 0 every factor is 1.0f and the outputs are the bits of k_gae / k_gae_vnorm.  VNORM: val is the network's raw output y and
+// the value of a step clamp(y, -clip, clip) / inv_std_f + mean_f; ret_n and v_old_n as in k_gae_vnorm, from the masked ret.
+template <bool VNORM>
+__global__ void __launch_bounds__(256) k_gae_ends(const float* __restrict__ rew, const float* __restrict__ end, const float* __restrict__ tout,
+                                                  const float* __restrict__ val, const float* __restrict__ last_end, int boot_on,
+                                                  const float* __restrict__ mean_f, const float* __restrict__ inv_std_f, float clip, float gamma, float gamma_tau,
+                                                  int T, int n, float* __restrict__ adv, float* __restrict__ ret, float* __restrict__ w,
+                                                  float* __restrict__ ret_n, float* __restrict__ v_old_n) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float mean = 0.0f, inv = 1.0f;
+    if constexpr (VNORM) { mean = mean_f[0]; inv = inv_std_f[0]; }
+    float last = 0.0f;
+    float v1 = val[(size_t)T * n + i];                           // the value of step t + 1
+    if constexpr (VNORM) { const float yT = clampf_nan(v1, clip), qT = yT / inv; v1 = qT + mean; }
+    float e0 = end[(size_t)(T - 1) * n + i];                     // end[t]
+    for (int t = T - 1; t >= 0; --t) {
+        float yc = val[(size_t)t * n + i], v0 = yc;
+        if constexpr (VNORM) { yc = clampf_nan(yc, clip); const float q = yc / inv; v0 = q + mean; }
+        const float ep = t > 0 ? end[(size_t)(t - 1) * n + i] : last_end[i];      // end[t - 1]
+        const float wt = 1.0f - ep, cont = 1.0f - e0;
+        float term = e0;
+        if (boot_on) { const float om = 1.0f - tout[(size_t)t * n + i]; term = e0 * om; }
+        const float boot = 1.0f - term;
+        const float gv = gamma * v1, gvn = gv * boot, s1 = rew[(size_t)t * n + i] + gvn, delta = s1 - v0;
+        const float gn = gamma_tau * cont, gl = gn * last;
+        last = delta + gl;
+        const float a = last * wt, r = a + v0;
+        adv[(size_t)t * n + i] = a;
+        ret[(size_t)t * n + i] = r;
+        w[(size_t)t * n + i] = wt;
+        if constexpr (VNORM) {
+            const float rm = r - mean, rs = rm * inv;
+            ret_n[(size_t)t * n + i] = clampf_nan(rs, clip);
+            v_old_n[(size_t)t * n + i] = yc;
+        }
+        v1 = v0;
+        e0 = ep;
+    }
+}
+
 // ---- one launch for the chunk sums of every layer of a backward pass ----
 struct SumArgs { const float* part[8]; float* gw[8]; float* gb[8]; int splits[8]; int n1[8]; int n2[8]; int first[9]; int n; };
 __global__ void __launch_bounds__(256) k_sum_partials_multi(SumArgs sa) {
@@ -920,6 +1022,31 @@ int tfp_gae_vnorm(const float* rew, const float* done, const float* y, const flo
     if (n <= 0 || T <= 0 || !mean_f || !inv_std_f || !(clip > 0.0f)) return -1;
     hipLaunchKernelGGL(k_gae_vnorm, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rew, done, y, mean_f, inv_std_f, clip, gamma, gamma_tau, T, n,
                        adv, ret, ret_n, v_old_n);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+// include/trifinger_ppo_episode.h
+int tfp_rollout_flags(const float* r, const void* reset_bytes, const int64_t* steps, float scale, int64_t episode_length, int32_t n, float* b_rew, float* b_end,
+                      float* b_tout, void* stream) {
+    if (n <= 0 || !r || !reset_bytes || !steps || !b_rew || !b_end || !b_tout) return -1;
+    hipLaunchKernelGGL(k_rollout_flags, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, r, (const unsigned char*)reset_bytes,
+                       (const long long*)steps, scale, (long long)episode_length, n, b_rew, b_end, b_tout);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+int tfp_gae_ends(const float* rew, const float* end, const float* tout, const float* val, const float* last_end, int32_t value_bootstrap, const float* mean_f,
+                 const float* inv_std_f, float clip, float gamma, float gamma_tau, int32_t T, int32_t n, float* adv, float* ret, float* w, float* ret_n,
+                 float* v_old_n, void* stream) {
+    if (n <= 0 || T <= 0 || !rew || !end || !tout || !val || !last_end || !adv || !ret || !w) return -1;
+    const bool vnorm = mean_f != nullptr;
+    if (vnorm != (inv_std_f != nullptr)) return -1;
+    if (vnorm && (!(clip > 0.0f) || !ret_n || !v_old_n)) return -1;
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    const int boot_on = value_bootstrap ? 1 : 0;
+    if (vnorm)
+        hipLaunchKernelGGL((k_gae_ends<true>), grid, block, 0, (hipStream_t)stream, rew, end, tout, val, last_end, boot_on, mean_f, inv_std_f, clip, gamma, gamma_tau,
+                           T, n, adv, ret, w, ret_n, v_old_n);
+    else
+        hipLaunchKernelGGL((k_gae_ends<false>), grid, block, 0, (hipStream_t)stream, rew, end, tout, val, last_end, boot_on, mean_f, inv_std_f, clip, gamma, gamma_tau,
+                           T, n, adv, ret, w, ret_n, v_old_n);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 // the products of tfp_gemm_tn_partials summed for n <= 8 layers in one launch (fixed order over the chunks: deterministic)

@@ -37,6 +37,30 @@ as with `fused_kernels=False` (the per-layer kernels are ELU only and are never 
 identity / None (the actor's rate stays; the KL statistic is still logged), linear (1e-6 + (learning_rate - 1e-6) * max(0, max_epochs - epoch) / max_epochs, set once
 per epoch); the central value network's rate is constant throughout.  Not built and refused by name (ValueError): `fixed_sigma: False`, `mu_activation` /
 `sigma_activation` other than None.
+Episode ends (`params.config.episode_ends`, `params.config.value_bootstrap`; both off by default, and off is the reference bit for bit).  The reference's
+`dones` is `reset_buf & goal_reset_buf`, which the shipped `success.activate: False` never sets although every env times out after `episode_length` steps
+and is reset inside the next step launch: by default GAE never sees an episode end.  With `episode_ends` the trainer resolves the engine
+behind the env once (evaluate.engine_of; an env without one is refused) and reads, after every env step t of a rollout, the engine's own buffers:
+    end[t]  = float(reset_buf != 0)                                       the episode ended in this step; the reset happens at the start of the NEXT step
+                                                                          launch, so the observation this step returned - and val[t + 1] - is the old episode's final state
+    tout[t] = float(episode_length > 0 and steps >= episode_length)       the time limit was hit (it takes precedence over a termination on the same step)
+    term[t] = end[t] * (1 - tout[t]) with `value_bootstrap`, end[t] without (RL-Games' default: a time-out counts as a terminal)
+    w[t]    = 1 - end[t - 1],  w[0] = 1 - last_end                        0 for a STALE sample: the policy acted on the final state of an episode that had ended, the
+                                                                          env was reset underneath it, reward and successor belong to the new episode
+`last_end` is the end row of the final step of the previous rollout, kept by the trainer; zero after construction, at the end of `evaluate` and in `restore`.
+GAE (`gae_with_ends`, the specification; float32, every operation rounded separately in the order written), t = T - 1 .. 0, last = 0:
+    cont = 1 - end[t];  boot = 1 - term[t];  delta = rew[t] + gamma * val[t + 1] * boot - val[t];  last = delta + (gamma * tau) * cont * last
+    adv[t] = last * w[t];  ret[t] = adv[t] + val[t]
+so a stale sample has adv = 0 and ret = val (neutral for the returns' record of `normalize_value`), and with end = 0 the buffers hold the bits they hold with
+the mode off (ret_n and v_old_n of `normalize_value` are formed from the masked ret as before).  Deliberately NOT RL-Games: its `value_bootstrap` adds gamma V of
+the observation BEFORE the step, this uses V of the final state, which the buffers hold.  buf["done"] does not exist with the mode on: `end` replaces it.
+Advantages are normalised over the samples with w = 1: mean = sum(w adv) / sum(w), std = sqrt(sum(w (adv - mean)^2) / (sum(w) - 1)),
+adv_n = w (adv - mean) / (std + 1e-8) (`masked_advantage_norm`: torch, once per epoch, no host sync).  In the objective every per-sample term - surrogate,
+value term, bounds term, KL statistic - and with it every per-sample gradient is multiplied by w_i; the divisor stays B, not sum(w) (the stale share is
+1 / episode_length, 0.13 % at 750 steps; a constant divisor needs no pre-pass over the minibatch); the batch-independent entropy term is unchanged.  The input
+records keep reading the whole rollout buffer (a stale observation is still a real observation).  `update()` reports `episodes_ended` = end.sum() of the epoch.
+On the GPU: include/trifinger_ppo_episode.h - one launch in place of the reward launch (`rollout_flags`), one in place of GAE (`gae_ends`), the weighted
+instantiation of the objective kernel reading (adv, w) interleaved, so that the gather still carries at most eight arrays.
 
 This is host-side training glue, NOT part of the measured hot path.  On a GPU the minibatch step runs on the hand-written kernels of
 csrc/ppo_kernels.hip (leibnizgym_amd/ppo_kernels.py): one gather launch, the Linear / ELU layers on fp32 MFMA, the objective with all
@@ -99,6 +123,13 @@ class PPOConfig:
     truncate_grads: bool = True       # params.config.truncate_grads: False = no gradient-norm truncation for the actor's optimiser
     value_truncate_grads: bool = True     # central_value_config.truncate_grads: the same for the central value network's
     lr_schedule: str = "adaptive"     # params.config.lr_schedule: adaptive | identity / None (constant) | linear (to 1e-6 at max_epochs, per epoch)
+    episode_ends: bool = False        # params.config.episode_ends: GAE and the objective see the engine's episode ends (module docstring); off = the reference
+    value_bootstrap: bool = False     # params.config.value_bootstrap (RL-Games' key): a time-out bootstraps from the final state's value; needs episode_ends
+
+    def __post_init__(self):
+        if self.value_bootstrap and not self.episode_ends:
+            raise ValueError("params.config.value_bootstrap: True needs params.config.episode_ends: True - without episode ends there is no time-out to "
+                             "bootstrap from")
 
     @classmethod
     def from_rlg(cls, rlg: dict, num_envs: int = None, **overrides):
@@ -130,7 +161,8 @@ class PPOConfig:
                   clip_value=bool(c.get("clip_value", False)), normalize_value=bool(c.get("normalize_value", False)),
                   activation=activation_name(net["mlp"].get("activation", "elu"), "params.network.mlp.activation"),
                   d2rl=bool(net["mlp"].get("d2rl", False)), truncate_grads=bool(c.get("truncate_grads", True)),
-                  lr_schedule=lr_schedule_name(c.get("lr_schedule", "adaptive")))
+                  lr_schedule=lr_schedule_name(c.get("lr_schedule", "adaptive")),
+                  episode_ends=bool(c.get("episode_ends", False)), value_bootstrap=bool(c.get("value_bootstrap", False)))
         # without a central value network the critic takes the actor's keys
         kw.update(value_activation=kw["activation"], value_d2rl=kw["d2rl"], value_truncate_grads=kw["truncate_grads"])
         if cv:
@@ -368,6 +400,32 @@ def denormalize_value(y, rec: "InputNorm"):
     return torch.clamp(y, -rec.clip, rec.clip) / rec.inv_std_f + rec.mean_f
 
 
+def gae_with_ends(rew, end, tout, val, last_end, gamma, tau, value_bootstrap):
+    """Generalised advantage estimation that sees episode ends (`episode_ends`; the module docstring has the definitions) - the SPECIFICATION of the loop,
+    what the torch path runs and what tfp_gae_ends reproduces bit for bit.  rew, end, tout [T, n]; val [T + 1, n] in reward units; last_end [n]: the end
+    row of the final step of the previous rollout.  Returns (adv, ret, w), each [T, n]; float32, every operation rounded separately in the order written."""
+    T = rew.shape[0]
+    term = end * (1.0 - tout) if value_bootstrap else end
+    w = torch.cat([(1.0 - last_end).unsqueeze(0), 1.0 - end[:T - 1]], dim=0)
+    adv, last = torch.zeros_like(rew), torch.zeros_like(rew[0])
+    for t in reversed(range(T)):
+        cont = 1.0 - end[t]
+        boot = 1.0 - term[t]
+        delta = rew[t] + gamma * val[t + 1] * boot - val[t]
+        last = delta + gamma * tau * cont * last
+        adv[t] = last * w[t]
+    return adv, adv + val[:T], w
+
+
+def masked_advantage_norm(adv, w):
+    """advantage normalisation over the samples with w = 1 (`episode_ends`): mean and unbiased std of those samples alone, stale samples leave as 0.
+    Sums only - no boolean indexing, no host sync"""
+    sw = w.sum()
+    mean = (w * adv).sum() / sw
+    std = torch.sqrt((w * (adv - mean) ** 2).sum() / (sw - 1.0))
+    return w * (adv - mean) / (std + 1e-8)
+
+
 class ActorCritic(nn.Module):
     obs_norm = None            # InputNorm of `obs` / of `states` (plain attributes, not modules: the model's state_dict keeps its keys); set by the trainer
     state_norm = None
@@ -539,6 +597,15 @@ class PPOTrainer:
         # otherwise receive the same noise sequence): re-seed with the rank after the weights are in place
         torch.manual_seed(c.seed + 7919 * rank)
         self.last = self._unpack(env.reset())
+        # `episode_ends`: the engine behind the env, resolved ONCE (its ValueError for an env without one), its episode length read where `evaluate` reads
+        # it (none = no time-outs), and the end row of the previous rollout's final step.  Off: none of it exists
+        self.ends = bool(c.episode_ends)
+        self.ends_engine, self.ends_ep_len, self.last_end = None, 0, None
+        if self.ends:
+            from .evaluate import engine_of
+            self.ends_engine = engine_of(env)
+            self.ends_ep_len = int(getattr(getattr(self.ends_engine, "cfg", None), "episode_length", 0) or 0)
+            self.last_end = torch.zeros(self.last[0].shape[0], device=self.device)
         self.frames = 0
         self.epoch = 0
         self.last_info = {}
@@ -725,6 +792,8 @@ class PPOTrainer:
         self.lr = float(ck.get("lr", self.lr))
         self.frames, self.epoch = int(ck.get("frames", 0)), int(ck.get("epoch", 0))
         self.best_reward = float(ck.get("best_reward", -float("inf")))
+        if self.last_end is not None:
+            self.last_end.zero_()
         return ck
 
     @torch.no_grad()
@@ -791,6 +860,8 @@ class PPOTrainer:
         res = stats.result()
         res["steps"] = steps
         self.last = self._unpack(self.env.reset())
+        if self.last_end is not None:                        # every env starts a fresh episode: no sample of the next rollout is stale
+            self.last_end.zero_()
         return res
 
     @staticmethod
@@ -815,7 +886,12 @@ class PPOTrainer:
         buf = dict(obs=torch.zeros(T, n, obs.shape[1], device=dev),
                    states=torch.zeros(T, n, states.shape[1], device=dev) if states is not None else None,
                    act=torch.zeros(T, n, A, device=dev), nlp=torch.zeros(T, n, device=dev), val=torch.zeros(T + 1, n, device=dev),
-                   rew=torch.zeros(T, n, device=dev), done=torch.zeros(T, n, device=dev), mu=torch.zeros(T, n, A, device=dev))
+                   rew=torch.zeros(T, n, device=dev), mu=torch.zeros(T, n, A, device=dev))
+        ends, eng, ep_len = self.ends, self.ends_engine, self.ends_ep_len
+        if ends:                                             # `end` replaces `done` (module docstring)
+            buf["end"], buf["tout"] = torch.zeros(T, n, device=dev), torch.zeros(T, n, device=dev)
+        else:
+            buf["done"] = torch.zeros(T, n, device=dev)
         for t in range(T):
             mu, ls, val_t = self.net.dist_and_value(obs, states)
             if fused:
@@ -836,7 +912,18 @@ class PPOTrainer:
             obs, states = ((out["obs"], out["states"]) if isinstance(out, dict) else (out, None)) if live else self._unpack(out)
             if isinstance(extra, (list, tuple)) and len(extra) > 1 and isinstance(extra[1], dict):
                 self.last_info = extra[1]                   # RL-Games convention: [[], info] (direct logging from the env)
-            if fused and r.is_cuda and r.dtype == torch.float32 and r.is_contiguous() and d.is_cuda and d.dtype in (torch.bool, torch.uint8) and d.is_contiguous():
+            if ends:
+                # the engine's buffers behind the step: stable until its next step, read in place (one launch where the reward launch stands)
+                rb, st = eng.reset_buf, eng.steps
+                if (fused and r.is_cuda and r.dtype == torch.float32 and r.is_contiguous() and rb.device == r.device and rb.dtype in (torch.bool, torch.uint8)
+                        and rb.is_contiguous() and st.device == r.device and st.dtype == torch.int64 and st.is_contiguous()):
+                    pk.rollout_flags(r, rb, st, c.reward_scale, ep_len, buf["rew"][t], buf["end"][t], buf["tout"][t])
+                else:
+                    buf["rew"][t] = r.to(dev) * c.reward_scale
+                    buf["end"][t] = (rb != 0).to(dev).float()
+                    if ep_len > 0:
+                        buf["tout"][t] = (st >= ep_len).to(dev).float()
+            elif fused and r.is_cuda and r.dtype == torch.float32 and r.is_contiguous() and d.is_cuda and d.dtype in (torch.bool, torch.uint8) and d.is_contiguous():
                 pk.rollout_reward(r, d, c.reward_scale, buf["rew"][t], buf["done"][t])
             else:
                 buf["rew"][t] = r.to(dev) * c.reward_scale
@@ -844,7 +931,21 @@ class PPOTrainer:
         buf["val"][T] = self.net.value(obs, states)
         self.last = (obs, states)
         vn = self.value_norm
-        if vn is not None and fused:
+        if ends:
+            if fused and vn is not None:                     # as below: buf["val"] keeps the raw normalised output y on this path
+                buf["adv"], buf["ret"], buf["w"], buf["ret_n"], buf["v_old_n"] = pk.gae_ends(buf["rew"], buf["end"], buf["tout"], buf["val"], self.last_end, c.gamma,
+                                                                                             c.tau, c.value_bootstrap, vn.mean_f, vn.inv_std_f, vn.clip)
+            elif fused:
+                buf["adv"], buf["ret"], buf["w"] = pk.gae_ends(buf["rew"], buf["end"], buf["tout"], buf["val"], self.last_end, c.gamma, c.tau, c.value_bootstrap)
+            else:
+                if vn is not None:
+                    buf["v_old_n"] = torch.clamp(buf["val"][:T], -vn.clip, vn.clip)
+                    buf["val"] = denormalize_value(buf["val"], vn)
+                buf["adv"], buf["ret"], buf["w"] = gae_with_ends(buf["rew"], buf["end"], buf["tout"], buf["val"], self.last_end, c.gamma, c.tau, c.value_bootstrap)
+                if vn is not None:
+                    buf["ret_n"] = torch.clamp((buf["ret"] - vn.mean_f) * vn.inv_std_f, -vn.clip, vn.clip)
+            self.last_end = buf["end"][T - 1].clone()        # w[0] of the next rollout
+        elif vn is not None and fused:
             # buf["val"] holds the network's raw output y, a NORMALISED value: GAE runs on v = clamp(y, -5, 5) / inv_std_f + mean_f (module docstring), which
             # the kernel forms on the way - buf["val"] keeps y on this path, the torch form below replaces it by v
             buf["adv"], buf["ret"], buf["ret_n"], buf["v_old_n"] = pk.gae_vnorm(buf["rew"], buf["done"], buf["val"], vn.mean_f, vn.inv_std_f, vn.clip, c.gamma, c.tau)
@@ -880,13 +981,16 @@ class PPOTrainer:
         nlp = neglogp(d["act"][idx], mu, ls)
         ratio = (d["old_nlp"][idx] - nlp).exp()
         a = d["adv"][idx]
-        a_loss = torch.max(-a * ratio, -a * ratio.clamp(1 - c.e_clip, 1 + c.e_clip)).mean()
+        # `episode_ends`: every per-sample term times w_i, the divisor stays B (module docstring); off: the expressions as they were
+        w = d["w"][idx] if self.ends else None
+        wmean = (lambda x: (w * x).mean()) if self.ends else (lambda x: x.mean())
+        a_loss = wmean(torch.max(-a * ratio, -a * ratio.clamp(1 - c.e_clip, 1 + c.e_clip)))
         v = self.net.value(obs, d["states"][idx] if d["states"] is not None else None)
         if self.clip_v:
-            c_loss = clipped_value_loss(v, d["ret"][idx], d["old_v"][idx], c.e_clip).mean()
+            c_loss = wmean(clipped_value_loss(v, d["ret"][idx], d["old_v"][idx], c.e_clip))
         else:
-            c_loss = (v - d["ret"][idx]).pow(2).mean()
-        b_loss = ((mu - 1.1).clamp(min=0).pow(2) + (-1.1 - mu).clamp(min=0).pow(2)).sum(-1).mean()
+            c_loss = wmean((v - d["ret"][idx]).pow(2))
+        b_loss = wmean(((mu - 1.1).clamp(min=0).pow(2) + (-1.1 - mu).clamp(min=0).pow(2)).sum(-1))
         ent = (ls + 0.5 + 0.5 * math.log(2 * math.pi)).sum(-1).mean()
         # with a central value network RL-Games trains it on its own unweighted MSE and drops the critic term from the
         # actor loss; the two gradients do not overlap (separate parameters), so one backward serves both
@@ -896,7 +1000,7 @@ class PPOTrainer:
             p.grad = None
         loss.backward()
         with torch.no_grad():      # KL between the old and new diagonal Gaussians (same sigma)
-            kl = (0.5 * ((mu - d["old_mu"][idx]) / ls.exp()).pow(2)).sum(-1).mean()
+            kl = wmean((0.5 * ((mu - d["old_mu"][idx]) / ls.exp()).pow(2)).sum(-1))
             acc["kl"] += kl
             acc["loss"] += loss.detach(); acc["a_loss"] += a_loss.detach(); acc["c_loss"] += c_loss.detach()
 
@@ -908,9 +1012,9 @@ class PPOTrainer:
         statistics accumulate on the device in `acc["_fused"]` = (loss, a_loss, c_loss, kl)"""
         from . import ppo_kernels as pk
         c = self.cfg
-        srcs = [d["obs"], d["act"], d["old_nlp"], d["adv"], d["ret"], d["old_mu"]] + ([d["old_v"]] if self.clip_v else []) + \
+        srcs = [d["obs"], d["act"], d["old_nlp"], d["adv_w"] if self.ends else d["adv"], d["ret"], d["old_mu"]] + ([d["old_v"]] if self.clip_v else []) + \
                ([d["states"]] if d["states"] is not None else [])
-        assert len(srcs) <= pk.GATHER_MAX                  # obs, act, old_nlp, adv, ret (or ret_n), old_mu, old_v, states: exactly one launch's worth
+        assert len(srcs) <= pk.GATHER_MAX                  # obs, act, old_nlp, adv (or (adv, w) interleaved), ret (or ret_n), old_mu, old_v, states: exactly one launch's worth
         na, ns = self.net.obs_norm, self.net.state_norm
         if na is None and ns is None:
             g = pk.gather_rows(srcs, idx)
@@ -933,6 +1037,8 @@ class PPOTrainer:
             mu, v = ya[-1], yc[-1].squeeze(-1)
             v_coef = 1.0 if self.net.central else 0.5 * c.critic_coef
             kw = {"old_v": old_v} if self.clip_v else {}
+            if self.ends:                                  # the gathered array is (adv_i, w_i): the weighted instantiation of the objective
+                kw["adv_w"], adv = adv, None
             _, d_mu, d_v, _ = pk.ppo_loss_and_grads(mu, self.net.log_std, v, act, old_nlp, adv, ret, old_mu, acc["_fused"], c.e_clip, v_coef,
                                                     c.entropy_coef, c.bounds_loss_coef, d_ls_out=self.flat_opt.grad_view(self.net.log_std), **kw)
             try:
@@ -985,13 +1091,19 @@ class PPOTrainer:
         T, n = buf["nlp"].shape
         flat = lambda x: x.reshape(T * n, *x.shape[2:]) if x is not None else None  # noqa: E731
         adv = flat(buf["adv"])
+        w = flat(buf["w"]) if self.ends else None
         if c.normalize_advantage:
-            adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+            adv = masked_advantage_norm(adv, w) if self.ends else (adv - adv.mean()) / (adv.std() + 1e-8)
         vn = self.value_norm
         src = dict(obs=flat(buf["obs"]), states=flat(buf["states"]), act=flat(buf["act"]), old_nlp=flat(buf["nlp"]),
                    ret=flat(buf["ret_n"] if vn is not None else buf["ret"]), adv=adv, old_mu=flat(buf["mu"]))
         if self.clip_v:                            # the value the loss is clipped around, in the units the network works in
             src["old_v"] = flat(buf["v_old_n"] if vn is not None else buf["val"][:T])
+        if self.ends:
+            src["w"] = w
+            if self.fused_loss:                    # (adv_i, w_i) interleaved, stacked once per epoch: ONE gathered array, the gather keeps its eight
+                src["adv_w"] = torch.stack([adv, w], dim=1)
+            ended = buf["end"].sum()               # device side; fetched with the other statistics below
         total = T * n
         mb = max(1, total // c.minibatches)
         dev = src["obs"].device
@@ -1038,6 +1150,8 @@ class PPOTrainer:
             stats[k] = float(acc[k]) / max(count, 1)
         stats["lr"] = self.lr
         stats["mean_reward"] = float(buf["rew"].mean() / c.reward_scale)
+        if self.ends:
+            stats["episodes_ended"] = int(ended)
         return stats
 
     @torch.no_grad()

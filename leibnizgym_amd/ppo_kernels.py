@@ -95,6 +95,15 @@ def load():
         lib.tfp_eval_step.argtypes = [C.c_void_p] * 7 + [C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_void_p]
         lib.tfp_eval_test_predicates.restype = C.c_int
         lib.tfp_eval_test_predicates.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
+        # episode ends (include/trifinger_ppo_episode.h), bound by symbol like the rest
+        lib.tfp_rollout_flags.restype = C.c_int
+        lib.tfp_rollout_flags.argtypes = [C.c_void_p] * 3 + [C.c_float, C.c_int64, C.c_int32] + [C.c_void_p] * 4
+        lib.tfp_gae_ends.restype = C.c_int
+        lib.tfp_gae_ends.argtypes = [C.c_void_p] * 5 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32] + [C.c_void_p] * 6
+        lib.tfp_ppo_loss_w.restype = C.c_int
+        lib.tfp_ppo_loss_w.argtypes = lib.tfp_ppo_loss.argtypes
+        lib.tfp_ppo_loss_vclip_w.restype = C.c_int
+        lib.tfp_ppo_loss_vclip_w.argtypes = lib.tfp_ppo_loss_vclip.argtypes
         _LIB = lib
     return _LIB
 
@@ -130,25 +139,31 @@ class _FusedPPOLoss(torch.autograd.Function):
         return d_mu * g, d_ls * g, d_v * g, None, None, None, None, None, None, None, None, None, None
 
 
-def ppo_loss_and_grads(mu, log_std, v, act, old_nlp, adv, ret, old_mu, stats, e_clip, v_coef, ent_coef, bounds_coef, d_ls_out=None, old_v=None):
+def ppo_loss_and_grads(mu, log_std, v, act, old_nlp, adv, ret, old_mu, stats, e_clip, v_coef, ent_coef, bounds_coef, d_ls_out=None, old_v=None, adv_w=None):
     """(loss, d loss / d mu, d loss / d v, d loss / d log_std) straight from the kernel - for a caller that starts the backward pass at
     the network outputs itself (`torch.autograd.backward((mu, v), (d_mu, d_v))`), without a loss node multiplying them by one.
-    `old_v` [B] (the value recorded in the rollout): the value term is clipped around it with the surrogate's `e_clip` (tfp_ppo_loss_vclip: `clip_value`)"""
+    `old_v` [B] (the value recorded in the rollout): the value term is clipped around it with the surrogate's `e_clip` (tfp_ppo_loss_vclip: `clip_value`).
+    `adv_w` [B, 2] = (adv_i, w_i) interleaved (`episode_ends`; `adv` is then None): every per-sample term and gradient times w_i, the divisor stays B
+    (tfp_ppo_loss_w / tfp_ppo_loss_vclip_w, include/trifinger_ppo_episode.h)"""
     lib = load()
     mu, v = mu.contiguous(), v.contiguous()
     B, A = mu.shape
+    if adv_w is not None:
+        assert adv is None and adv_w.dtype == torch.float32 and adv_w.is_contiguous() and tuple(adv_w.shape) == (B, 2) and adv_w.device == mu.device
+        adv = adv_w
+    fn, fn_clip, tag = (lib.tfp_ppo_loss, lib.tfp_ppo_loss_vclip, "") if adv_w is None else (lib.tfp_ppo_loss_w, lib.tfp_ppo_loss_vclip_w, "_w")
     d_mu, d_v = torch.empty_like(mu), torch.empty_like(v)
     out = torch.empty(A + 1, device=mu.device, dtype=torch.float32)
     d_ls, loss = (out[:A] if d_ls_out is None else d_ls_out), out[A]      # d_ls_out: e.g. the parameter's slot of a flat gradient buffer
     if old_v is not None:
         assert old_v.dtype == torch.float32 and old_v.is_contiguous() and old_v.numel() == B and old_v.device == mu.device
-        _chk(lib.tfp_ppo_loss_vclip(mu.data_ptr(), log_std.data_ptr(), act.data_ptr(), old_nlp.data_ptr(), adv.data_ptr(), old_mu.data_ptr(),
-                                    v.data_ptr(), ret.data_ptr(), old_v.data_ptr(), B, A, float(e_clip), float(v_coef), float(ent_coef), float(bounds_coef),
-                                    d_mu.data_ptr(), d_v.data_ptr(), d_ls.data_ptr(), loss.data_ptr(), stats.data_ptr(), _stream(mu)), "tfp_ppo_loss_vclip")
+        _chk(fn_clip(mu.data_ptr(), log_std.data_ptr(), act.data_ptr(), old_nlp.data_ptr(), adv.data_ptr(), old_mu.data_ptr(),
+                     v.data_ptr(), ret.data_ptr(), old_v.data_ptr(), B, A, float(e_clip), float(v_coef), float(ent_coef), float(bounds_coef),
+                     d_mu.data_ptr(), d_v.data_ptr(), d_ls.data_ptr(), loss.data_ptr(), stats.data_ptr(), _stream(mu)), "tfp_ppo_loss_vclip" + tag)
         return loss, d_mu, d_v, d_ls
-    _chk(lib.tfp_ppo_loss(mu.data_ptr(), log_std.data_ptr(), act.data_ptr(), old_nlp.data_ptr(), adv.data_ptr(), old_mu.data_ptr(),
-                          v.data_ptr(), ret.data_ptr(), B, A, float(e_clip), float(v_coef), float(ent_coef), float(bounds_coef),
-                          d_mu.data_ptr(), d_v.data_ptr(), d_ls.data_ptr(), loss.data_ptr(), stats.data_ptr(), _stream(mu)), "tfp_ppo_loss")
+    _chk(fn(mu.data_ptr(), log_std.data_ptr(), act.data_ptr(), old_nlp.data_ptr(), adv.data_ptr(), old_mu.data_ptr(),
+            v.data_ptr(), ret.data_ptr(), B, A, float(e_clip), float(v_coef), float(ent_coef), float(bounds_coef),
+            d_mu.data_ptr(), d_v.data_ptr(), d_ls.data_ptr(), loss.data_ptr(), stats.data_ptr(), _stream(mu)), "tfp_ppo_loss" + tag)
     return loss, d_mu, d_v, d_ls
 
 
@@ -426,6 +441,38 @@ def gae_vnorm(rew, done, y, mean_f, inv_std_f, clip, gamma, tau):
     _chk(load().tfp_gae_vnorm(rew.data_ptr(), done.data_ptr(), y.data_ptr(), mean_f.data_ptr(), inv_std_f.data_ptr(), float(clip), float(gamma), float(gamma * tau),
                               T, n, adv.data_ptr(), ret.data_ptr(), ret_n.data_ptr(), v_old_n.data_ptr(), _stream(rew)), "tfp_gae_vnorm")
     return adv, ret, ret_n, v_old_n
+
+
+# ---- episode ends (include/trifinger_ppo_episode.h; ppo.PPOTrainer with `episode_ends`) --------------------------------------------------------
+def rollout_flags(r, reset_buf, steps, scale, episode_length, rew_t, end_t, tout_t):
+    """rew_t = r * scale, end_t = float(reset_buf != 0), tout_t = float(episode_length > 0 and steps >= episode_length) in ONE launch (it stands where
+    `rollout_reward` does); reset_buf: torch.bool / uint8 [n], steps: int64 [n] - the engine's own buffers, only read"""
+    n = r.numel()
+    assert r.dtype == torch.float32 and r.is_contiguous() and reset_buf.dtype in (torch.bool, torch.uint8) and reset_buf.is_contiguous() and reset_buf.numel() == n
+    assert steps.dtype == torch.int64 and steps.is_contiguous() and steps.numel() == n and reset_buf.device == r.device and steps.device == r.device
+    for t in (rew_t, end_t, tout_t):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n and t.device == r.device
+    _chk(load().tfp_rollout_flags(r.data_ptr(), reset_buf.data_ptr(), steps.data_ptr(), float(scale), int(episode_length), n, rew_t.data_ptr(), end_t.data_ptr(),
+                                  tout_t.data_ptr(), _stream(r)), "tfp_rollout_flags")
+
+
+def gae_ends(rew, end, tout, val, last_end, gamma, tau, value_bootstrap, mean_f=None, inv_std_f=None, clip=0.0):
+    """`gae` with episode ends in one launch (ppo.gae_with_ends is the specification): rew, end, tout [T, n], val [T + 1, n], last_end [n] ->
+    (adv, ret, w), each [T, n].  With mean_f / inv_std_f (the float32 [1] tensors of the returns' record) and clip, val is the value network's raw
+    normalised output and the result is (adv, ret, w, ret_n, v_old_n): `gae_vnorm` with episode ends."""
+    T, n = rew.shape
+    vnorm = mean_f is not None
+    ins = (rew, end, tout, val, last_end) + ((mean_f, inv_std_f) if vnorm else ())
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.device == rew.device for t in ins)
+    assert end.shape == (T, n) and tout.shape == (T, n) and val.shape == (T + 1, n) and last_end.shape == (n,)
+    assert not vnorm or (mean_f.numel() == 1 and inv_std_f.numel() == 1 and float(clip) > 0.0)
+    adv, ret, w = (torch.empty_like(rew) for _ in range(3))
+    ret_n, v_old_n = (torch.empty_like(rew), torch.empty_like(rew)) if vnorm else (None, None)
+    _chk(load().tfp_gae_ends(rew.data_ptr(), end.data_ptr(), tout.data_ptr(), val.data_ptr(), last_end.data_ptr(), 1 if value_bootstrap else 0,
+                             mean_f.data_ptr() if vnorm else None, inv_std_f.data_ptr() if vnorm else None, float(clip), float(gamma), float(gamma * tau), T, n,
+                             adv.data_ptr(), ret.data_ptr(), w.data_ptr(), ret_n.data_ptr() if vnorm else None, v_old_n.data_ptr() if vnorm else None,
+                             _stream(rew)), "tfp_gae_ends")
+    return (adv, ret, w, ret_n, v_old_n) if vnorm else (adv, ret, w)
 
 
 def gemm_tn_bias(a, b, y=None, chunk=256, out=None, defer=False):
