@@ -15,6 +15,7 @@
 #include <stdint.h>
 #include "tf_device_math.h"
 #include "../../include/trifinger_ppo_eval.h"
+#include "../../include/trifinger_ppo_track.h"
 
 #define EV_THREADS 256
 #define EV_WAVES (EV_THREADS / 64)
@@ -159,7 +160,94 @@ __global__ void __launch_bounds__(EV_THREADS) k_eval_predicates(const float* __r
     }
 }
 
+// ---- the training-time episode tracker (include/trifinger_ppo_track.h): the launch behind every env step of a rollout, with the bookkeeping folded in ----
+// One env per lane as above.  Every lane does what k_rollout_reward (mode A: `done_bytes` given) or k_rollout_flags (mode B) of ppo_kernels.hip does - the
+// same single product and the same selects, under the same contraction-free flags - and keeps its env's running return and `armed` flag (two int32).  A
+// workgroup in which nobody ends an episode leaves there (one __syncthreads_or): no atomic, and the 14 pose rows are never loaded.  In a workgroup with an
+// end only the lanes that end an ARMED episode load their pose; counters are ballots, sums 64-bit shuffle reductions, the four wavefronts meet in LDS and
+// the workgroup issues one 64-bit integer atomicAdd per non-zero quantity.
+__global__ void __launch_bounds__(EV_THREADS) k_rollout_track(const TfpTrackArgs a) {
+    __shared__ long long s_part[EV_WAVES][TFP_TRACK_ACC];
+    const int t = threadIdx.x, i = (int)blockIdx.x * EV_THREADS + t, N = a.N;
+    bool ends = false, armed = false, tout = false;
+    float ret = 0.0f;
+    long long len = 0;
+    if (i < N) {
+        const float r = a.reward[i];
+        ends = ((const uint8_t*)a.reset_buf)[i] != 0;
+        len = a.steps[i];
+        tout = a.episode_length > 0 && len >= a.episode_length;
+        a.b_rew[i] = r * a.scale;
+        if (a.done_bytes) {
+            a.b_done[i] = ((const uint8_t*)a.done_bytes)[i] ? 1.0f : 0.0f;
+        } else {
+            a.b_end[i] = ends ? 1.0f : 0.0f;
+            a.b_tout[i] = tout ? 1.0f : 0.0f;
+        }
+        int* __restrict__ trk = a.env_trk;
+        const bool first = len == 1;
+        ret = first ? r : __int_as_float(trk[(size_t)TFP_TRACK_ENV_RETURN * N + i]) + r;
+        armed = first || trk[(size_t)TFP_TRACK_ENV_ARMED * N + i] != 0;
+        trk[(size_t)TFP_TRACK_ENV_RETURN * N + i] = ends ? 0 : __float_as_int(ret);
+        trk[(size_t)TFP_TRACK_ENV_ARMED * N + i] = (armed && !ends) ? 1 : 0;
+    }
+    if (!__syncthreads_or(ends)) return;
+
+    // ---- a workgroup in which an episode ended: everything below is uniform control flow but for the pose loads ----
+    bool counted = false, nonfin = false, pos_ok = false, ori_ok = false, at_goal = false;
+    float e_p = 0.0f, e_o = 0.0f;
+    if (ends && armed) {
+        bool qfinite;
+        eval_errors((const float*)a.state, N, i, e_p, e_o, qfinite);
+        pos_ok = e_p <= a.pos_tol;
+        ori_ok = e_o <= a.ori_tol;
+        at_goal = a.rule == 0 ? pos_ok : (a.rule == 1 ? (pos_ok && ori_ok) : ori_ok);
+        counted = finite_f(ret) && finite_f(e_p) && finite_f(e_o) && qfinite;
+        nonfin = !counted;
+    }
+    const int wave = t >> 6, lane = t & 63;
+    long long v[TFP_TRACK_ACC];
+    v[TFP_TRACK_EPISODES] = wave_count(counted);
+    v[TFP_TRACK_SUCCESS] = wave_count(counted && at_goal);
+    v[TFP_TRACK_POS_OK] = wave_count(counted && pos_ok);
+    v[TFP_TRACK_ORI_OK] = wave_count(counted && ori_ok);
+    v[TFP_TRACK_TIMEOUT] = wave_count(counted && tout);
+    v[TFP_TRACK_NONFINITE] = wave_count(nonfin);
+    v[TFP_TRACK_UNARMED] = wave_count(ends && !armed);
+    long long q_ret = 0, q_pos = 0, q_ori = 0;
+    if (counted) {                                   // finite: the clamps see no NaN, the products are exact, the conversions defined
+        q_ret = __float2ll_rn(f_clamp(ret, -33554432.0f, 33554432.0f) * 65536.0f);
+        q_pos = __float2ll_rn(f_min(e_p, 1024.0f) * 1073741824.0f);
+        q_ori = __float2ll_rn(f_min(e_o, 4.0f) * 268435456.0f);
+    }
+    v[TFP_TRACK_SUM_LENGTH] = wave_sum_ll(counted ? len : 0);
+    v[TFP_TRACK_SUM_RETURN] = wave_sum_ll(q_ret);
+    v[TFP_TRACK_SUM_POS_ERR] = wave_sum_ll(q_pos);
+    v[TFP_TRACK_SUM_ORI_ERR] = wave_sum_ll(q_ori);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < TFP_TRACK_ACC; ++k) s_part[wave][k] = v[k];
+    }
+    __syncthreads();
+    if (t < TFP_TRACK_ACC) {
+        long long s = 0;
+#pragma unroll
+        for (int w = 0; w < EV_WAVES; ++w) s += s_part[w][t];
+        if (s != 0) atomicAdd((u64*)&a.acc[t], (u64)s);                 // two's complement: a negative return sum adds as it should
+    }
+}
+
 extern "C" {
+
+int tfp_rollout_track(const TfpTrackArgs* args, void* stream) {
+    if (!args) return -1;
+    const TfpTrackArgs a = *args;
+    if (!a.state || !a.reward || !a.reset_buf || !a.steps || !a.b_rew || !a.env_trk || !a.acc) return -1;
+    if (a.done_bytes ? !a.b_done : (!a.b_end || !a.b_tout)) return -1;
+    if (a.N < 1 || a.N > TF_MAX_ENVS || a.rule < 0 || a.rule > 2 || a.pos_tol != a.pos_tol || a.ori_tol != a.ori_tol) return -1;
+    hipLaunchKernelGGL(k_rollout_track, dim3((unsigned)((a.N + EV_THREADS - 1) / EV_THREADS)), dim3(EV_THREADS), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
 
 int tfp_eval_step(const void* state, const void* reward, const void* reset_buf, const void* goal_reset_buf, const void* steps, void* env_acc, void* acc,
                   int32_t N, float pos_tol, float ori_tol, int32_t rule, int32_t max_episodes_per_env, void* stream) {

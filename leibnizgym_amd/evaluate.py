@@ -229,3 +229,200 @@ def summarize(raw):
         "envs_complete": raw[ENVS_COMPLETE],
         "raw": raw,
     }
+
+
+# ---- the training-time episode tracker (include/trifinger_ppo_track.h) -------------------------------------------------------------------------------
+TRK_RETURN, TRK_ARMED, TRK_ROWS = 0, 1, 2
+(T_EPISODES, T_SUCCESS, T_POS_OK, T_ORI_OK, T_TIMEOUT, T_SUM_LENGTH, T_SUM_RETURN, T_SUM_POS_ERR, T_SUM_ORI_ERR, T_NONFINITE, T_UNARMED, TRACK_ACC) = range(12)
+_TRACK_BUFFERS = ("state", "reward", "reset_buf", "steps")
+
+
+def _fma32(a, b, c):
+    """float32 fma(a, b, c), rounded ONCE, out of float64 operations: the product of two float32 is exact in float64; the sum is rounded to odd (the
+    error of the float64 addition is recovered with TwoSum, and an inexact sum with an even last bit moves to its odd neighbour on the side of the
+    error), after which the rounding to float32 is the rounding of the exact value (53 >= 2 * 24 + 2 bits)"""
+    p, c = a.double() * b.double(), c.double()
+    s = p + c
+    bb = s - p
+    err = (p - (s - bb)) + (c - bb)
+    even = (s.view(torch.int64) & 1) == 0
+    odd = torch.nextafter(s, torch.where(err > 0, torch.full_like(s, math.inf), torch.full_like(s, -math.inf)))
+    return torch.where((err != 0) & even & torch.isfinite(s), odd, s).float()
+
+
+def _sqrt32(x):
+    """the correctly rounded float32 square root (the device's IEEE sqrt), whatever torch's own float32 sqrt does on this backend: through float64,
+    whose 53 bits make the second rounding harmless for a square root"""
+    return x.double().sqrt().float()
+
+
+def step_asin(x):
+    """tf_asin of csrc/tf_device_math.h operation for operation in float32 - the arcsine the step, the evaluator's kernel and the tracker's kernel use -,
+    for x >= 0"""
+    f = lambda v: torch.full_like(x, v)                                    # noqa: E731
+    a = torch.where(x < 1.0, x, f(1.0))                                    # fminf: a NaN becomes 1
+    big = a > 0.5
+    z = torch.where(big, 0.5 * (1.0 - a), a * a)
+    y = torch.where(big, _sqrt32(z), a)
+    p = f(4.2163199048e-2)
+    for k in (2.4181311049e-2, 4.5470025998e-2, 7.4953002686e-2, 1.6666752422e-1):
+        p = _fma32(p, z, f(k))
+    p = _fma32(p * z, y, y)
+    return torch.where(big, 1.5707963267948966 - (p + p), p)
+
+
+def step_errors(state):
+    """(e_p, e_o, both quaternions finite) per env from the state rows, in the step's own expressions (csrc/tf_eval.hip: eval_errors) - float32, every
+    operation rounded separately in the device code's order, the arcsine the step's polynomial (step_asin), so that the values are the kernel's"""
+    from .utils.torch_utils import quat_conjugate, quat_mul
+    cp, gp = state[capi.S_CUBE_P:capi.S_CUBE_P + 3], state[capi.S_GOAL_P:capi.S_GOAL_P + 3]
+    cq, gq = state[capi.S_CUBE_Q:capi.S_CUBE_Q + 4].t().contiguous(), state[capi.S_GOAL_Q:capi.S_GOAL_Q + 4].t().contiguous()
+    d = cp - gp
+    e_p = _sqrt32(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])
+    m = quat_mul(cq, quat_conjugate(gq))
+    nrm = _sqrt32(m[:, 0] * m[:, 0] + m[:, 1] * m[:, 1] + m[:, 2] * m[:, 2])
+    e_o = 2.0 * step_asin(nrm)
+    return e_p, e_o, torch.isfinite(cq).all(1) & torch.isfinite(gq).all(1)
+
+
+class EpisodeTracker:
+    """What an EPISODE is worth while the policy trains (`params.config.track_episodes`): returns, lengths and success of the episodes that end during
+    the rollouts, accumulated on the device behind every env step with no host synchronisation.  include/trifinger_ppo_track.h has the definitions; in
+    short, per env: the float32 return is summed in step order from the step with steps == 1 (which ARMS the env), and at a step with reset_buf set an
+    armed env's episode enters the integer accumulator `acc` [TRACK_ACC] - with the final errors, predicates and finite test of `EpisodeStats` - while an
+    env that was never armed (the tracker did not see the episode's first step) adds to UNARMED alone.  So a tracker created in the middle of episodes, or
+    whose envs were reset underneath it, needs no protocol with the caller.
+    `update()` accounts for the env step that has just run.  On the GPU the trainer calls `step_fused(...)` instead: ONE launch that also does the work of
+    the launch it replaces (ppo_kernels.rollout_track).  The plain-torch statement serves CPU tensors and `fused=False`: the integers are identical and
+    the return is summed in the same order.  `merge(group)` sums the accumulator over ranks, `take()` hands it out and clears it (no sync),
+    `window_stats` turns integer vectors into the reported dict.  `episode_length` (for TIMEOUT) defaults to the engine's config; 0: no time limit."""
+
+    def __init__(self, engine, pos_tol=None, ori_tol=None, rule=None, fused=None, episode_length=None):
+        self.engine = engine = engine_of(engine)
+        cfg = getattr(engine, "cfg", None)
+        if (pos_tol is None or ori_tol is None or rule is None) and cfg is None:
+            raise ValueError("an engine without a config needs pos_tol, ori_tol and rule")
+        self.pos_tol = float(cfg.position_tolerance if pos_tol is None else pos_tol)
+        self.ori_tol = float(cfg.orientation_tolerance if ori_tol is None else ori_tol)
+        self.rule = int(rule_of_difficulty(int(cfg.task_difficulty)) if rule is None else rule)
+        self.ep_len = int((getattr(cfg, "episode_length", 0) or 0) if episode_length is None else episode_length)
+        if self.rule not in (0, 1, 2) or math.isnan(self.pos_tol) or math.isnan(self.ori_tol):
+            raise ValueError(f"rule {self.rule} (0, 1, 2), tolerances {self.pos_tol}, {self.ori_tol}")
+        st = engine.state
+        self.num_envs = n = int(st.shape[1])
+        on_gpu = st.is_cuda
+        self.fused = on_gpu if fused is None else bool(fused)
+        if self.fused and not on_gpu:
+            raise ValueError("fused=True: the kernel reads device buffers, this engine lives on the CPU")
+        if self.fused:
+            if tuple(st.shape) != (capi.TF_STATE_ROWS, n) or st.dtype != torch.float32 or not st.is_contiguous():
+                raise ValueError("engine buffer 'state' of another layout than include/trifinger.h: contiguous float32 [TF_STATE_ROWS, N]")
+            for k, ok in (("reward", (torch.float32,)), ("reset_buf", (torch.bool, torch.uint8)), ("steps", (torch.int64,))):
+                t = getattr(engine, k)
+                if t.dtype not in ok or tuple(t.shape) != (n,) or not t.is_contiguous() or t.device != st.device:
+                    raise ValueError(f"engine buffer '{k}': {t.dtype} {tuple(t.shape)} on {t.device}, the kernel reads contiguous "
+                                     f"{' / '.join(str(d) for d in ok)} [{n}] on {st.device}")
+            self._scratch = torch.empty((3, n), dtype=torch.float32, device=st.device)       # the outputs of a launch nobody asked outputs of (`update`)
+        self.env_trk = torch.zeros((TRK_ROWS, n), dtype=torch.int32, device=st.device)
+        self.acc = torch.zeros((TRACK_ACC,), dtype=torch.int64, device=st.device)
+        self.n_allreduce = 0
+
+    def reset_envs(self):
+        """forget every running episode (the accumulator stays): after `restore()` and at the end of `evaluate()`"""
+        self.env_trk.zero_()
+
+    def step_fused(self, scale, rew_t, done=None, done_t=None, end_t=None, tout_t=None):
+        """the ONE launch behind an env step: rew_t = reward * scale and, with `done`, done_t = float(done) (in place of ppo_kernels.rollout_reward) or
+        end_t / tout_t (in place of ppo_kernels.rollout_flags) - and the tracker's update.  Fused trackers only."""
+        if not self.fused:
+            raise ValueError("step_fused on a tracker that runs the torch statement: call update()")
+        from . import ppo_kernels as pk
+        e = self.engine
+        pk.rollout_track(e.state, e.reward, e.reset_buf, e.steps, self.env_trk, self.acc, scale, self.ep_len, self.pos_tol, self.ori_tol, self.rule,
+                         rew_t, done=done, done_t=done_t, end_t=end_t, tout_t=tout_t)
+
+    def update(self):
+        """account for the env step that has just run (on the stream it ran on); no host synchronisation"""
+        if self.fused:
+            s = self._scratch
+            dev = s.device
+            if torch.cuda.current_device() != dev.index:
+                with torch.cuda.device(dev):
+                    self.step_fused(1.0, s[0], end_t=s[1], tout_t=s[2])
+            else:
+                self.step_fused(1.0, s[0], end_t=s[1], tout_t=s[2])
+        else:
+            self._update_torch()
+
+    @torch.no_grad()
+    def _update_torch(self):
+        """the statement of include/trifinger_ppo_track.h in plain torch"""
+        e, trk, acc = self.engine, self.env_trk, self.acc
+        st, r = e.state, e.reward
+        s = e.steps.to(torch.int64)
+        ends = e.reset_buf.to(torch.bool)
+        first = s == 1
+        ret = torch.where(first, r, trk[TRK_RETURN].view(torch.float32) + r)
+        armed = first | (trk[TRK_ARMED] != 0)
+        e_p, e_o, qfinite = step_errors(st)
+        pos_ok, ori_ok = e_p <= self.pos_tol, e_o <= self.ori_tol
+        at_goal = pos_ok if self.rule == 0 else ((pos_ok & ori_ok) if self.rule == 1 else ori_ok)
+        fin = torch.isfinite(ret) & torch.isfinite(e_p) & torch.isfinite(e_o) & qfinite
+        counted, nonfin, unarmed = ends & armed & fin, ends & armed & ~fin, ends & ~armed
+        tout = (s >= self.ep_len) if self.ep_len > 0 else torch.zeros_like(ends)
+        i64 = torch.int64
+
+        def fixed(x, lo, hi, scale):
+            return torch.round(x.clamp(lo, hi) * scale).to(i64)
+        clean = torch.zeros_like(ret)                                      # a non-finite value never reaches a conversion
+        acc[T_EPISODES] += counted.sum()
+        acc[T_SUCCESS] += (counted & at_goal).sum()
+        acc[T_POS_OK] += (counted & pos_ok).sum()
+        acc[T_ORI_OK] += (counted & ori_ok).sum()
+        acc[T_TIMEOUT] += (counted & tout).sum()
+        acc[T_SUM_LENGTH] += torch.where(counted, s, torch.zeros_like(s)).sum()
+        acc[T_SUM_RETURN] += fixed(torch.where(counted, ret, clean), -RETURN_MAX, RETURN_MAX, S_RETURN).sum()
+        acc[T_SUM_POS_ERR] += fixed(torch.where(counted, e_p, clean), 0.0, POS_ERR_MAX, S_POS_ERR).sum()
+        acc[T_SUM_ORI_ERR] += fixed(torch.where(counted, e_o, clean), 0.0, ORI_ERR_MAX, S_ORI_ERR).sum()
+        acc[T_NONFINITE] += nonfin.sum()
+        acc[T_UNARMED] += unarmed.sum()
+        trk[TRK_RETURN] = torch.where(ends, clean, ret).view(torch.int32)
+        trk[TRK_ARMED] = (armed & ~ends).to(torch.int32)
+
+    def take(self):
+        """the accumulator since the last take (int64 [TRACK_ACC], a device tensor of its own), cleared behind it; no host synchronisation"""
+        v = self.acc.clone()
+        self.acc.zero_()
+        return v
+
+    def merge(self, group=None):
+        """sum the accumulator over the ranks of `group` (before `take`): ONE all-reduce of the int64 vector, after which every rank holds the same bits"""
+        import torch.distributed as dist
+        dist.all_reduce(self.acc, op=dist.ReduceOp.SUM, group=group)
+        self.n_allreduce += 1
+
+    @staticmethod
+    def window(vectors, games_to_track):
+        """of epoch vectors in time order, the most recent ones with EPISODES > 0, taken whole, until their EPISODES reach `games_to_track`
+        (returned in time order; empty before any episode has ended)"""
+        out, n = [], 0
+        for v in reversed(vectors):
+            if int(v[T_EPISODES]) > 0:
+                out.append([int(x) for x in v])
+                n += out[-1][T_EPISODES]
+                if n >= int(games_to_track):
+                    break
+        return out[::-1]
+
+    @staticmethod
+    def window_stats(vectors):
+        """the reported dict of a window of integer vectors: their sum, as means and rates over its EPISODES.  Without an episode only
+        {"episodes": 0}: no NaN goes into a log."""
+        raw = [sum(int(v[k]) for v in vectors) for k in range(TRACK_ACC)]
+        n = raw[T_EPISODES]
+        if n <= 0:
+            return {"episodes": 0}
+        return {"episodes": n, "episode_return": raw[T_SUM_RETURN] / S_RETURN / n, "episode_length": raw[T_SUM_LENGTH] / n,
+                "success_rate": raw[T_SUCCESS] / n, "pos_ok_rate": raw[T_POS_OK] / n, "ori_ok_rate": raw[T_ORI_OK] / n,
+                "timeout_rate": raw[T_TIMEOUT] / n, "final_pos_err": raw[T_SUM_POS_ERR] / S_POS_ERR / n,
+                "final_ori_err": raw[T_SUM_ORI_ERR] / S_ORI_ERR / n}

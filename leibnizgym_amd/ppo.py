@@ -61,6 +61,32 @@ value term, bounds term, KL statistic - and with it every per-sample gradient is
 records keep reading the whole rollout buffer (a stale observation is still a real observation).  `update()` reports `episodes_ended` = end.sum() of the epoch.
 On the GPU: include/trifinger_ppo_episode.h - one launch in place of the reward launch (`rollout_flags`), one in place of GAE (`gae_ends`), the weighted
 instantiation of the objective kernel reading (adv, w) interleaved, so that the gather still carries at most eight arrays.
+Episode tracking (`params.config.track_episodes`, off by default; `games_to_track` and `score_to_win` are RL-Games' keys): what an EPISODE is worth, in the
+statistics of every epoch.  The trainer resolves the engine once (an env without one is refused) and keeps an `evaluate.EpisodeTracker` on it.  After every env
+step of a rollout, per env i, from the engine's buffers: r = reward[i] (raw, before reward_scale), rb = reset_buf[i] != 0, s = steps[i] (after a step the number
+of steps taken in the current episode: s == 1 marks an episode's first step), and the cube and goal pose rows of `state`.  Per-env state `env_trk`, int32 [2][N],
+zero at construction: the bits of the running float32 return, and `armed`.
+    if s == 1: ret = r; armed = 1          else: ret = ret + r        (float32, step order)
+    if rb:
+        if armed:
+            e_p, e_o, pos_ok, ori_ok, at_goal(rule): the device functions and tolerances of the evaluator (include/trifinger_ppo_eval.h)
+            finite = ret, e_p, e_o and both quaternions finite
+            finite:     EPISODES += 1; SUCCESS += at_goal; POS_OK += pos_ok; ORI_OK += ori_ok; TIMEOUT += (episode_length > 0 and s >= episode_length);
+                        SUM_LENGTH += s; SUM_RETURN, SUM_POS_ERR, SUM_ORI_ERR += fixed point (2^16, 2^30, 2^28, the evaluator's clamps)
+            not finite: NONFINITE += 1
+        else: UNARMED += 1                 (an episode the tracker did not see from its first step: not counted)
+        ret = 0; armed = 0
+The accumulator is int64 [11] in that order - integers only, so the bits do not depend on the order of the workgroups or of the ranks.  The arming rule makes
+the tracker self-synchronising: after `restore()` and at the end of `evaluate()` `env_trk` is zeroed and every partial episode is discarded, with no protocol.
+On the GPU the tracker's launch (include/trifinger_ppo_track.h: `rollout_track`) stands where `rollout_reward` / `rollout_flags` stand and writes their bits: one
+launch per step either way; otherwise the torch statement runs behind the step.  `update()` takes the epoch's vector - one SUM all-reduce with a process group,
+counted in `n_track_allreduce` - and reads it with the other statistics at the end.  The WINDOW is the most recent epoch vectors with EPISODES > 0, newest
+first, taken whole until their EPISODES reach `games_to_track` (8192 envs that time out in step: the last epoch in which episodes ended).  Reported:
+`episode_return`, `episode_length`, `success_rate`, `pos_ok_rate`, `ori_ok_rate`, `timeout_rate`, `final_pos_err`, `final_ori_err` over the window (absent
+before any episode has ended: no NaN goes into a log), `episodes` (the window's count), and the cumulative `episodes_total`, `episodes_nonfinite`,
+`episodes_unarmed`.  `train()` then judges `<name>_best.pth` by `episode_return` and stops above `score_to_win` (its docstring).  Checkpoints carry the window and
+the cumulative counts; one written without tracking restores with an empty window and best_reward = -inf (a reward per step and an episode return are different
+units; likewise the other way round).  With the key off no tracker exists and every launch, buffer and statistic is what it was.
 
 This is host-side training glue, NOT part of the measured hot path.  On a GPU the minibatch step runs on the hand-written kernels of
 csrc/ppo_kernels.hip (leibnizgym_amd/ppo_kernels.py): one gather launch, the Linear / ELU layers on fp32 MFMA, the objective with all
@@ -125,6 +151,9 @@ class PPOConfig:
     lr_schedule: str = "adaptive"     # params.config.lr_schedule: adaptive | identity / None (constant) | linear (to 1e-6 at max_epochs, per epoch)
     episode_ends: bool = False        # params.config.episode_ends: GAE and the objective see the engine's episode ends (module docstring); off = the reference
     value_bootstrap: bool = False     # params.config.value_bootstrap (RL-Games' key): a time-out bootstraps from the final state's value; needs episode_ends
+    track_episodes: bool = False      # params.config.track_episodes: episode returns, lengths and success in the statistics (module docstring); off = as before
+    games_to_track: int = 100         # params.config.games_to_track (RL-Games' key): the episodes the reported window holds at least, once that many have ended
+    score_to_win: float = float("inf")    # params.config.score_to_win (RL-Games' key): train() stops when episode_return exceeds it; needs track_episodes
 
     def __post_init__(self):
         if self.value_bootstrap and not self.episode_ends:
@@ -162,7 +191,9 @@ class PPOConfig:
                   activation=activation_name(net["mlp"].get("activation", "elu"), "params.network.mlp.activation"),
                   d2rl=bool(net["mlp"].get("d2rl", False)), truncate_grads=bool(c.get("truncate_grads", True)),
                   lr_schedule=lr_schedule_name(c.get("lr_schedule", "adaptive")),
-                  episode_ends=bool(c.get("episode_ends", False)), value_bootstrap=bool(c.get("value_bootstrap", False)))
+                  episode_ends=bool(c.get("episode_ends", False)), value_bootstrap=bool(c.get("value_bootstrap", False)),
+                  track_episodes=bool(c.get("track_episodes", False)), games_to_track=int(c.get("games_to_track", 100)),
+                  score_to_win=float(c.get("score_to_win", float("inf"))))
         # without a central value network the critic takes the actor's keys
         kw.update(value_activation=kw["activation"], value_d2rl=kw["d2rl"], value_truncate_grads=kw["truncate_grads"])
         if cv:
@@ -606,6 +637,15 @@ class PPOTrainer:
             self.ends_engine = engine_of(env)
             self.ends_ep_len = int(getattr(getattr(self.ends_engine, "cfg", None), "episode_length", 0) or 0)
             self.last_end = torch.zeros(self.last[0].shape[0], device=self.device)
+        # `track_episodes`: the tracker on the engine behind the env (resolved once, like `episode_ends`: an env without one is refused by name), the
+        # window of epoch vectors (integers, time order) and the cumulative counts.  Off: none of it exists
+        self.tracker, self.track_window, self.track_totals = None, [], [0, 0, 0]       # totals: episodes, non-finite, unarmed
+        self.n_track_allreduce = 0
+        if c.track_episodes:
+            from .evaluate import EpisodeTracker, engine_of
+            eng = self.ends_engine if self.ends_engine is not None else engine_of(env)
+            fused_trk = bool(fk and eng.state.is_cuda)
+            self.tracker = EpisodeTracker(eng, fused=fused_trk)
         self.frames = 0
         self.epoch = 0
         self.last_info = {}
@@ -752,6 +792,8 @@ class PPOTrainer:
             sd["input_norm"] = {k: r.state_dict() for k, r in recs.items()}
         if self.value_norm is not None:                              # likewise
             sd["value_norm"] = self.value_norm.state_dict()
+        if self.tracker is not None:                                 # likewise: the window (integer vectors, time order) and the cumulative counts
+            sd["track"] = {"window": [list(v) for v in self.track_window], "totals": list(self.track_totals)}
         return sd
 
     def save(self, path: str):
@@ -794,6 +836,14 @@ class PPOTrainer:
         self.best_reward = float(ck.get("best_reward", -float("inf")))
         if self.last_end is not None:
             self.last_end.zero_()
+        trk = ck.get("track")
+        if (trk is not None) != (self.tracker is not None):          # best_reward is an episode return with tracking and a reward per step without: the
+            self.best_reward = -float("inf")                         # units differ, the best so far starts again
+        if self.tracker is not None:
+            self.tracker.reset_envs()                                # the env is where it is, not where the checkpoint's episodes were: they re-arm at their next first step
+            self.tracker.acc.zero_()
+            self.track_window = [[int(x) for x in v] for v in trk["window"]] if trk is not None else []
+            self.track_totals = [int(x) for x in trk["totals"]] if trk is not None else [0, 0, 0]
         return ck
 
     @torch.no_grad()
@@ -862,6 +912,8 @@ class PPOTrainer:
         self.last = self._unpack(self.env.reset())
         if self.last_end is not None:                        # every env starts a fresh episode: no sample of the next rollout is stale
             self.last_end.zero_()
+        if self.tracker is not None:                         # the evaluation's episodes are not the training run's: every env re-arms at its next first step
+            self.tracker.reset_envs()
         return res
 
     @staticmethod
@@ -888,6 +940,7 @@ class PPOTrainer:
                    act=torch.zeros(T, n, A, device=dev), nlp=torch.zeros(T, n, device=dev), val=torch.zeros(T + 1, n, device=dev),
                    rew=torch.zeros(T, n, device=dev), mu=torch.zeros(T, n, A, device=dev))
         ends, eng, ep_len = self.ends, self.ends_engine, self.ends_ep_len
+        trk = self.tracker                                   # `track_episodes`: its launch stands where rollout_flags / rollout_reward stand (one launch either way)
         if ends:                                             # `end` replaces `done` (module docstring)
             buf["end"], buf["tout"] = torch.zeros(T, n, device=dev), torch.zeros(T, n, device=dev)
         else:
@@ -904,7 +957,7 @@ class PPOTrainer:
                 buf["nlp"][t] = neglogp(a, mu, ls)
                 buf["val"][t] = val_t
             out, r, d, extra = self.env.step(a)
-            last_step = t == T - 1
+            last_step, tracked = t == T - 1, False
             # an env that DECLARES its buffers stable until its next step (`buffers_stable_until_next_step`: RlGamesGpuEnvAdapter hands out the
             # engine's own tensors) is read in place - they are filed above before the next step overwrites them, only what outlives the loop is cloned;
             # any other env gets a snapshot per step (it may refresh its observation asynchronously or on another stream)
@@ -917,17 +970,27 @@ class PPOTrainer:
                 rb, st = eng.reset_buf, eng.steps
                 if (fused and r.is_cuda and r.dtype == torch.float32 and r.is_contiguous() and rb.device == r.device and rb.dtype in (torch.bool, torch.uint8)
                         and rb.is_contiguous() and st.device == r.device and st.dtype == torch.int64 and st.is_contiguous()):
-                    pk.rollout_flags(r, rb, st, c.reward_scale, ep_len, buf["rew"][t], buf["end"][t], buf["tout"][t])
+                    if trk is not None and trk.fused and r.data_ptr() == eng.reward.data_ptr() and dev == r.device:
+                        trk.step_fused(c.reward_scale, buf["rew"][t], end_t=buf["end"][t], tout_t=buf["tout"][t])
+                        tracked = True
+                    else:
+                        pk.rollout_flags(r, rb, st, c.reward_scale, ep_len, buf["rew"][t], buf["end"][t], buf["tout"][t])
                 else:
                     buf["rew"][t] = r.to(dev) * c.reward_scale
                     buf["end"][t] = (rb != 0).to(dev).float()
                     if ep_len > 0:
                         buf["tout"][t] = (st >= ep_len).to(dev).float()
             elif fused and r.is_cuda and r.dtype == torch.float32 and r.is_contiguous() and d.is_cuda and d.dtype in (torch.bool, torch.uint8) and d.is_contiguous():
-                pk.rollout_reward(r, d, c.reward_scale, buf["rew"][t], buf["done"][t])
+                if trk is not None and trk.fused and r.data_ptr() == trk.engine.reward.data_ptr() and d.device == r.device and dev == r.device:
+                    trk.step_fused(c.reward_scale, buf["rew"][t], done=d, done_t=buf["done"][t])
+                    tracked = True
+                else:
+                    pk.rollout_reward(r, d, c.reward_scale, buf["rew"][t], buf["done"][t])
             else:
                 buf["rew"][t] = r.to(dev) * c.reward_scale
                 buf["done"][t] = d.to(dev).float()
+            if trk is not None and not tracked:             # the fused conditions do not hold: the tracker's own update (the torch statement on CPU tensors)
+                trk.update()
         buf["val"][T] = self.net.value(obs, states)
         self.last = (obs, states)
         vn = self.value_norm
@@ -1104,6 +1167,11 @@ class PPOTrainer:
             if self.fused_loss:                    # (adv_i, w_i) interleaved, stacked once per epoch: ONE gathered array, the gather keeps its eight
                 src["adv_w"] = torch.stack([adv, w], dim=1)
             ended = buf["end"].sum()               # device side; fetched with the other statistics below
+        if self.tracker is not None:               # the epoch's vector: summed over the ranks (ONE all-reduce), taken and cleared on the device; read below
+            if self.dist_on:
+                self.tracker.merge(self.group)
+                self.n_track_allreduce += 1
+            track_vec = self.tracker.take()
         total = T * n
         mb = max(1, total // c.minibatches)
         dev = src["obs"].device
@@ -1152,7 +1220,21 @@ class PPOTrainer:
         stats["mean_reward"] = float(buf["rew"].mean() / c.reward_scale)
         if self.ends:
             stats["episodes_ended"] = int(ended)
+        if self.tracker is not None:
+            stats.update(self._track_stats(track_vec.tolist()))
         return stats
+
+    def _track_stats(self, vec):
+        """file the epoch's vector (a list of integers, the same on every rank) and return the episode keys of the statistics: the window's means and rates
+        (absent before any episode has ended), its count `episodes`, and the cumulative counts"""
+        from .evaluate import EpisodeTracker, T_EPISODES, T_NONFINITE, T_UNARMED
+        for k, j in enumerate((T_EPISODES, T_NONFINITE, T_UNARMED)):
+            self.track_totals[k] += int(vec[j])
+        if int(vec[T_EPISODES]) > 0:
+            self.track_window = EpisodeTracker.window(self.track_window + [[int(x) for x in vec]], self.cfg.games_to_track)
+        out = EpisodeTracker.window_stats(self.track_window)
+        out["episodes_total"], out["episodes_nonfinite"], out["episodes_unarmed"] = self.track_totals
+        return out
 
     @torch.no_grad()
     def _update_value_norm(self, src, buf):
@@ -1208,22 +1290,29 @@ class PPOTrainer:
 
     def train(self, epochs, log=None, checkpoint_dir=None):
         """`epochs` PPO iterations.  With `checkpoint_dir` (rank 0 only): `<name>.pth` every `save_frequency` epochs and
-        at the end, `<name>_best.pth` whenever the mean reward improves after `save_best_after` epochs."""
+        at the end, `<name>_best.pth` whenever the mean reward improves after `save_best_after` epochs.  With `track_episodes` the best is judged by
+        `episode_return` once a window exists (RL-Games' criterion), and an `episode_return` above `score_to_win` saves `<name>.pth`, marks `won` in the
+        epoch's statistics and stops - on every rank in the same epoch, since every rank holds the all-reduced vector."""
         import os
         out = []
         for _ in range(epochs):
             st = self.update(self.rollout())
             self.epoch += 1
             st["epoch"], st["frames"] = self.epoch - 1, self.frames
+            if self.tracker is not None and st.get("episode_return", -float("inf")) > self.cfg.score_to_win:
+                st["won"] = True
             out.append(st)
             if log:
                 log(st)
             if checkpoint_dir:
                 if self.epoch % max(self.cfg.save_frequency, 1) == 0:
                     self.save(os.path.join(checkpoint_dir, f"{self.cfg.name}.pth"))
-                if self.epoch >= self.cfg.save_best_after and st["mean_reward"] > self.best_reward:
-                    self.best_reward = st["mean_reward"]
+                score = st["mean_reward"] if self.tracker is None else st.get("episode_return")
+                if self.epoch >= self.cfg.save_best_after and score is not None and score > self.best_reward:
+                    self.best_reward = score
                     self.save(os.path.join(checkpoint_dir, f"{self.cfg.name}_best.pth"))
+            if self.tracker is not None and st.get("episode_return", -float("inf")) > self.cfg.score_to_win:
+                break                                        # the final save below writes <name>.pth
             if self.epoch >= self.cfg.max_epochs:
                 break
         if checkpoint_dir:

@@ -104,6 +104,9 @@ def load():
         lib.tfp_ppo_loss_w.argtypes = lib.tfp_ppo_loss.argtypes
         lib.tfp_ppo_loss_vclip_w.restype = C.c_int
         lib.tfp_ppo_loss_vclip_w.argtypes = lib.tfp_ppo_loss_vclip.argtypes
+        # the training-time episode tracker (include/trifinger_ppo_track.h: csrc/tf_eval.hip), bound by symbol like the rest
+        lib.tfp_rollout_track.restype = C.c_int
+        lib.tfp_rollout_track.argtypes = [C.c_void_p, C.c_void_p]
         _LIB = lib
     return _LIB
 
@@ -473,6 +476,46 @@ def gae_ends(rew, end, tout, val, last_end, gamma, tau, value_bootstrap, mean_f=
                              adv.data_ptr(), ret.data_ptr(), w.data_ptr(), ret_n.data_ptr() if vnorm else None, v_old_n.data_ptr() if vnorm else None,
                              _stream(rew)), "tfp_gae_ends")
     return (adv, ret, w, ret_n, v_old_n) if vnorm else (adv, ret, w)
+
+
+# ---- the training-time episode tracker (include/trifinger_ppo_track.h; evaluate.EpisodeTracker, ppo.PPOTrainer with `track_episodes`) ---------------------
+TRACK_ENV_ROWS, TRACK_ACC = 2, 11
+
+
+class TfpTrackArgs(C.Structure):
+    """include/trifinger_ppo_track.h: TfpTrackArgs"""
+    _fields_ = [("state", C.c_void_p), ("reward", C.c_void_p), ("reset_buf", C.c_void_p), ("steps", C.c_void_p), ("done_bytes", C.c_void_p),
+                ("b_rew", C.c_void_p), ("b_done", C.c_void_p), ("b_end", C.c_void_p), ("b_tout", C.c_void_p), ("env_trk", C.c_void_p), ("acc", C.c_void_p),
+                ("episode_length", C.c_int64), ("scale", C.c_float), ("pos_tol", C.c_float), ("ori_tol", C.c_float), ("rule", C.c_int32), ("N", C.c_int32)]
+
+
+def rollout_track(state, reward, reset_buf, steps, env_trk, acc, scale, episode_length, pos_tol, ori_tol, rule, rew_t, done=None, done_t=None, end_t=None,
+                  tout_t=None):
+    """ONE launch behind an env step of a rollout, on torch's current stream (tfp_rollout_track): with `done` / `done_t` it stands where `rollout_reward`
+    does (rew_t = reward * scale, done_t = float(done)), with `end_t` / `tout_t` where `rollout_flags` does - the same bits -, and either way it updates the
+    tracker's per-env state `env_trk` (int32 [2, N]) and its accumulator `acc` (int64 [TRACK_ACC]) from the engine's buffers, which are only read.
+    No allocation, no synchronisation."""
+    n = reward.numel()
+    dev = reward.device
+    mode_a = done is not None
+    outs = (rew_t, done_t) if mode_a else (rew_t, end_t, tout_t)
+    assert reward.dtype == torch.float32 and reward.is_contiguous() and state.dtype == torch.float32 and state.is_contiguous() and state.shape[1] == n
+    assert reset_buf.dtype in (torch.bool, torch.uint8) and reset_buf.is_contiguous() and reset_buf.numel() == n
+    assert steps.dtype == torch.int64 and steps.is_contiguous() and steps.numel() == n
+    assert not mode_a or (done.dtype in (torch.bool, torch.uint8) and done.is_contiguous() and done.numel() == n and done.device == dev)
+    assert all(t is not None and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n and t.device == dev for t in outs)
+    assert env_trk.dtype == torch.int32 and env_trk.is_contiguous() and tuple(env_trk.shape) == (TRACK_ENV_ROWS, n)
+    assert acc.dtype == torch.int64 and acc.is_contiguous() and acc.numel() == TRACK_ACC
+    assert all(t.device == dev for t in (state, reset_buf, steps, env_trk, acc))
+    a = TfpTrackArgs()
+    a.state, a.reward, a.reset_buf, a.steps = state.data_ptr(), reward.data_ptr(), reset_buf.data_ptr(), steps.data_ptr()
+    a.done_bytes = done.data_ptr() if mode_a else None
+    a.b_rew = rew_t.data_ptr()
+    a.b_done = done_t.data_ptr() if mode_a else None
+    a.b_end, a.b_tout = (None, None) if mode_a else (end_t.data_ptr(), tout_t.data_ptr())
+    a.env_trk, a.acc = env_trk.data_ptr(), acc.data_ptr()
+    a.episode_length, a.scale, a.pos_tol, a.ori_tol, a.rule, a.N = int(episode_length), float(scale), float(pos_tol), float(ori_tol), int(rule), n
+    _chk(load().tfp_rollout_track(C.byref(a), _stream(reward)), "tfp_rollout_track")
 
 
 def gemm_tn_bias(a, b, y=None, chunk=256, out=None, defer=False):

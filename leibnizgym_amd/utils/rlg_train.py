@@ -215,6 +215,23 @@ class EnvInfoObserver(_AlgoObserver):
 LeibnizAlgoObserver = EnvInfoObserver            # the reference's name, for code written against it
 
 
+def episode_scalars(st, total_time):
+    """(tag, value, step) of the episode statistics of an epoch (`track_episodes`), under RL-Games' tags - rewards/* and episode_lengths/* over frames, epochs
+    and wall time - and info/* for the rest; nothing before the first window exists, so no NaN is logged"""
+    if "episode_return" not in st:
+        return []
+    axes = (("frame", st["frames"]), ("iter", st["epoch"]), ("time", total_time))
+    out = [(f"rewards/{a}", st["episode_return"], x) for a, x in axes] + [(f"episode_lengths/{a}", st["episode_length"], x) for a, x in axes]
+    return out + [(f"info/{k}", st[k], st["frames"]) for k in ("success_rate", "timeout_rate", "final_pos_err", "final_ori_err")]
+
+
+def episode_line(st):
+    """what the printed line of an epoch gains once a window of episodes exists"""
+    if "episode_return" not in st:
+        return ""
+    return f"  episode return {st['episode_return']:.3f} length {st['episode_length']:.1f} success {st['success_rate']:.3f} ({st['episodes']} episodes)"
+
+
 # ---- the in-repo runner behind RL-Games' Runner interface ------------------------------------------------------------------
 class NativeRunner:
     """`load(rlg) / reset() / run(args)` like `rl_games.torch_runner.Runner`, driving leibnizgym_amd.ppo.PPOTrainer on the
@@ -273,12 +290,14 @@ class NativeRunner:
             total_time = time.perf_counter() - t0
             for k in ("loss", "a_loss", "c_loss", "kl", "lr", "mean_reward"):
                 self.writer.add_scalar(f"losses/{k}" if k.endswith("loss") else f"info/{k}", st[k], st["frames"])
+            for tag, value, step in episode_scalars(st, total_time):
+                self.writer.add_scalar(tag, value, step)
             if self.observer is not None:
                 self.observer.process_infos([[], tr.last_info], [])
                 self.observer.after_print_stats(st["frames"], st["epoch"], total_time)
             if conf_print:
                 print(f"epoch {st['epoch']:5d} frames {st['frames']:11d} reward/step {st['mean_reward']:9.3f} kl {st['kl']:.4f} "
-                      f"lr {st['lr']:.2e}  {st['frames'] / total_time:.3e} frames/s", flush=True)
+                      f"lr {st['lr']:.2e}  {st['frames'] / total_time:.3e} frames/s{episode_line(st)}", flush=True)
         conf_print = bool(self.params["params"]["config"].get("print_stats", True))
         stats = tr.train(cfg.max_epochs, log, checkpoint_dir=os.path.join(args.get("logdir") or ".", "nn"))
         self.writer.close()

@@ -17,7 +17,7 @@ import torch  # noqa: E402
 from leibnizgym_amd.config import compose  # noqa: E402
 from leibnizgym_amd.envs import TrifingerEnv  # noqa: E402
 from leibnizgym_amd.ppo import PPOConfig, PPOTrainer  # noqa: E402
-from leibnizgym_amd.utils.rlg_train import RlGamesGpuEnvAdapter  # noqa: E402
+from leibnizgym_amd.utils.rlg_train import RlGamesGpuEnvAdapter, episode_line  # noqa: E402
 from leibnizgym_amd.wrappers import VecTaskPython  # noqa: E402
 
 
@@ -72,7 +72,7 @@ def main(argv):
             steady = (marks[-1][1] - back[1]) / max(now - back[0], 1e-9) if len(marks) > 1 else 0.0
             print(f"epoch {st['epoch']:4d} frames {st['frames'] * world:10d} reward/step {st['mean_reward']:9.3f} "
                   f"kl {st['kl']:.4f} lr {st['lr']:.2e} loss {st['loss']:.4f}  {st['frames'] * world / (now - t0):.3e} frames/s "
-                  f"since start, {steady:.3e} over the last {min(len(marks) - 1, 10)} epochs", flush=True)
+                  f"since start, {steady:.3e} over the last {min(len(marks) - 1, 10)} epochs{episode_line(st)}", flush=True)
     tr.train(epochs, log, checkpoint_dir=save_dir if rank == 0 else None)
     if world > 1 or launched:
         if rank == 0:
