@@ -16,6 +16,7 @@
 #include "tf_device_math.h"
 #include "../../include/trifinger_ppo_eval.h"
 #include "../../include/trifinger_ppo_track.h"
+#include "../../include/trifinger_ppo_record.h"
 
 #define EV_THREADS 256
 #define EV_WAVES (EV_THREADS / 64)
@@ -237,7 +238,115 @@ __global__ void __launch_bounds__(EV_THREADS) k_rollout_track(const TfpTrackArgs
     }
 }
 
+// ---- the episode flight recorder (include/trifinger_ppo_record.h): the launch behind every env step of an evaluation that records ----
+// One env per lane as above, the first W envs only.  A lane reads its STATE word; a frozen lane stops there.  An armed lane whose step is recorded loads
+// the 59 state rows of the record (coalesced lines of the SoA: a wavefront reads 256 bytes per row) into registers, an ending lane forms its final errors
+// with eval_errors from the same lines, a lane at its first step loads the 14 TF_S_DR rows - and only then does the lane store: the record into its slot
+// (unsigned)COUNT % L of the ring, the header, its env_rec words.  A lane that neither records nor ends loads none of the rows.  No index read from memory
+// is used unreduced.  A workgroup with nothing to count leaves at one __syncthreads_or; otherwise the four counters are ballots, the wavefronts meet in
+// LDS and the workgroup issues one 64-bit integer atomicAdd per non-zero counter.
+__global__ void __launch_bounds__(EV_THREADS) k_record_step(const TfpRecordArgs a) {
+    __shared__ long long s_part[EV_WAVES][TFP_REC_ACC];
+    const int t = threadIdx.x, i = (int)blockIdx.x * EV_THREADS + t, N = a.N, W = a.W;
+    bool rec = false, ended = false, froze = false, unarmed = false;
+    if (i < W) {
+        int* __restrict__ er = a.env_rec;
+        const int st = er[(size_t)TFP_REC_ENV_STATE * W + i];
+        if (st != TFP_REC_ST_FROZEN) {
+            const float* __restrict__ state = (const float*)a.state;
+            const long long s = a.steps[i];
+            const int s32 = (int)(s < 0 ? 0 : (s > 0x7FFFFFFF ? 0x7FFFFFFF : s));
+            const bool rb = ((const uint8_t*)a.reset_buf)[i] != 0;
+            const bool first = s == 1;
+            if (first || st == TFP_REC_ST_ARMED) {
+                const float r = a.reward[i];
+                const float ret = (first ? 0.0f : __int_as_float(er[(size_t)TFP_REC_ENV_RETURN * W + i])) + r;
+                const unsigned cnt = first ? 0u : (unsigned)er[(size_t)TFP_REC_ENV_COUNT * W + i];
+                rec = rb || (s32 - 1) % a.every == 0;
+                // ---- loads ----
+                float h[TF_NUM_DR], v[TFP_REC_STATE_ROWS];
+                if (first) {
+#pragma unroll
+                    for (int j = 0; j < TF_NUM_DR; ++j) h[j] = state[(size_t)(TF_S_DR + j) * N + i];
+                }
+                int outcome = 0;
+                float e_p = 0.0f, e_o = 0.0f;
+                if (rec) {
+#pragma unroll
+                    for (int j = 0; j < TFP_REC_STATE_ROWS; ++j) v[j] = state[(size_t)(TF_S_Q + j) * N + i];
+                    if (rb) {
+                        bool qfinite;
+                        eval_errors(state, N, i, e_p, e_o, qfinite);
+                        const bool pos_ok = e_p <= a.pos_tol, ori_ok = e_o <= a.ori_tol;
+                        const bool at_goal = a.rule == 0 ? pos_ok : (a.rule == 1 ? (pos_ok && ori_ok) : ori_ok);
+                        const bool fin = finite_f(ret) && finite_f(e_p) && finite_f(e_o) && qfinite;
+                        const bool tout = a.episode_length > 0 && s >= a.episode_length;
+                        outcome = (at_goal ? TFP_REC_OUT_AT_GOAL : 0) | (pos_ok ? TFP_REC_OUT_POS_OK : 0) | (ori_ok ? TFP_REC_OUT_ORI_OK : 0)
+                                  | (tout ? TFP_REC_OUT_TIMEOUT : 0) | (fin ? 0 : TFP_REC_OUT_NONFINITE);
+                        ended = true;
+                        froze = ((a.select & TFP_REC_SEL_FAILURE) && fin && !at_goal) || ((a.select & TFP_REC_SEL_SUCCESS) && fin && at_goal)
+                                || ((a.select & TFP_REC_SEL_NONFINITE) && !fin);
+                    }
+                }
+                // ---- stores ----
+                if (first) {
+#pragma unroll
+                    for (int j = 0; j < TF_NUM_DR; ++j) a.hdr[(size_t)j * W + i] = h[j];
+                }
+                if (rec) {
+                    float* __restrict__ slot = a.ring + (size_t)(cnt % (unsigned)a.L) * TFP_REC_ROWS * W + i;
+#pragma unroll
+                    for (int j = 0; j < TFP_REC_STATE_ROWS; ++j) slot[(size_t)j * W] = v[j];
+                    slot[(size_t)TFP_REC_REWARD * W] = r;
+                    slot[(size_t)TFP_REC_STEP * W] = __int_as_float(s32);
+                    er[(size_t)TFP_REC_ENV_COUNT * W + i] = (int)(cnt + 1u);
+                } else if (first) {
+                    er[(size_t)TFP_REC_ENV_COUNT * W + i] = 0;
+                }
+                er[(size_t)TFP_REC_ENV_RETURN * W + i] = __float_as_int(ret);
+                const int nst = ended ? (froze ? TFP_REC_ST_FROZEN : TFP_REC_ST_IDLE) : TFP_REC_ST_ARMED;
+                if (nst != st) er[(size_t)TFP_REC_ENV_STATE * W + i] = nst;
+                if (ended) {
+                    er[(size_t)TFP_REC_ENV_OUTCOME * W + i] = outcome;
+                    if (froze) {
+                        er[(size_t)TFP_REC_ENV_LENGTH * W + i] = s32;
+                        er[(size_t)TFP_REC_ENV_E_P * W + i] = __float_as_int(e_p);
+                        er[(size_t)TFP_REC_ENV_E_O * W + i] = __float_as_int(e_o);
+                    }
+                }
+            } else {
+                unarmed = rb;
+            }
+        }
+    }
+    if (!__syncthreads_or(rec || unarmed)) return;
+
+    // ---- a workgroup with something to count: uniform control flow ----
+    const int wave = t >> 6, lane = t & 63;
+    const long long c0 = wave_count(ended), c1 = wave_count(froze), c2 = wave_count(unarmed), c3 = wave_count(rec);
+    if (lane == 0) {
+        s_part[wave][TFP_REC_ENDED_ARMED] = c0; s_part[wave][TFP_REC_FROZEN] = c1; s_part[wave][TFP_REC_UNARMED] = c2; s_part[wave][TFP_REC_RECORDS] = c3;
+    }
+    __syncthreads();
+    if (t < TFP_REC_ACC) {
+        long long s = 0;
+#pragma unroll
+        for (int w = 0; w < EV_WAVES; ++w) s += s_part[w][t];
+        if (s != 0) atomicAdd((u64*)&a.acc[t], (u64)s);
+    }
+}
+
 extern "C" {
+
+int tfp_record_step(const TfpRecordArgs* args, void* stream) {
+    if (!args) return -1;
+    const TfpRecordArgs a = *args;
+    if (!a.state || !a.reward || !a.reset_buf || !a.steps || !a.ring || !a.hdr || !a.env_rec || !a.acc) return -1;
+    if (a.N < 1 || a.N > TF_MAX_ENVS || a.W < 1 || a.W > a.N || a.L < 1 || a.every < 1 || a.select < 1 || a.select > 7 || a.rule < 0 || a.rule > 2) return -1;
+    if (a.episode_length < 0 || a.pos_tol != a.pos_tol || a.ori_tol != a.ori_tol) return -1;
+    hipLaunchKernelGGL(k_record_step, dim3((unsigned)((a.W + EV_THREADS - 1) / EV_THREADS)), dim3(EV_THREADS), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
 
 int tfp_rollout_track(const TfpTrackArgs* args, void* stream) {
     if (!args) return -1;

@@ -595,6 +595,7 @@ class PPOTrainer:
         self.n_grad_allreduce = self.n_kl_allreduce = 0       # collectives issued so far (what a test of the distributed path counts)
         self.n_norm_allgather = 0
         self.n_eval_allreduce = 0
+        self.last_recording = None                           # the episodes the last evaluate(record=...) harvested (leibnizgym_amd/record.py)
         rank = 0
         try:
             import torch.distributed as dist
@@ -866,7 +867,7 @@ class PPOTrainer:
         return total / max(steps, 1), info
 
     @torch.no_grad()
-    def evaluate(self, episodes_per_env=1, deterministic=True, max_steps=None, pos_tol=None, ori_tol=None, check_every=32):
+    def evaluate(self, episodes_per_env=1, deterministic=True, max_steps=None, pos_tol=None, ori_tol=None, check_every=32, record=None):
         """Episode statistics of the current policy over `episodes_per_env` whole episodes of every env (leibnizgym_amd/evaluate.py: EpisodeStats, whose
         result dict this returns, with the number of env steps taken as "steps").  The env is reset first - every env starts at step 0, there are no
         partial episodes -, then stepped with the deterministic action (ActorCritic.mean_action) or with mu + sigma * randn, the statistics updated on the
@@ -875,7 +876,11 @@ class PPOTrainer:
         needs `max_steps` (ValueError).  Tolerances default to the env's.  With a process group the accumulators of all ranks are summed in one
         all-reduce (`n_eval_allreduce` counts them) and every rank returns the statistics of the whole population.
         Nothing of the trainer moves: no weight, no normalisation record, no counter (frames, epoch).  The env does: at the end it is reset again and
-        `self.last` is that fresh observation - TRAINING CONTINUES FROM A RESET, not from where the last rollout stopped."""
+        `self.last` is that fresh observation - TRAINING CONTINUES FROM A RESET, not from where the last rollout stopped.
+        `record`: None, or a dict (`select`, `every`, `length`, `watch`, `max_episodes`) - a flight recorder (leibnizgym_amd/record.py: EpisodeRecorder,
+        with the evaluation's tolerances) is updated behind the statistics, one more launch per step and no host synchronisation; at the end this rank's
+        selected episodes (at most `max_episodes`, ascending env id) are harvested into `self.last_recording` and the result gains
+        "episodes_recorded", their number.  With None no recorder exists: every launch, buffer and result key is as without the argument."""
         from .evaluate import EpisodeStats, engine_of
         k = int(episodes_per_env)
         if k < 1:
@@ -888,6 +893,17 @@ class PPOTrainer:
         if max_steps is not None:
             limit = min(limit, int(max_steps))
         stats = EpisodeStats(eng, pos_tol=pos_tol, ori_tol=ori_tol, max_episodes_per_env=k)
+        recorder = None
+        if record is not None:
+            from .record import EpisodeRecorder
+            unknown = sorted(set(record) - {"select", "every", "length", "watch", "max_episodes"})
+            if unknown:
+                raise ValueError(f"record: unknown key(s) {unknown}; known: select, every, length, watch, max_episodes")
+            length = record.get("length")
+            if length is None and ep_len <= 0:
+                length = limit // max(1, int(record.get("every", 1))) + 2          # no episode length: the ring takes the whole evaluation
+            recorder = EpisodeRecorder(eng, select=record.get("select", "failure"), every=record.get("every", 1), length=length,
+                                       watch=record.get("watch"), pos_tol=pos_tol, ori_tol=ori_tol)
         live = getattr(self.env, "buffers_stable_until_next_step", False)      # the observation is consumed before the next step overwrites it
 
         def obs_of(o):
@@ -900,6 +916,8 @@ class PPOTrainer:
             mu = self.net.mean_action(obs)
             out = self.env.step(mu if deterministic else mu + sigma * torch.randn_like(mu))[0]
             stats.update()
+            if recorder is not None:
+                recorder.update()
             obs = obs_of(out)
             steps += 1
             if steps % every == 0 and steps < limit and stats.envs_complete() == stats.num_envs:
@@ -909,6 +927,9 @@ class PPOTrainer:
             self.n_eval_allreduce += 1
         res = stats.result()
         res["steps"] = steps
+        if recorder is not None:
+            self.last_recording = recorder.take(record.get("max_episodes"))
+            res["episodes_recorded"] = len(self.last_recording)
         self.last = self._unpack(self.env.reset())
         if self.last_end is not None:                        # every env starts a fresh episode: no sample of the next rollout is stale
             self.last_end.zero_()

@@ -107,6 +107,9 @@ def load():
         # the training-time episode tracker (include/trifinger_ppo_track.h: csrc/tf_eval.hip), bound by symbol like the rest
         lib.tfp_rollout_track.restype = C.c_int
         lib.tfp_rollout_track.argtypes = [C.c_void_p, C.c_void_p]
+        # the episode flight recorder (include/trifinger_ppo_record.h: csrc/tf_eval.hip), bound by symbol like the rest
+        lib.tfp_record_step.restype = C.c_int
+        lib.tfp_record_step.argtypes = [C.c_void_p, C.c_void_p]
         _LIB = lib
     return _LIB
 
@@ -516,6 +519,42 @@ def rollout_track(state, reward, reset_buf, steps, env_trk, acc, scale, episode_
     a.env_trk, a.acc = env_trk.data_ptr(), acc.data_ptr()
     a.episode_length, a.scale, a.pos_tol, a.ori_tol, a.rule, a.N = int(episode_length), float(scale), float(pos_tol), float(ori_tol), int(rule), n
     _chk(load().tfp_rollout_track(C.byref(a), _stream(reward)), "tfp_rollout_track")
+
+
+# ---- the episode flight recorder (include/trifinger_ppo_record.h; record.EpisodeRecorder) -------------------------------------------------------------
+REC_STATE_ROWS, REC_ROWS, REC_ENV_ROWS, REC_ACC = 59, 61, 8, 4
+
+
+class TfpRecordArgs(C.Structure):
+    """include/trifinger_ppo_record.h: TfpRecordArgs"""
+    _fields_ = [("state", C.c_void_p), ("reward", C.c_void_p), ("reset_buf", C.c_void_p), ("steps", C.c_void_p), ("ring", C.c_void_p), ("hdr", C.c_void_p),
+                ("env_rec", C.c_void_p), ("acc", C.c_void_p), ("episode_length", C.c_int64), ("pos_tol", C.c_float), ("ori_tol", C.c_float),
+                ("N", C.c_int32), ("W", C.c_int32), ("L", C.c_int32), ("every", C.c_int32), ("select", C.c_int32), ("rule", C.c_int32)]
+
+
+def record_step(state, reward, reset_buf, steps, ring, hdr, env_rec, acc, every, select, episode_length, pos_tol, ori_tol, rule):
+    """ONE launch of the episode flight recorder behind an env step, on torch's current stream (tfp_record_step): reads the engine's buffers, writes the
+    caller's `ring` (float32 [L, REC_ROWS, W]), `hdr` (float32 [TF_NUM_DR, W]), `env_rec` (int32 [REC_ENV_ROWS, W]) and `acc` (int64 [REC_ACC]); the
+    ring's shape gives L and W.  No allocation, no synchronisation."""
+    n = reward.numel()
+    dev = reward.device
+    assert ring.dim() == 3 and ring.shape[1] == REC_ROWS
+    L, w = int(ring.shape[0]), int(ring.shape[2])
+    assert 1 <= w <= n and L >= 1
+    assert reward.dtype == torch.float32 and reward.is_contiguous() and state.dtype == torch.float32 and state.is_contiguous() and state.dim() == 2
+    assert state.shape[1] == n and state.shape[0] >= 98                                  # rows up to TF_S_DR + TF_NUM_DR are read
+    assert reset_buf.dtype in (torch.bool, torch.uint8) and reset_buf.is_contiguous() and reset_buf.numel() == n
+    assert steps.dtype == torch.int64 and steps.is_contiguous() and steps.numel() == n
+    assert ring.dtype == torch.float32 and ring.is_contiguous() and hdr.dtype == torch.float32 and hdr.is_contiguous() and tuple(hdr.shape) == (14, w)
+    assert env_rec.dtype == torch.int32 and env_rec.is_contiguous() and tuple(env_rec.shape) == (REC_ENV_ROWS, w)
+    assert acc.dtype == torch.int64 and acc.is_contiguous() and acc.numel() == REC_ACC
+    assert all(t.device == dev for t in (state, reset_buf, steps, ring, hdr, env_rec, acc))
+    a = TfpRecordArgs()
+    a.state, a.reward, a.reset_buf, a.steps = state.data_ptr(), reward.data_ptr(), reset_buf.data_ptr(), steps.data_ptr()
+    a.ring, a.hdr, a.env_rec, a.acc = ring.data_ptr(), hdr.data_ptr(), env_rec.data_ptr(), acc.data_ptr()
+    a.episode_length, a.pos_tol, a.ori_tol = int(episode_length), float(pos_tol), float(ori_tol)
+    a.N, a.W, a.L, a.every, a.select, a.rule = n, w, L, int(every), int(select), int(rule)
+    _chk(load().tfp_record_step(C.byref(a), _stream(reward)), "tfp_record_step")
 
 
 def gemm_tn_bias(a, b, y=None, chunk=256, out=None, defer=False):

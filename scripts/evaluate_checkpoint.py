@@ -3,12 +3,20 @@
 
     python scripts/evaluate_checkpoint.py gym=trifinger_difficulty_4 checkpoint=run/nn/trifinger.pth num_envs=8192 episodes_per_env=2
                                           [pos_tol=0.02] [ori_tol=0.2] [stochastic=1] [max_steps=N] [further overrides of the config tree]
+                                          [--record SELECT] [--record-max K] [--record-every E]
+                                          [--record-dir DIR] [--record-frames]
 
 The env is built the way scripts/train_ppo.py builds it, the checkpoint restored, every env run for `episodes_per_env` whole episodes under the
 deterministic action (stochastic=1: mu + sigma * noise), and the result printed as ONE JSON line: success rate at the end of an episode, final position and
 orientation error (mean, median and 90 % bins), episode return and length, time at the goal and time to reach it.  The network shape and the normalisation
 switches are taken from the checkpoint where it records them; everything else from the agent tree.  Launched by torch.distributed.run, every rank
-evaluates its shard and the statistics are summed over the ranks; rank 0 prints."""
+evaluates its shard and the statistics are summed over the ranks; rank 0 prints.
+
+With --record SELECT (failure, success, nonfinite, or a `|`-joined set such as "failure|nonfinite") the episodes that end as selected are captured on the device (leibnizgym_amd/record.py: the last steps of every env's current episode, frozen
+in place at a selected end) and every rank writes its first K of them (--record-max, ascending env id; default 16) to DIR/episodes.npz
+(DIR/episodes_rank<r>.npz in a distributed run; --record-dir, default "recordings"): numbers only, read back with leibnizgym_amd.record.load_npz.
+--record-every E keeps every E-th step and the final one.  With --record-frames the episodes are also rendered, one PNG per recorded step
+(DIR/ep<env>_<step>.png)."""
 import json
 import os
 import sys
@@ -29,8 +37,21 @@ SHAPE_KEYS = ("units", "activation", "value_activation", "d2rl", "value_d2rl", "
 
 def main(argv):
     own = {"checkpoint": None, "num_envs": None, "episodes_per_env": "1", "pos_tol": None, "ori_tol": None, "stochastic": "0", "max_steps": None}
-    rest = []
-    for a in argv:
+    rec = {"--record": None, "--record-max": "16", "--record-every": "1", "--record-dir": "recordings"}
+    frames, rest, argv = False, [], list(argv)
+    while argv:
+        a = argv.pop(0)
+        if a == "--record-frames":
+            frames = True
+            continue
+        flag, eq, val = a.partition("=")
+        if flag in rec:
+            if not eq:
+                if not argv:
+                    raise SystemExit(f"evaluate_checkpoint.py: {flag} needs a value")
+                val = argv.pop(0)
+            rec[flag] = val
+            continue
         key, _, val = a.partition("=")
         if key in own:
             own[key] = val
@@ -64,7 +85,21 @@ def main(argv):
     tr.restore(own["checkpoint"])
     res = tr.evaluate(episodes_per_env=int(own["episodes_per_env"]), deterministic=own["stochastic"] in ("0", "", "false", "False"),
                       max_steps=int(own["max_steps"]) if own["max_steps"] else None,
-                      pos_tol=float(own["pos_tol"]) if own["pos_tol"] else None, ori_tol=float(own["ori_tol"]) if own["ori_tol"] else None)
+                      pos_tol=float(own["pos_tol"]) if own["pos_tol"] else None, ori_tol=float(own["ori_tol"]) if own["ori_tol"] else None,
+                      record={"select": rec["--record"], "every": int(rec["--record-every"]), "max_episodes": int(rec["--record-max"])}
+                      if rec["--record"] else None)
+    if rec["--record"]:
+        from leibnizgym_amd import record as rc
+        path = os.path.join(rec["--record-dir"], "episodes.npz" if world == 1 else f"episodes_rank{rank}.npz")
+        rc.save_npz(path, tr.last_recording)
+        res["recording"] = path
+        if frames and tr.last_recording:
+            from leibnizgym_amd.render import SceneRenderer
+            renderer = SceneRenderer(env._engine.cfg.model, device=dev)
+            renderer.set_camera()
+            for ep in tr.last_recording:
+                rc.replay_frames(ep, renderer, out_dir=rec["--record-dir"])
+            renderer.close()
     res.update(checkpoint=own["checkpoint"], num_envs=world * n, epoch=tr.epoch, frames=tr.frames)
     if rank == 0:
         print(json.dumps(res), flush=True)
