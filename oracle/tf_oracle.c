@@ -294,9 +294,26 @@ struct TfHandle_ {
     int64_t timed_launches;
     float wall_s[3];                    /* slopes of the boundary profile between its knots */
     float wall_c[3], wall_sn[3];        /* cos and sin of the slope angle of each segment (fingertip - boundary contact) */
+#ifdef TF_FF_CENSUS
+    int32_t* census;                    /* tf_census_bind: one mask per env, substep() ORs TF_FFC_* bits into it, the caller clears it */
+#endif
 };
 
 static char g_err[256] = "";
+#ifdef TF_FF_CENSUS   /* developer build (make -C oracle census): the same arithmetic, plus a census of the finger-finger pre-pass - which of its rows were
+                       * live (lambda > 0) together in one substep, per env.  Single-threaded: g_census is the mask of the env being stepped. */
+enum { TF_FFC_D1 = 1 << 0,       /* a distal pair is live */
+       TF_FFC_D2 = 1 << 1,       /* two or more distal pairs: the later one sees the earlier one */
+       TF_FFC_M1 = 1 << 2,       /* a middle-distal row is live */
+       TF_FFC_M2 = 1 << 3,       /* two or more middle-distal rows */
+       TF_FFC_MB2 = 1 << 4,      /* << f: finger f is the distal side of two rows */
+       TF_FFC_OWN2 = 1 << 7,     /* << f: finger f owns (is the middle side of) two live rows */
+       TF_FFC_X = 1 << 10,       /* a finger is changed by a row of the first group (fd = fm + 2) and by one of the second */
+       TF_FFC_DM = 1 << 11,      /* a finger is changed by a distal pair and by a middle-distal row */
+       TF_FFC_M3 = 1 << 12 };    /* a finger is changed by three or more middle-distal rows */
+static int32_t* g_census = NULL;
+int tf_census_bind(tf_handle h, int32_t* mask) { if (!h) return TF_ERR_INVALID_ARG; h->census = mask; return TF_OK; }
+#endif
 
 int tf_api_version(void) { return TF_API_VERSION; }
 const char* tf_backend_name(void) { return "oracle-c"; }
@@ -1492,6 +1509,9 @@ static void substep(const struct TfHandle_* H, Env* e, float h) {
      * the finger contacts below measure their approach speeds on the velocities before this pass ---- */
     float vq_ff[3][3];
     for (int f = 0; f < 3; ++f) for (int j = 0; j < 3; ++j) vq_ff[f][j] = fr[f].vq[j];
+#ifdef TF_FF_CENSUS
+    int fc_nd = 0, fc_nm = 0, fc_d[3] = {0, 0, 0}, fc_mb[3] = {0, 0, 0}, fc_own[3] = {0, 0, 0}, fc_grp[3] = {0, 0, 0};
+#endif
     for (int p = 0; p < 3; ++p) {
         const int fa = p, fb = (p + 1) % 3;
         float Pa[3], Pb[3];
@@ -1524,6 +1544,9 @@ static void substep(const struct TfHandle_* H, Env* e, float h) {
         if (!contact_live(m, gap, vn0, h)) continue;
         float bias = contact_bias(m, gap, vn0, inv_h, rest_ff);
         float lam = f_max(-(vn0 + bias) * f_rcp2(dot3(Ja, Wa) + dot3(Jb, Wb)), 0.0f);
+#ifdef TF_FF_CENSUS
+        if (lam > 0.0f) { ++fc_nd; fc_d[fa] = 1; fc_d[fb] = 1; }
+#endif
         for (int j = 0; j < 3; ++j) { va[j] = FMA(Wa[j], lam, va[j]); vb[j] = FMA(-Wb[j], lam, vb[j]); }
     }
     /* ---- FF, second part (TfModel.ff_middle_pairs, on by default since API 8): the MIDDLE link of finger fm against the distal capsule of each other
@@ -1601,6 +1624,9 @@ static void substep(const struct TfHandle_* H, Env* e, float h) {
                 if (!contact_live(m, gap, vn0, h)) continue;
                 float bias = contact_bias(m, gap, vn0, inv_h, rest_ff);
                 float lam = f_max(-(vn0 + bias) * f_rcp2(dot3(Jd, Wd) + dot3(Jm, Wm)), 0.0f);
+#ifdef TF_FF_CENSUS
+                if (lam > 0.0f) { ++fc_nm; ++fc_mb[fd]; ++fc_own[fm]; fc_grp[fd] |= (o == 2) ? 1 : 2; fc_grp[fm] |= (o == 2) ? 1 : 2; }
+#endif
                 for (int j = 0; j < 3; ++j) {
                     const float dd = Wd[j] * lam, dm = Wm[j] * lam;
                     if (dd != 0.0f) vq_ff[fd][j] = vq_ff[fd][j] + dd;
@@ -1609,6 +1635,19 @@ static void substep(const struct TfHandle_* H, Env* e, float h) {
             }
         }
     }
+#ifdef TF_FF_CENSUS
+    if (g_census) {
+        int32_t bits = (fc_nd >= 1 ? TF_FFC_D1 : 0) | (fc_nd >= 2 ? TF_FFC_D2 : 0) | (fc_nm >= 1 ? TF_FFC_M1 : 0) | (fc_nm >= 2 ? TF_FFC_M2 : 0);
+        for (int f = 0; f < 3; ++f) {
+            if (fc_mb[f] >= 2) bits |= TF_FFC_MB2 << f;
+            if (fc_own[f] >= 2) bits |= TF_FFC_OWN2 << f;
+            if (fc_grp[f] == 3) bits |= TF_FFC_X;
+            if (fc_d[f] && fc_mb[f] + fc_own[f] >= 1) bits |= TF_FFC_DM;
+            if (fc_mb[f] + fc_own[f] >= 3) bits |= TF_FFC_M3;
+        }
+        *g_census |= bits;
+    }
+#endif
     /* ---- F2: contacts of each finger ---- */
     float cube_top_check = cpr[2];
     for (int f = 0; f < 3; ++f) {
@@ -2481,6 +2520,9 @@ static int run_step(tf_handle h, const float* action, int is_reset, int random_a
             for (int j = 0; j < 3; ++j) ST(h, TF_S_PREV_OBJ_P + j, i) = e.cp[j];   /* history[1] of the object */
             for (int j = 0; j < 4; ++j) ST(h, TF_S_PREV_OBJ_Q + j, i) = e.cq[j];
             for (int j = 0; j < 18; ++j) e.ft[j] = 0.0f;
+#ifdef TF_FF_CENSUS
+            g_census = h->census ? &h->census[i] : NULL;
+#endif
             for (int s = 0; s < nsim * c->substeps; ++s) substep(h, &e, hsub);
             post_step_env(h, i, &e, prev_obj, &rc, !is_reset, &local);
             goal_advance(h, &e, nsim * c->substeps, hsub);
@@ -2573,6 +2615,9 @@ int tf_simulate(tf_handle h, void* stream) {
     for (int i = 0; i < h->cfg.num_envs; ++i) {
         Env e;
         env_load(h, i, &e);
+#ifdef TF_FF_CENSUS
+        g_census = h->census ? &h->census[i] : NULL;
+#endif
         for (int s = 0; s < h->cfg.substeps; ++s) substep(h, &e, hsub);
         env_store(h, i, &e, 1);
     }

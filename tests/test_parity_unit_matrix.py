@@ -31,6 +31,10 @@ Every floor is HALF of the measured minimum (the rollouts are seeded: that leave
 lost its contacts); time-outs are exactly 2 x 130 = 260.  With domain randomisation the six factor rows must leave 1.0 and (action_repeat_prob 0.2 in
 every DR family) a non-zero applied torque must repeat bit for bit from one snapshot to the next at least half as often as measured.  If a floor is
 missed: change the seed or the placement, never the floor.
+
+What these rollouts do NOT reach: a census of the oracle (make -C oracle census) finds a live middle-distal finger-finger row in 3 .. 97 env-steps of
+every `step` rollout but NO substep with two of them in any - nothing in which the placement of those rows, the order of their additions or a second
+mailbox message could show.  That is pinned by tests/test_parity_ff_shared_finger.py: the same cells on rollouts of tangled finger poses.
 """
 import os
 import re
