@@ -25,6 +25,49 @@ DEV bool contact_live(const DevModel& m, float gap, float vn0, float h) {
     return (gap < m.contact_margin) && (gap < FMA(h, f_max(-vn0, 0.0f), m.contact_slack));
 }
 
+// ---- Link-speed gate of the middle-distal finger-finger rows (middle link of finger fm against the distal capsule of finger fd) ----
+// With n the unit normal, C_d the point of fd's capsule surface and C_m the point of fm's middle-link surface, vn0 = n.v(C_d) - n.v(C_m) in exact
+// arithmetic (Jd[j] = L_j . n_b, Jm[2] = 0), so -vn0 <= |v(C_d)| + |v(C_m)|.  The velocity field of a rigid link is affine in the position, so along a
+// chord its norm is convex: no point of the chord p3 - tip (distal) or p2 - p3 (middle) moves faster than the faster end.  A point of the distal axis
+// A + s (B - A) lies within (1 - s) |cap_a| of the chord point p3 + s (B - p3) (B IS the chord's end), the surface point cap_radius further; a point of
+// the middle axis lies within max(|a|, |b - j3_origin|) of the chord point p2 + s (p3 - p2), the surface point |ext| <= EXT_MAX further (EXT_MAX: rho +
+// |(w1 - rho, w2 - rho)| + |(o1, o2)| at the wider end; every term is linear in s and the sum of norms convex).  An offset d on a link adds at most
+// |omega| d with |omega| <= the sum of the |joint speeds| that move the link.  With |v(p2)| = |q'1| r2 <= |v(p3)| + |q'1| r2 (r2: the distance of the
+// joint-2 origin from the axis of joint 1, 17 mm) the middle chord needs only the speed of p3:
+//     s_dist = max(|v(p3)|, |v(B)|) + (|q'1| + |q'2| + |q'3|) kd,     s_mid = |v(p3)| + (|q'1| + |q'2|) km,
+//     kd = cap_radius + |cap_a| + 20 um,     km = EXT_MAX + max(|a|, |b - j3_origin|) + r2 + 20 um        (host: tf_create, rounded up)
+// on the FREE velocities the finger publishes (P_VQ: the ones the rows are solved on), and a row can be live only if gap < slack + h (s_dist + s_mid).
+// The two point speeds are formed in the frame of link 1 (the base frame turned by joint 1 about y; a rotation keeps norms): joint 1 is the y axis
+// through the origin, joints 2 and 3 are the x axis through p2 and p3, so y x P = (P_z, 0, -P_x) and x x r = (0, -r_z, r_y); p2 is the constant
+// j2_origin there.  r = Rx(q2) j3_origin and u = Rx(q2 + q3) cap_b are the products fk_setup and link_point<3> form (the compiler shares them).
+// fp32, and why the margin is the 20 um on the levers and nothing else: the kernels evaluate vn0 as dot3(Jd, vd) - dot3(Jm, vm), about 40 rounded
+// operations on terms of size at most |q'_j| |L_j| with levers below the finger's reach of 0.4 m: |vn0(fp32) - vn0| < 40 x 2^-24 x 0.4 m x sum |q'_j|
+// < 1 um x sum |q'_j|.  The bound's own evaluation (about 15 operations without cancellation - sums of squares and of absolute values - and a 1 ulp
+// square root) is off by less than 1e-6 of its value, which is below 0.5 m x sum |q'_j|: another 0.5 um x sum |q'_j|.  Both are terms in sum |q'_j|,
+// so they are paid as lever: 20 um covers their 1.5 um thirteen times over.  No relative factor and no absolute term are needed beside it, because
+// the gate is the SAME rounded expression as contact_live's second test - FMA(h, x, contact_slack) with x = s_dist + s_mid in the place of
+// max(-vn0, 0) - and a correctly rounded FMA is monotone in x; the gap is the very float contact_live tests.  A non-finite joint speed makes a sum
+// of absolute values, and with it the bound, NaN or +inf, and !(gap >= bound) true: the oracle does not skip such a lane, nor does the gate.
+DEV void ff_link_speeds(const DevParams& P, const FK& k, const float vq[3], float& s_dist, float& s_mid) {
+    const DevModel& m = P.m;
+    const float w = vq[0], a2 = vq[1], a23 = vq[1] + vq[2];
+    const float ry = FMA(k.c2, m.j3_origin[1], -(k.s2 * m.j3_origin[2])), rz = FMA(k.s2, m.j3_origin[1], k.c2 * m.j3_origin[2]);
+    const float uy = FMA(k.c23, m.cap_b[1], -(k.s23 * m.cap_b[2])), uz = FMA(k.s23, m.cap_b[1], k.c23 * m.cap_b[2]);
+    const float x3 = P.ffg_x3, z3 = m.j2_origin[2] + rz;      // p3 in the frame of link 1 (its y does not enter)
+    const float v3[3] = {w * z3, a2 * rz, FMA(a2, ry, -(w * x3))};                                              // v(p3), the sign of y dropped
+    const float vb[3] = {w * (z3 + uz), FMA(a23, uz, v3[1]), FMA(a23, uy, FMA(-w, m.cap_b[0], v3[2]))};      // v(B), likewise
+    // the faster end of the distal chord by the squares (v_sqrt_f32: 1 ulp; a denormal square counts as zero, 1e-19 m/s).  f_max drops a NaN
+    // operand; the sums of absolute joint speeds do not, and they cover every joint speed the squares are made of.
+    const float q3 = dot3(v3, v3), qb = dot3(vb, vb);
+    const float s12 = f_abs(w) + f_abs(a2);
+    s_dist = FMA(s12 + f_abs(vq[2]), P.ffg_kd, __builtin_amdgcn_sqrtf(f_max(q3, qb)));
+    s_mid = FMA(s12, P.ffg_km, __builtin_amdgcn_sqrtf(q3));
+}
+// can the row be live at all?  (the callers put it where gap < contact_margin stood, which contact_live repeats)
+DEV bool ff_gate(const DevModel& m, float gap, float s_dist, float s_mid, float h) {
+    return !(gap >= FMA(h, s_dist + s_mid, m.contact_slack));
+}
+
 // base-frame position of a point given in the frame of link LINK (1..3)
 template <int LINK> DEV void link_point(const FK& k, const float local[3], float out[3]) {
     float t[3];

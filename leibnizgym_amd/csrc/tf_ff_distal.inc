@@ -30,7 +30,7 @@
                         const int ff_ = side ? fb : fa;
                         const Yaw yy = {m.base_yaw_cos[ff_], m.base_yaw_sin[ff_], 0.0f, 0.0f, m.base_height};
                         FingerPubRegs pp;
-                        read_pub(lds, lane, ff_, pp);
+                        read_pub<WIDE>(m, lds, lane, ff_, pp);
                         float C[3], Cb_[3], L1[3], L2[3], L3[3], nb[3];
 #pragma unroll
                         for (int j = 0; j < 3; ++j) C[j] = side ? FMA(m.cap_radius, n[j], Pb[j]) : FMA(-m.cap_radius, n[j], Pa[j]);

@@ -78,6 +78,14 @@ struct DevParams {
     // obs/states offset and 1/range tables, action limits, PD gains (index = TAB_*).  Embedded so that every access
     // is a scalar load at a constant offset of the parameter block (a pointer member would be fetched per lane).
     float tables[TAB_FLOATS];
+    // (the fields below were added behind the tables: every older field keeps its offset, so the kernels that read none of them keep their code)
+    // constants of the link-speed gate of the middle-distal finger-finger rows (tf_contact.h: ff_link_speeds; filled by tf_create)
+    float ffg_x3;            // x of the joint-3 origin in the frame of link 1: j2_origin[0] + j3_origin[0]
+    float ffg_kd, ffg_km;    // what a unit of summed |joint speed| adds to the speed bound of the distal / middle link (metres)
+    // quotients of launch-invariant scalars, formed once by the host (tf_create) with the operations the 128-register kernels used to spend on them in every role
+    float inv_hsub;          // 1 / hsub
+    float inv_cube_mass;     // 1 / m.cube_mass: the kernels without domain randomisation (factor 1.0f)
+    float ffm_inv_j;         // f_rcp(j3_y^2 + j3_z^2) of the middle frame of the middle-distal rows
 };
 
 // what changes every launch travels by value; everything else is read through a pointer to constant

@@ -41,7 +41,12 @@ enum { M_ACT_IN = 1, M_RESETS = 2, M_TORQUE = 4, M_SIM = 8, M_POST = 16, M_FINIS
 #define P_MINV 6
 #define P_S1 12
 #define P_C1 13
-#define P_P2 14
+#define P_P2 14                         //   256-register kernels: p2
+#define P_GD 14                         //   128-register kernels: the link-speed gate of the middle-distal rows (tf_contact.h: ff_link_speeds) - bound on the speed
+#define P_GM 15                         //   of this finger's distal link, and of its middle link (p2 is two FMAs on s1, c1 there: read_pub; slot 16 is free).
+                                        //   Owned by the finger like the rest of the publication: written in front of S1, read by whoever builds a middle-distal
+                                        //   row before S1b.  The 256-register kernels keep the test gap < contact_margin: with one or two wavefronts per SIMD the
+                                        //   gate's values cost them more in front of S1 and in front of the ballot than the skipped blocks return.
 #define P_P3 17
 #define P_VQ 20                         //   -> 23 slots
 // cube pose and free velocity published by the cube role for contact generation (free tails of records 0 and 1)
@@ -387,14 +392,16 @@ DEV void tip_state(const DevModel& m, const Yaw& y, const FK& k, const float q[3
 // =====================================================================================================================
 // what a finger publishes after its free motion, as the registers of a reader (the finger-finger rows)
 struct FingerPubRegs { FK k; };
-DEV void read_pub(const float* lds, int lane, int f, FingerPubRegs& p) {
+template <bool WIDE>
+DEV void read_pub(const DevModel& m, const float* lds, int lane, int f, FingerPubRegs& p) {
     const int pb = L_REC(f);
 #pragma unroll
-    for (int j = 0; j < 3; ++j) { p.k.p2[j] = LD(pb + P_P2 + j); p.k.p3[j] = LD(pb + P_P3 + j); }
+    for (int j = 0; j < 3; ++j) { if (WIDE) p.k.p2[j] = LD(pb + P_P2 + j); p.k.p3[j] = LD(pb + P_P3 + j); }
 #pragma unroll
     for (int j = 0; j < 6; ++j) p.k.Minv[j] = LD(pb + P_MINV + j);
     p.k.s1 = LD(pb + P_S1); p.k.c1 = LD(pb + P_C1);
     p.k.ax[0] = p.k.c1; p.k.ax[1] = 0.0f; p.k.ax[2] = -p.k.s1;
+    if (!WIDE) rot_link<1>(p.k, m.j2_origin, p.k.p2);      // 128-register kernels (slots 14, 15 hold the gate's bounds there): the line of fk_setup on the same s1, c1 - the same bits
 }
 
 struct TipContact {            // fingertip sphere against one feature of the arena: finger-only rows
@@ -577,7 +584,7 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
     constexpr bool FT_IN_REGS = ((MODE & M_SIM) != 0) && ((MODE & M_POST) != 0);      // (in LDS, to be exact: the parking slots of the last substep)
     float k_ft[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};      // WIDE: the fingertip wrench accumulator, carried in registers through the substeps into the post phase
     if (MODE & M_SIM) {
-        const float h = P.hsub, inv_h = 1.0f / h;
+        const float h = P.hsub, inv_h = WIDE ? 1.0f / h : P.inv_hsub;      // (128-register kernels: the host's quotient - no division, no register)
         const int nsub = sa.nsim * P.substeps;
         float k_lam_fc[4] = {0.0f, 0.0f, 0.0f, 0.0f}, k_fc_link = 0.0f, k_lam_tf[3] = {0.0f, 0.0f, 0.0f}, k_lam_tw[3] = {0.0f, 0.0f, 0.0f};   // WIDE: carried in registers between substeps
         for (int s = 0; s < nsub; ++s) {
@@ -633,7 +640,7 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
             const float* tau = taus;
             const float cube_mass = m.cube_mass * dr[0];
             const float cube_inertia = m.cube_inertia * dr[0] * dr[1] * dr[1];
-            const float inv_m = 1.0f / cube_mass, inv_I = 1.0f / cube_inertia;
+            const float inv_m = (DR || WIDE) ? 1.0f / cube_mass : P.inv_cube_mass, inv_I = 1.0f / cube_inertia;      // (128-register kernels without domain randomisation: the mass is the model's - the host's quotient, the same bits)
             // per-body friction factors, robot base and stage offsets (neutral constants when the feature is off)
             const float fr1 = dr[TF_DR_FRICTION_ROBOT] - 1.0f, fo1 = dr[TF_DR_FRICTION_OBJECT] - 1.0f, fs1 = dr[TF_DR_FRICTION_STAGE] - 1.0f;
             const float mu_fc = (m.mu_finger_cube * dr[2]) * (EXT ? pair_factor(m.mu_robot, fr1, m.mu_object, fo1) : 1.0f);
@@ -665,6 +672,11 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
                 const float damp = 1.0f - h * m.link_angular_damping;
 #pragma unroll
                 for (int j = 0; j < 3; ++j) vq[j] = FMA(h, acc[j], qd[j]) * damp;
+                if (!WIDE && m.ff_middle_pairs != 0) {      // how fast this finger's distal and middle link can move at all: the gate of the middle-distal rows (tf_contact.h: ff_gate)
+                    float ffg_d, ffg_m;
+                    ff_link_speeds(P, k, vq, ffg_d, ffg_m);
+                    LD(L_REC(f) + P_GD) = ffg_d; LD(L_REC(f) + P_GM) = ffg_m;
+                }
                 float Ab[3], Bb[3], To[3];
                 link_point<3>(k, m.cap_a, Ab);
                 link_point<3>(k, m.cap_b, Bb);
@@ -674,7 +686,7 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
                 base_to_world(yw, To, Tw);
                 const int pb = L_REC(f);
 #pragma unroll
-                for (int j = 0; j < 3; ++j) { LD(pb + P_AW + j) = Aw[j]; LD(pb + P_BW + j) = Bw[j]; LD(pb + P_P2 + j) = k.p2[j]; LD(pb + P_P3 + j) = k.p3[j]; LD(pb + P_VQ + j) = vq[j]; }
+                for (int j = 0; j < 3; ++j) { LD(pb + P_AW + j) = Aw[j]; LD(pb + P_BW + j) = Bw[j]; if (WIDE) LD(pb + P_P2 + j) = k.p2[j]; LD(pb + P_P3 + j) = k.p3[j]; LD(pb + P_VQ + j) = vq[j]; }
 #pragma unroll
                 for (int j = 0; j < 6; ++j) LD(pb + P_MINV + j) = k.Minv[j];
                 LD(pb + P_S1) = k.s1; LD(pb + P_C1) = k.c1;
@@ -810,7 +822,7 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
             if (ffm_here && !HELP) {                                   // (HELP: wavefront 4 + f builds them, helper_role)
                 const TfLinkShape& sh = m.shape2;
                 const float jx = m.j3_origin[0], jy = m.j3_origin[1], jz = m.j3_origin[2];
-                const float inv_j = f_rcp(FMA(jy, jy, jz * jz));
+                const float inv_j = WIDE ? f_rcp(FMA(jy, jy, jz * jz)) : P.ffm_inv_j;      // (128-register kernels: formed once by the host with the same operations)
                 const float ex[3] = {k.c1, 0.0f, -k.s1};
                 float ey[3], aw[3], bw[3];
                 {
@@ -853,13 +865,17 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
                     const float o1 = FMA(sp, sh.o1[1] - sh.o1[0], sh.o1[0]), o2 = FMA(sp, sh.o2[1] - sh.o2[0], sh.o2[0]);
                     const float ext = FMA(o2, u2, FMA(o1, u1, FMA(h2, f_abs(u2), FMA(h1, f_abs(u1), rho))));
                     const float gap_ff = dist - ext - m.cap_radius;
-                    const bool near_ff = (dist2 > 1e-12f) && (gap_ff < m.contact_margin);
+                    // (the gate in the place of gap < contact_margin, which contact_live repeats; s_mid is this finger's own, re-read: no register across S1)
+                    const bool near_ff = WIDE ? ((dist2 > 1e-12f) && (gap_ff < m.contact_margin)) : (ff_gate(m, gap_ff, LD(L_REC(fd) + P_GD), LD(L_REC(f) + P_GM), h) && (dist2 > 1e-12f));
                     if (__builtin_amdgcn_ballot_w64(near_ff) != 0ull) {
                         float Jd[3], Wd[3], Jm[3], Wm[3], vd[3];
+                        // the record address of fd, formed again: left to itself the compiler keeps the one of the loads above in scratch and reloads it twice
+                        int fdn = fd;
+                        if (!WIDE) asm volatile("" : "+s"(fdn));
                         {   // distal side: the point of the capsule surface that faces the middle link
                             const Yaw yd = {m.base_yaw_cos[fd], m.base_yaw_sin[fd], 0.0f, 0.0f, m.base_height};
                             FingerPubRegs pd;
-                            read_pub(lds, lane, fd, pd);
+                            read_pub<WIDE>(m, lds, lane, fdn, pd);
                             float C[3], Cb_[3], L1[3], L2[3], L3[3], nb[3];
 #pragma unroll
                             for (int j = 0; j < 3; ++j) C[j] = FMA(-m.cap_radius, n[j], Pd[j]);
@@ -879,7 +895,7 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
                             sym3_mul(k.Minv, Jm, Wm);
                         }
 #pragma unroll
-                        for (int j = 0; j < 3; ++j) vd[j] = LD(L_REC(fd) + P_VQ + j);          // free velocities on both sides
+                        for (int j = 0; j < 3; ++j) vd[j] = LD(L_REC(fdn) + P_VQ + j);          // free velocities on both sides
                         const float vn0 = dot3(Jd, vd) - dot3(Jm, vq);
                         if (near_ff && contact_live(m, gap_ff, vn0, h)) {
                             const float bias = contact_bias(m, gap_ff, vn0, inv_h, rest_ff);
@@ -1437,7 +1453,7 @@ DEV void helper_role(const DevParams& P, const StepArgs& sa, float* lds, const C
                 for (int f = 0; f < 3; ++f) {
 #pragma unroll
                     for (int j = 0; j < 3; ++j) { Aw_[f][j] = LD(L_REC(f) + P_AW + j); Bw_[f][j] = LD(L_REC(f) + P_BW + j); vel[f][j] = LD(L_REC(f) + P_VQ + j); }
-                    read_pub(lds, lane, f, pp[f]);
+                    read_pub<true>(m, lds, lane, f, pp[f]);      // (<true>: the helper wavefronts exist in the 256-register kernels only, whose fingers publish p2 in slots 14 .. 16 and no gate bounds)
                 }
                 float gapp[3], Ja[3][3], Wa[3][3], Jb[3][3], Wb[3][3];
                 bool nearp[3];
@@ -1497,7 +1513,7 @@ DEV void helper_role(const DevParams& P, const StepArgs& sa, float* lds, const C
             } else if (m.ff_middle_pairs != 0) {
                 const float rest_ff = m.restitution_ff * (DR ? LD(L_HELP_DR + fm) : TF_DR_NEUTRAL(5));
                 FingerPubRegs pm;
-                read_pub(lds, lane, fm, pm);
+                read_pub<true>(m, lds, lane, fm, pm);
                 const float ex[3] = {pm.k.c1, 0.0f, -pm.k.s1};
                 float ey[3], aw[3], bw[3], vm[3];
                 {
@@ -1547,7 +1563,7 @@ DEV void helper_role(const DevParams& P, const StepArgs& sa, float* lds, const C
                         {   // distal side: the point of the capsule surface that faces the middle link
                             const Yaw yd = {m.base_yaw_cos[fd], m.base_yaw_sin[fd], 0.0f, 0.0f, m.base_height};
                             FingerPubRegs pd;
-                            read_pub(lds, lane, fd, pd);
+                            read_pub<true>(m, lds, lane, fd, pd);
                             float C[3], Cb_[3], L1[3], L2[3], L3[3], nb[3];
 #pragma unroll
                             for (int j = 0; j < 3; ++j) C[j] = FMA(-m.cap_radius, n[j], Pd[j]);
@@ -1869,7 +1885,7 @@ DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restri
     // =================================================================================================================
     STAMP(2);
     if (MODE & M_SIM) {
-        const float h = P.hsub, inv_h = 1.0f / h;
+        const float h = P.hsub, inv_h = WIDE ? 1.0f / h : P.inv_hsub;
         const int nsub = sa.nsim * P.substeps;
         // The cube role carries the serial chain of the solve (every row depends on the one before it); the finger roles
         // of the other workgroups on this SIMD only fill its issue gaps.  Without a raised priority the older finger
@@ -1891,7 +1907,7 @@ DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restri
             const float* dr = drs;
             const float cube_mass = m.cube_mass * dr[0];
             const float cube_inertia = m.cube_inertia * dr[0] * dr[1] * dr[1];
-            const float inv_m = 1.0f / cube_mass, inv_I = 1.0f / cube_inertia;
+            const float inv_m = (DR || WIDE) ? 1.0f / cube_mass : P.inv_cube_mass, inv_I = 1.0f / cube_inertia;      // (128-register kernels without domain randomisation: the mass is the model's - the host's quotient, the same bits)
             const float fr1 = dr[TF_DR_FRICTION_ROBOT] - 1.0f, fo1 = dr[TF_DR_FRICTION_OBJECT] - 1.0f, fs1 = dr[TF_DR_FRICTION_STAGE] - 1.0f;
             const float mu_fc = (m.mu_finger_cube * dr[2]) * (EXT ? pair_factor(m.mu_robot, fr1, m.mu_object, fo1) : 1.0f);
             const float mu_cf = (m.mu_cube_floor * dr[2]) * (EXT ? pair_factor(m.mu_object, fo1, m.mu_floor, fs1) : 1.0f);
@@ -1982,13 +1998,13 @@ DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restri
             if (!WIDE && m.ff_middle_pairs != 0) {
                 const TfLinkShape& sh = m.shape2;
                 const float jx = m.j3_origin[0], jy = m.j3_origin[1], jz = m.j3_origin[2];
-                const float inv_j = f_rcp(FMA(jy, jy, jz * jz));
+                const float inv_j = P.ffm_inv_j;                    // f_rcp(jy jy + jz jz), formed once by the host with the same operations (this block: 128-register kernels only)
 #pragma unroll 1
                 for (int o_ = 2; o_ >= (BOXK ? 1 : 2); --o_)
 #pragma unroll 1
                 for (int fm = 0; fm < 3; ++fm) {
                     FingerPubRegs pm;
-                    read_pub(lds, lane, fm, pm);
+                    read_pub<WIDE>(m, lds, lane, fm, pm);
                     const Yaw ym = {m.base_yaw_cos[fm], m.base_yaw_sin[fm], 0.0f, 0.0f, m.base_height};
                     const float ex[3] = {pm.k.c1, 0.0f, -pm.k.s1};
                     float ey[3], aw[3], bw[3];
@@ -2030,12 +2046,13 @@ DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restri
                         const float o1 = FMA(sp, sh.o1[1] - sh.o1[0], sh.o1[0]), o2 = FMA(sp, sh.o2[1] - sh.o2[0], sh.o2[0]);
                         const float ext = FMA(o2, u2, FMA(o1, u1, FMA(h2, f_abs(u2), FMA(h1, f_abs(u1), rho))));
                         const float gap = dist - ext - m.cap_radius;
-                        if ((dist2 > 1e-12f) && (gap < m.contact_margin)) {
+                        // the link-speed gate (tf_contact.h: ff_gate) in the place of gap < contact_margin, which contact_live repeats
+                        if ((dist2 > 1e-12f) && ff_gate(m, gap, LD(L_REC(fd) + P_GD), LD(L_REC(fm) + P_GM), h)) {
                             float Jd[3], Wd[3], Jm[3], Wm[3], vd[3], vm[3];
                             {   // distal side: the point of the capsule surface that faces the middle link
                                 const Yaw yd = {m.base_yaw_cos[fd], m.base_yaw_sin[fd], 0.0f, 0.0f, m.base_height};
                                 FingerPubRegs pd;
-                                read_pub(lds, lane, fd, pd);
+                                read_pub<WIDE>(m, lds, lane, fd, pd);
                                 float C[3], Cb_[3], L1[3], L2[3], L3[3], nb[3];
 #pragma unroll
                                 for (int j = 0; j < 3; ++j) C[j] = FMA(-m.cap_radius, n[j], Pd[j]);

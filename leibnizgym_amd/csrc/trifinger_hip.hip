@@ -436,6 +436,39 @@ int tf_create(const TfConfig* cfg, tf_handle* out) {
         P.wall_c[i] = (float)(1.0 / sqrt(1.0 + sl * sl));
         P.wall_sn[i] = (float)(sl / sqrt(1.0 + sl * sl));
     }
+    {   // quotients the kernels used to form in every role (tf_params.h): the same IEEE operations on the same floats, hence the same bits
+        const TfModel& cm = cfg->model;
+        P.inv_hsub = 1.0f / P.hsub;
+        P.inv_cube_mass = 1.0f / cm.cube_mass;
+        const float jy = cm.j3_origin[1], jz = cm.j3_origin[2];
+        const float x = fmaf(jy, jy, jz * jz);                    // f_rcp (tf_device_math.h) on the host
+        uint32_t xb, rb;
+        memcpy(&xb, &x, 4);
+        rb = 0x7EF311C7u - xb;
+        float r;
+        memcpy(&r, &rb, 4);
+        for (int it = 0; it < 3; ++it) r = fmaf(r, fmaf(-x, r, 1.0f), r);
+        P.ffm_inv_j = r;
+    }
+    {   // link-speed gate of the middle-distal rows (tf_contact.h: ff_link_speeds): model constants, rounded up
+        // (tools/experiments/ff_gate_census.patch restates these lines and ff_link_speeds in C for the census on the oracle: change them together)
+        const TfModel& cm = cfg->model;
+        auto norm3 = [](double x, double y, double z) { return sqrt(x * x + y * y + z * z); };
+        const TfLinkShape& s2 = cm.shape2;
+        double ext_max = 0.0;                              // largest reach of the middle link's cross-section from its axis
+        for (int e = 0; e < 2; ++e) {
+            const double h1 = (double)s2.w1[e] - (double)s2.rho[e], h2 = (double)s2.w2[e] - (double)s2.rho[e];
+            const double r = fabs((double)s2.rho[e]) + sqrt(h1 * h1 + h2 * h2) + sqrt((double)s2.o1[e] * s2.o1[e] + (double)s2.o2[e] * s2.o2[e]);
+            ext_max = r > ext_max ? r : ext_max;
+        }
+        const double off_a = norm3(s2.a[0], s2.a[1], s2.a[2]);
+        const double off_b = norm3((double)s2.b[0] - cm.j3_origin[0], (double)s2.b[1] - cm.j3_origin[1], (double)s2.b[2] - cm.j3_origin[2]);
+        const double r2 = sqrt((double)cm.j2_origin[0] * cm.j2_origin[0] + (double)cm.j2_origin[2] * cm.j2_origin[2]);
+        const double up = 1.0 + 1e-6;                      // the float conversions below must not round a bound down
+        P.ffg_x3 = cm.j2_origin[0] + cm.j3_origin[0];
+        P.ffg_kd = (float)(up * (fabs((double)cm.cap_radius) + norm3(cm.cap_a[0], cm.cap_a[1], cm.cap_a[2]) + 2e-5));
+        P.ffg_km = (float)(up * (ext_max + (off_a > off_b ? off_a : off_b) + r2 + 2e-5));
+    }
     void* tk = nullptr;
     e = hipMalloc(&tk, STAT_WORDS * sizeof(unsigned long long));
     if (e != hipSuccess) { delete h; return hip_fail(e, "hipMalloc(tickets)"); }
