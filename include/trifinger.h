@@ -93,8 +93,9 @@ enum {
     TF_S_TAU = 50,       /*  9 applied joint torque (what set_dof_actuation_force_tensor received) */
     TF_S_PREV_OBJ_P = 59,/*  3 object position of history[1]: the pose the step's physics started from */
     TF_S_PREV_OBJ_Q = 62,/*  4 object orientation of history[1]                                   */
-    TF_S_FT = 66,        /* 18 fingertip contact wrench (world frame force 3 + torque 3 per finger about
-                              the tip-link origin, mean over the substeps of the step); split path only */
+    TF_S_FT = 66,        /* 18 fingertip contact wrench accumulator: world frame force 3 + torque 3 per finger, on the fingertip,
+                              about the tip-link origin, SUMMED over the substeps since tf_pre_step zeroed it (tf_post_step
+                              divides by substeps x control_decimation and rotates into the tip-link frame); split path only */
     TF_S_DR = 84,        /* 14 per-env domain-randomisation values drawn at reset (index list: TF_DR_* below): scale factors
                               (1.0 when DR is off) for cube mass, cube size, contact friction, motor torque, finger link
                               mass, finger contact restitution; offsets in metres (0.0 when off) of the robot base (x, y, z)
@@ -109,7 +110,8 @@ enum {
     TF_S_LAM_TF = 113,   /*  9 fingertip-floor contact of finger f at [3f..3f+2]: normal, tangent 1, tangent 2       */
     TF_S_LAM_TW = 122,   /*  9 fingertip-boundary-wall contact of finger f, same layout                             */
     TF_S_LAM_CF = 131,   /* 12 cube corner i against the floor at [3i..3i+2]: +z (normal), +x, +y                   */
-    TF_S_CF_FACE = 143,  /*  1 cube face whose corners those were (0 none, 1..6)                                   */
+    TF_S_CF_FACE = 143,  /*  1 cube face whose corners those were: 1..6, the lowest face after every substep whether or not the
+                          *    floor pushes (a corner that does not push has zero impulses); 0 only after a reset            */
     TF_S_LAM_CW = 144,   /* 12 cube corner i against the boundary wall at [3i..3i+2]: normal, tangent, +z; with TfModel.cube_wall_surface
                           *    on, a corner above wall_z[0] holds the tilted normal (c n_h, s), the horizontal tangent and the UP-SLOPE
                           *    tangent (-s n_h, c) in place of +z (on the vertical ring the two models coincide)                       */

@@ -122,8 +122,10 @@ def check_torque(lib, device):
 def check_obs(lib, device):
     """T5: obs[41|50] / states[113|122] assembly + scale tables, for the slots that are inputs of the
     native step (q, qd, object pose/vel, goal, last action, dof force).  Fingertip slots are produced by
-    the build's own FK and are checked in test_physics_analytic.py; here they are compared after
-    re-normalising the FK tips with the golden scale table."""
+    the build's own FK: test_privileged_state.py checks the whole block (position, orientation, both
+    velocities, three fingers) and the wrench slots against fp64 physics, test_physics_analytic.py the tip
+    position of finger 0 in its base frame; here they are compared after re-normalising the FK tips with the
+    golden scale table."""
     g = golden("obs")
     n = g["q"].shape[0]
     for mode in ("torque", "position", "position_impedance"):

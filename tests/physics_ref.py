@@ -123,6 +123,20 @@ def point_jacobian(f, q, link, world_point):
     return J
 
 
+def tip_state_ref(f, q, qd):
+    """fp64 state of finger f's tip link in the world: (position of its origin, rotation matrix, linear velocity of the origin, angular velocity).
+    The velocities are derivatives of the forward kinematics along qd: the point Jacobian for the origin, the central difference of the rotation
+    (W = dR/dt R^T, w its axial vector) for the spin."""
+    q, qd = np.asarray(q, dtype=np.float64), np.asarray(qd, dtype=np.float64)
+    p = link_point_world(f, q, 3, MF.TIP)
+    R = link_rotation_world(f, q, 3)
+    v = point_jacobian(f, q, 3, p) @ qd
+    eps = 1e-6
+    W = (link_rotation_world(f, q + eps * qd, 3) - link_rotation_world(f, q - eps * qd, 3)) / (2 * eps) @ R.T
+    w = 0.5 * np.array([W[2, 1] - W[1, 2], W[0, 2] - W[2, 0], W[1, 0] - W[0, 1]])
+    return p, R, v, w
+
+
 def bias_forces(q, qd, gravity_z):
     """h(q, qd) = Mdot qd - 1/2 d(qd^T M qd)/dq + dV/dq, every derivative numerical."""
     eps = 1e-5
