@@ -860,53 +860,6 @@ __global__ void __launch_bounds__(256) k_rollout_reward(const float* __restrict_
     b_rew[i] = r[i] * scale;
     b_done[i] = d[i] ? 1.0f : 0.0f;
 }
-// generalised advantage estimation, one thread per env walking its T steps backwards; every product and sum rounded separately in the order of the torch
-// loop it replaces (8 launches per step of the horizon): nd = 1 - done; delta = (rew + (gamma val[t+1]) nd) - val[t]; last = delta + ((gamma tau) nd) last
-__global__ void __launch_bounds__(256) k_gae(const float* __restrict__ rew, const float* __restrict__ done, const float* __restrict__ val, float gamma, float gamma_tau,
-                                             int T, int n, float* __restrict__ adv, float* __restrict__ ret) {
-#pragma clang fp contract(off)
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    float last = 0.0f;
-    for (int t = T - 1; t >= 0; --t) {
-        const float nd = 1.0f - done[(size_t)t * n + i], v0 = val[(size_t)t * n + i];
-        const float gv = gamma * val[(size_t)(t + 1) * n + i], gvn = gv * nd, s1 = rew[(size_t)t * n + i] + gvn, delta = s1 - v0;
-        const float gn = gamma_tau * nd, gl = gn * last;
-        last = delta + gl;
-        adv[(size_t)t * n + i] = last;
-        ret[(size_t)t * n + i] = last + v0;
-    }
-}
-// `normalize_value` (include/trifinger_ppo_value.h): k_gae on values the network emits in NORMALISED units.  y [T + 1, n] is its raw output; the value of
-// a step is v = clamp(y, -clip, clip) / inv_std + mean (quotient and sum rounded separately), GAE runs on v with the operations of k_gae in their order, and
-// next to adv and ret (reward units) the thread files what the minibatches regress on and clip around: ret_n = clamp((ret - mean) * inv_std, -clip, clip) and
-// v_old_n = clamp(y[t], -clip, clip).  mean / inv_std: the record's published floats, read from the device (no host value enters the launch).
-__device__ __forceinline__ float clampf_nan(float x, float c) { return x < -c ? -c : (x > c ? c : x); }     // torch.clamp: a NaN stays a NaN
-__global__ void __launch_bounds__(256) k_gae_vnorm(const float* __restrict__ rew, const float* __restrict__ done, const float* __restrict__ y,
-                                                   const float* __restrict__ mean_f, const float* __restrict__ inv_std_f, float clip, float gamma, float gamma_tau,
-                                                   int T, int n, float* __restrict__ adv, float* __restrict__ ret, float* __restrict__ ret_n, float* __restrict__ v_old_n) {
-#pragma clang fp contract(off)
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float mean = mean_f[0], inv = inv_std_f[0];
-    float last = 0.0f;
-    const float yT = clampf_nan(y[(size_t)T * n + i], clip), qT = yT / inv;
-    float v1 = qT + mean;                                     // the value of step t + 1
-    for (int t = T - 1; t >= 0; --t) {
-        const float yc = clampf_nan(y[(size_t)t * n + i], clip), q = yc / inv, v0 = q + mean;
-        const float nd = 1.0f - done[(size_t)t * n + i];
-        const float gv = gamma * v1, gvn = gv * nd, s1 = rew[(size_t)t * n + i] + gvn, delta = s1 - v0;
-        const float gn = gamma_tau * nd, gl = gn * last;
-        last = delta + gl;
-        const float r = last + v0, rm = r - mean, rs = rm * inv;
-        adv[(size_t)t * n + i] = last;
-        ret[(size_t)t * n + i] = r;
-        ret_n[(size_t)t * n + i] = clampf_nan(rs, clip);
-        v_old_n[(size_t)t * n + i] = yc;
-        v1 = v0;
-    }
-}
-
 // ---- `episode_ends` (include/trifinger_ppo_episode.h): the rollout sees the engine's episode ends ----
 // k_rollout_reward with the engine's own buffers in place of the public `done`: rew[t] = r * scale, end[t] = float(reset_buf != 0),
 // tout[t] = float(episode_length > 0 and steps >= episode_length).  reset_buf: one byte per env; steps: int64.  The engine's buffers are only read.
@@ -920,18 +873,23 @@ __global__ void __launch_bounds__(256) k_rollout_flags(const float* __restrict__
     b_end[i] = reset_buf[i] ? 1.0f : 0.0f;
     b_tout[i] = (episode_length > 0 && steps[i] >= episode_length) ? 1.0f : 0.0f;
 }
-// k_gae / k_gae_vnorm with episode ends, one thread per env, every operation rounded separately in the order of ppo.gae_with_ends:
-//   term = end (1 - tout) with BOOT, end otherwise;  w[t] = 1 - end[t-1], w[0] = 1 - last_end
-//   cont = 1 - end;  boot = 1 - term;  delta = (rew + (gamma val[t+1]) boot) - val[t];  last = delta + ((gamma tau) cont) last
-//   adv = last w;  ret = adv + val[t]
-// With end = 0 and last_end = 0 every factor is 1.0f and the outputs are the bits of k_gae / k_gae_vnorm.  VNORM: val is the network's raw output y and
-// the value of a step clamp(y, -clip, clip) / inv_std_f + mean_f; ret_n and v_old_n as in k_gae_vnorm, from the masked ret.
-template <bool VNORM>
-__global__ void __launch_bounds__(256) k_gae_ends(const float* __restrict__ rew, const float* __restrict__ end, const float* __restrict__ tout,
-                                                  const float* __restrict__ val, const float* __restrict__ last_end, int boot_on,
-                                                  const float* __restrict__ mean_f, const float* __restrict__ inv_std_f, float clip, float gamma, float gamma_tau,
-                                                  int T, int n, float* __restrict__ adv, float* __restrict__ ret, float* __restrict__ w,
-                                                  float* __restrict__ ret_n, float* __restrict__ v_old_n) {
+// generalised advantage estimation, one thread per env walking its T steps backwards, every operation rounded separately in the order of ppo.gae_spec
+// (the torch loop it replaces costs 8 launches per step of the horizon).  ONE kernel, four instantiations:
+//   cont = 1 - end[t];  boot = 1 - term[t];  delta = (rew + (gamma val[t+1]) boot) - val[t];  last = delta + ((gamma tau) cont) last
+//   ENDS (`episode_ends`, include/trifinger_ppo_episode.h):  term = end (1 - tout) with `boot_on`, end otherwise;  w[t] = 1 - end[t-1], w[0] = 1 - last_end;
+//         adv = last w;  ret = adv + val[t].  With end = 0 and last_end = 0 every factor is 1.0f and the outputs are the bits of the instantiation without ENDS.
+//   without ENDS: `end` holds the rollout's `done` rows, term = end, adv = last; tout, last_end and w are not touched.
+//   VNORM (`normalize_value`, include/trifinger_ppo_value.h): val is the network's raw output y [T + 1, n] in NORMALISED units; the value of a step is
+//         v = clamp(y, -clip, clip) / inv_std + mean (quotient and sum rounded separately), and next to adv and ret (reward units) the thread files what the
+//         minibatches regress on and clip around: ret_n = clamp((ret - mean) * inv_std, -clip, clip) and v_old_n = clamp(y[t], -clip, clip).  mean / inv_std:
+//         the record's published floats, read from the device (no host value enters the launch).
+__device__ __forceinline__ float clampf_nan(float x, float c) { return x < -c ? -c : (x > c ? c : x); }     // torch.clamp: a NaN stays a NaN
+template <bool ENDS, bool VNORM>
+__global__ void __launch_bounds__(256) k_gae(const float* __restrict__ rew, const float* __restrict__ end, const float* __restrict__ tout,
+                                             const float* __restrict__ val, const float* __restrict__ last_end, int boot_on,
+                                             const float* __restrict__ mean_f, const float* __restrict__ inv_std_f, float clip, float gamma, float gamma_tau,
+                                             int T, int n, float* __restrict__ adv, float* __restrict__ ret, float* __restrict__ w,
+                                             float* __restrict__ ret_n, float* __restrict__ v_old_n) {
 #pragma clang fp contract(off)
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -940,29 +898,33 @@ __global__ void __launch_bounds__(256) k_gae_ends(const float* __restrict__ rew,
     float last = 0.0f;
     float v1 = val[(size_t)T * n + i];                           // the value of step t + 1
     if constexpr (VNORM) { const float yT = clampf_nan(v1, clip), qT = yT / inv; v1 = qT + mean; }
-    float e0 = end[(size_t)(T - 1) * n + i];                     // end[t]
+    float e1 = 0.0f;                                             // ENDS: end[t], carried from the step that read it as end[t - 1]
+    if constexpr (ENDS) e1 = end[(size_t)(T - 1) * n + i];
     for (int t = T - 1; t >= 0; --t) {
         float yc = val[(size_t)t * n + i], v0 = yc;
         if constexpr (VNORM) { yc = clampf_nan(yc, clip); const float q = yc / inv; v0 = q + mean; }
-        const float ep = t > 0 ? end[(size_t)(t - 1) * n + i] : last_end[i];      // end[t - 1]
-        const float wt = 1.0f - ep, cont = 1.0f - e0;
+        float e0 = e1, ep = 0.0f;                                // end[t], end[t - 1]
+        if constexpr (ENDS) ep = t > 0 ? end[(size_t)(t - 1) * n + i] : last_end[i];
+        else e0 = end[(size_t)t * n + i];
+        const float cont = 1.0f - e0;
         float term = e0;
-        if (boot_on) { const float om = 1.0f - tout[(size_t)t * n + i]; term = e0 * om; }
+        if constexpr (ENDS) { if (boot_on) { const float om = 1.0f - tout[(size_t)t * n + i]; term = e0 * om; } }
         const float boot = 1.0f - term;
         const float gv = gamma * v1, gvn = gv * boot, s1 = rew[(size_t)t * n + i] + gvn, delta = s1 - v0;
         const float gn = gamma_tau * cont, gl = gn * last;
         last = delta + gl;
-        const float a = last * wt, r = a + v0;
+        float a = last;
+        if constexpr (ENDS) { const float wt = 1.0f - ep; a = last * wt; w[(size_t)t * n + i] = wt; }
+        const float r = a + v0;
         adv[(size_t)t * n + i] = a;
         ret[(size_t)t * n + i] = r;
-        w[(size_t)t * n + i] = wt;
         if constexpr (VNORM) {
             const float rm = r - mean, rs = rm * inv;
             ret_n[(size_t)t * n + i] = clampf_nan(rs, clip);
             v_old_n[(size_t)t * n + i] = yc;
         }
         v1 = v0;
-        e0 = ep;
+        e1 = ep;
     }
 }
 
@@ -981,6 +943,16 @@ __global__ void __launch_bounds__(256) k_sum_partials_multi(SumArgs sa) {
     for (int z = 0; z < sa.splits[k]; ++z) s += part[(size_t)z * tot + i];
     const int r = i / (N2 + 1), c = i - r * (N2 + 1);
     if (c < N2) sa.gw[k][(size_t)r * N2 + c] = s; else sa.gb[k][r] = s;
+}
+
+// the four instantiations of k_gae behind the three entry points
+template <bool ENDS, bool VNORM>
+static int launch_gae(const float* rew, const float* end, const float* tout, const float* val, const float* last_end, int boot_on, const float* mean_f,
+                      const float* inv_std_f, float clip, float gamma, float gamma_tau, int T, int n, float* adv, float* ret, float* w, float* ret_n,
+                      float* v_old_n, void* stream) {
+    hipLaunchKernelGGL((k_gae<ENDS, VNORM>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rew, end, tout, val, last_end, boot_on, mean_f,
+                       inv_std_f, clip, gamma, gamma_tau, T, n, adv, ret, w, ret_n, v_old_n);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
 extern "C" {
@@ -1014,15 +986,12 @@ int tfp_rollout_reward(const float* r, const void* done_bytes, float scale, int3
 }
 int tfp_gae(const float* rew, const float* done, const float* val, float gamma, float gamma_tau, int32_t T, int32_t n, float* adv, float* ret, void* stream) {
     if (n <= 0 || T <= 0) return -1;
-    hipLaunchKernelGGL(k_gae, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rew, done, val, gamma, gamma_tau, T, n, adv, ret);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_gae<false, false>(rew, done, nullptr, val, nullptr, 0, nullptr, nullptr, 0.0f, gamma, gamma_tau, T, n, adv, ret, nullptr, nullptr, nullptr, stream);
 }
 int tfp_gae_vnorm(const float* rew, const float* done, const float* y, const float* mean_f, const float* inv_std_f, float clip, float gamma, float gamma_tau,
                   int32_t T, int32_t n, float* adv, float* ret, float* ret_n, float* v_old_n, void* stream) {
     if (n <= 0 || T <= 0 || !mean_f || !inv_std_f || !(clip > 0.0f)) return -1;
-    hipLaunchKernelGGL(k_gae_vnorm, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rew, done, y, mean_f, inv_std_f, clip, gamma, gamma_tau, T, n,
-                       adv, ret, ret_n, v_old_n);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_gae<false, true>(rew, done, nullptr, y, nullptr, 0, mean_f, inv_std_f, clip, gamma, gamma_tau, T, n, adv, ret, nullptr, ret_n, v_old_n, stream);
 }
 // include/trifinger_ppo_episode.h
 int tfp_rollout_flags(const float* r, const void* reset_bytes, const int64_t* steps, float scale, int64_t episode_length, int32_t n, float* b_rew, float* b_end,
@@ -1039,15 +1008,9 @@ int tfp_gae_ends(const float* rew, const float* end, const float* tout, const fl
     const bool vnorm = mean_f != nullptr;
     if (vnorm != (inv_std_f != nullptr)) return -1;
     if (vnorm && (!(clip > 0.0f) || !ret_n || !v_old_n)) return -1;
-    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
     const int boot_on = value_bootstrap ? 1 : 0;
-    if (vnorm)
-        hipLaunchKernelGGL((k_gae_ends<true>), grid, block, 0, (hipStream_t)stream, rew, end, tout, val, last_end, boot_on, mean_f, inv_std_f, clip, gamma, gamma_tau,
-                           T, n, adv, ret, w, ret_n, v_old_n);
-    else
-        hipLaunchKernelGGL((k_gae_ends<false>), grid, block, 0, (hipStream_t)stream, rew, end, tout, val, last_end, boot_on, mean_f, inv_std_f, clip, gamma, gamma_tau,
-                           T, n, adv, ret, w, ret_n, v_old_n);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return vnorm ? launch_gae<true, true>(rew, end, tout, val, last_end, boot_on, mean_f, inv_std_f, clip, gamma, gamma_tau, T, n, adv, ret, w, ret_n, v_old_n, stream)
+                 : launch_gae<true, false>(rew, end, tout, val, last_end, boot_on, mean_f, inv_std_f, clip, gamma, gamma_tau, T, n, adv, ret, w, ret_n, v_old_n, stream);
 }
 // the products of tfp_gemm_tn_partials summed for n <= 8 layers in one launch (fixed order over the chunks: deterministic)
 int tfp_sum_partials_multi(const void* const* part, void* const* gw, void* const* gb, const int32_t* splits, const int32_t* n1, const int32_t* n2,

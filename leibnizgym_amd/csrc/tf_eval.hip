@@ -59,6 +59,52 @@ DEV long long wave_sum_ll(long long v) {
 }
 DEV long long wave_count(bool p) { return (long long)__popcll(__ballot(p)); }
 
+// THE episode outcome of env i, stated once for the evaluator, the tracker and the recorder (evaluate.episode_outcome is the same statement in torch):
+// the final errors, the two predicates, the at-goal rule (0 position, 1 both, 2 orientation) and the finite test of an episode whose return is `ret`.
+// The caller decides which lanes load the 14 pose rows by deciding which lanes call.  `fin` takes the return when it is asked, not when the pose is
+// loaded: the evaluator loads its running return behind the pose rows, and two loads held across them would cost k_eval_step two registers.
+struct Outcome {
+    float e_p, e_o;
+    bool pos_ok, ori_ok, at_goal, pose_finite;
+    DEV bool fin(float ret) const { return finite_f(ret) && pose_finite; }
+};
+DEV Outcome episode_outcome(const float* __restrict__ state, int N, int i, float pos_tol, float ori_tol, int rule) {
+    Outcome o;
+    bool qfinite;
+    eval_errors(state, N, i, o.e_p, o.e_o, qfinite);
+    o.pos_ok = o.e_p <= pos_tol;
+    o.ori_ok = o.e_o <= ori_tol;
+    o.at_goal = rule == 0 ? o.pos_ok : (rule == 1 ? (o.pos_ok && o.ori_ok) : o.ori_ok);
+    o.pose_finite = finite_f(o.e_p) && finite_f(o.e_o) && qfinite;
+    return o;
+}
+// the fixed point of the three sums of a COUNTED episode: 2^16 (return, clamped to +-2^25), 2^30 (position error, to 2^10), 2^28 (orientation error, to 4);
+// zeros otherwise.  Finite: the clamps see no NaN, the products are exact, the conversions defined
+DEV void fixed_sums(bool counted, float ret, float e_p, float e_o, long long& q_ret, long long& q_pos, long long& q_ori) {
+    q_ret = q_pos = q_ori = 0;
+    if (counted) {
+        q_ret = __float2ll_rn(f_clamp(ret, -33554432.0f, 33554432.0f) * 65536.0f);
+        q_pos = __float2ll_rn(f_min(e_p, 1024.0f) * 1073741824.0f);
+        q_ori = __float2ll_rn(f_min(e_o, 4.0f) * 268435456.0f);
+    }
+}
+// per-wavefront values v[K] of a 256-thread workgroup -> LDS -> ONE 64-bit integer atomicAdd per non-zero entry (two's complement: a negative sum adds as
+// it should).  Uniform control flow: every thread of the workgroup calls; the barrier inside also orders whatever LDS the caller wrote before the call
+template <int K>
+DEV void block_add(const long long (&v)[K], long long (&s_part)[EV_WAVES][K], u64* __restrict__ acc, int t) {
+    if ((t & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) s_part[t >> 6][k] = v[k];
+    }
+    __syncthreads();
+    if (t < K) {
+        long long s = 0;
+#pragma unroll
+        for (int w = 0; w < EV_WAVES; ++w) s += s_part[w][t];
+        if (s != 0) atomicAdd(&acc[t], (u64)s);
+    }
+}
+
 __global__ void __launch_bounds__(EV_THREADS) k_eval_step(const EvalArgs a) {
     __shared__ long long s_part[EV_WAVES][EV_SCALARS];
     __shared__ int s_hist[EV_BINS];
@@ -69,11 +115,8 @@ __global__ void __launch_bounds__(EV_THREADS) k_eval_step(const EvalArgs a) {
     int atg = 0, first = 0;
     long long len = 0;
     if (valid) {
-        bool qfinite;
-        eval_errors(a.state, N, i, e_p, e_o, qfinite);
-        pos_ok = e_p <= a.pos_tol;
-        ori_ok = e_o <= a.ori_tol;
-        at_goal = a.rule == 0 ? pos_ok : (a.rule == 1 ? (pos_ok && ori_ok) : ori_ok);
+        const Outcome o = episode_outcome(a.state, N, i, a.pos_tol, a.ori_tol, a.rule);
+        e_p = o.e_p; e_o = o.e_o; pos_ok = o.pos_ok; ori_ok = o.ori_ok; at_goal = o.at_goal;
         int* __restrict__ ea = a.env_acc;
         ret = __int_as_float(ea[(size_t)TFP_EVAL_ENV_RETURN * N + i]) + a.reward[i];
         atg = ea[(size_t)TFP_EVAL_ENV_AT_GOAL_STEPS * N + i] + (at_goal ? 1 : 0);
@@ -85,7 +128,7 @@ __global__ void __launch_bounds__(EV_THREADS) k_eval_step(const EvalArgs a) {
         goal_ev = under && a.goal_reset_buf[i] != 0;
         ends = a.reset_buf[i] != 0;
         if (ends) {
-            const bool fin = finite_f(ret) && finite_f(e_p) && finite_f(e_o) && qfinite;
+            const bool fin = o.fin(ret);
             counted = under && fin;
             nonfin = under && !fin;
             complete = under && a.cap != 0 && eps + 1 == a.cap;
@@ -103,7 +146,6 @@ __global__ void __launch_bounds__(EV_THREADS) k_eval_step(const EvalArgs a) {
     if (!__syncthreads_or((ends && (counted || nonfin)) || goal_ev)) return;      // the barrier also publishes the zeroed histogram
 
     // ---- a workgroup with something to report: everything below is uniform control flow ----
-    const int wave = t >> 6, lane = t & 63;
     long long v[EV_SCALARS];
     v[TFP_EVAL_EPISODES] = wave_count(counted);
     v[TFP_EVAL_NONFINITE] = wave_count(nonfin);
@@ -113,11 +155,9 @@ __global__ void __launch_bounds__(EV_THREADS) k_eval_step(const EvalArgs a) {
     v[TFP_EVAL_REACHED] = wave_count(counted && first != 0);
     v[TFP_EVAL_GOAL_EVENTS] = wave_count(goal_ev);
     v[TFP_EVAL_ENVS_COMPLETE] = wave_count(complete);
-    long long q_ret = 0, q_pos = 0, q_ori = 0;
-    if (counted) {                                   // finite: the clamps see no NaN, the products are exact, the conversions defined
-        q_ret = __float2ll_rn(f_clamp(ret, -33554432.0f, 33554432.0f) * 65536.0f);
-        q_pos = __float2ll_rn(f_min(e_p, 1024.0f) * 1073741824.0f);
-        q_ori = __float2ll_rn(f_min(e_o, 4.0f) * 268435456.0f);
+    long long q_ret, q_pos, q_ori;
+    fixed_sums(counted, ret, e_p, e_o, q_ret, q_pos, q_ori);
+    if (counted) {
         atomicAdd(&s_hist[hist_bin(e_p, TFP_EVAL_POS_Q_LO, TFP_EVAL_POS_Q_HI)], 1);
         atomicAdd(&s_hist[TFP_EVAL_POS_BINS + hist_bin(e_o, TFP_EVAL_ORI_Q_LO, TFP_EVAL_ORI_Q_HI)], 1);
     }
@@ -127,17 +167,8 @@ __global__ void __launch_bounds__(EV_THREADS) k_eval_step(const EvalArgs a) {
     v[TFP_EVAL_SUM_RETURN] = wave_sum_ll(q_ret);
     v[TFP_EVAL_SUM_POS_ERR] = wave_sum_ll(q_pos);
     v[TFP_EVAL_SUM_ORI_ERR] = wave_sum_ll(q_ori);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < EV_SCALARS; ++k) s_part[wave][k] = v[k];
-    }
-    __syncthreads();
-    if (t < EV_SCALARS) {
-        long long s = 0;
-#pragma unroll
-        for (int w = 0; w < EV_WAVES; ++w) s += s_part[w][t];
-        if (s != 0) atomicAdd(&a.acc[t], (u64)s);                       // two's complement: a negative return sum adds as it should
-    } else if (t >= 64 && t < 64 + EV_BINS) {                           // another wavefront takes the bins
+    block_add(v, s_part, a.acc, t);
+    if (t >= 64 && t < 64 + EV_BINS) {                                  // another wavefront than the scalars' takes the bins
         const int b = t - 64, c = s_hist[b];
         if (c != 0) atomicAdd(&a.acc[TFP_EVAL_HIST_POS + b], (u64)c);
     }
@@ -148,11 +179,9 @@ __global__ void __launch_bounds__(EV_THREADS) k_eval_predicates(const float* __r
     const int i = (int)blockIdx.x * EV_THREADS + (int)threadIdx.x;
     bool pos_ok = false, ori_ok = false;
     if (i < N) {
-        float e_p, e_o;
-        bool qfinite;
-        eval_errors(state, N, i, e_p, e_o, qfinite);
-        pos_ok = e_p <= pos_tol;
-        ori_ok = e_o <= ori_tol;
+        const Outcome o = episode_outcome(state, N, i, pos_tol, ori_tol, 0);
+        pos_ok = o.pos_ok;
+        ori_ok = o.ori_ok;
     }
     const long long np = wave_count(pos_ok), no = wave_count(ori_ok);
     if ((threadIdx.x & 63) == 0) {
@@ -198,15 +227,11 @@ __global__ void __launch_bounds__(EV_THREADS) k_rollout_track(const TfpTrackArgs
     bool counted = false, nonfin = false, pos_ok = false, ori_ok = false, at_goal = false;
     float e_p = 0.0f, e_o = 0.0f;
     if (ends && armed) {
-        bool qfinite;
-        eval_errors((const float*)a.state, N, i, e_p, e_o, qfinite);
-        pos_ok = e_p <= a.pos_tol;
-        ori_ok = e_o <= a.ori_tol;
-        at_goal = a.rule == 0 ? pos_ok : (a.rule == 1 ? (pos_ok && ori_ok) : ori_ok);
-        counted = finite_f(ret) && finite_f(e_p) && finite_f(e_o) && qfinite;
+        const Outcome o = episode_outcome((const float*)a.state, N, i, a.pos_tol, a.ori_tol, a.rule);
+        e_p = o.e_p; e_o = o.e_o; pos_ok = o.pos_ok; ori_ok = o.ori_ok; at_goal = o.at_goal;
+        counted = o.fin(ret);
         nonfin = !counted;
     }
-    const int wave = t >> 6, lane = t & 63;
     long long v[TFP_TRACK_ACC];
     v[TFP_TRACK_EPISODES] = wave_count(counted);
     v[TFP_TRACK_SUCCESS] = wave_count(counted && at_goal);
@@ -215,27 +240,13 @@ __global__ void __launch_bounds__(EV_THREADS) k_rollout_track(const TfpTrackArgs
     v[TFP_TRACK_TIMEOUT] = wave_count(counted && tout);
     v[TFP_TRACK_NONFINITE] = wave_count(nonfin);
     v[TFP_TRACK_UNARMED] = wave_count(ends && !armed);
-    long long q_ret = 0, q_pos = 0, q_ori = 0;
-    if (counted) {                                   // finite: the clamps see no NaN, the products are exact, the conversions defined
-        q_ret = __float2ll_rn(f_clamp(ret, -33554432.0f, 33554432.0f) * 65536.0f);
-        q_pos = __float2ll_rn(f_min(e_p, 1024.0f) * 1073741824.0f);
-        q_ori = __float2ll_rn(f_min(e_o, 4.0f) * 268435456.0f);
-    }
+    long long q_ret, q_pos, q_ori;
+    fixed_sums(counted, ret, e_p, e_o, q_ret, q_pos, q_ori);
     v[TFP_TRACK_SUM_LENGTH] = wave_sum_ll(counted ? len : 0);
     v[TFP_TRACK_SUM_RETURN] = wave_sum_ll(q_ret);
     v[TFP_TRACK_SUM_POS_ERR] = wave_sum_ll(q_pos);
     v[TFP_TRACK_SUM_ORI_ERR] = wave_sum_ll(q_ori);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < TFP_TRACK_ACC; ++k) s_part[wave][k] = v[k];
-    }
-    __syncthreads();
-    if (t < TFP_TRACK_ACC) {
-        long long s = 0;
-#pragma unroll
-        for (int w = 0; w < EV_WAVES; ++w) s += s_part[w][t];
-        if (s != 0) atomicAdd((u64*)&a.acc[t], (u64)s);                 // two's complement: a negative return sum adds as it should
-    }
+    block_add(v, s_part, (u64*)a.acc, t);
 }
 
 // ---- the episode flight recorder (include/trifinger_ppo_record.h): the launch behind every env step of an evaluation that records ----
@@ -275,16 +286,14 @@ __global__ void __launch_bounds__(EV_THREADS) k_record_step(const TfpRecordArgs 
 #pragma unroll
                     for (int j = 0; j < TFP_REC_STATE_ROWS; ++j) v[j] = state[(size_t)(TF_S_Q + j) * N + i];
                     if (rb) {
-                        bool qfinite;
-                        eval_errors(state, N, i, e_p, e_o, qfinite);
-                        const bool pos_ok = e_p <= a.pos_tol, ori_ok = e_o <= a.ori_tol;
-                        const bool at_goal = a.rule == 0 ? pos_ok : (a.rule == 1 ? (pos_ok && ori_ok) : ori_ok);
-                        const bool fin = finite_f(ret) && finite_f(e_p) && finite_f(e_o) && qfinite;
+                        const Outcome o = episode_outcome(state, N, i, a.pos_tol, a.ori_tol, a.rule);
+                        const bool fin = o.fin(ret);
+                        e_p = o.e_p; e_o = o.e_o;
                         const bool tout = a.episode_length > 0 && s >= a.episode_length;
-                        outcome = (at_goal ? TFP_REC_OUT_AT_GOAL : 0) | (pos_ok ? TFP_REC_OUT_POS_OK : 0) | (ori_ok ? TFP_REC_OUT_ORI_OK : 0)
+                        outcome = (o.at_goal ? TFP_REC_OUT_AT_GOAL : 0) | (o.pos_ok ? TFP_REC_OUT_POS_OK : 0) | (o.ori_ok ? TFP_REC_OUT_ORI_OK : 0)
                                   | (tout ? TFP_REC_OUT_TIMEOUT : 0) | (fin ? 0 : TFP_REC_OUT_NONFINITE);
                         ended = true;
-                        froze = ((a.select & TFP_REC_SEL_FAILURE) && fin && !at_goal) || ((a.select & TFP_REC_SEL_SUCCESS) && fin && at_goal)
+                        froze = ((a.select & TFP_REC_SEL_FAILURE) && fin && !o.at_goal) || ((a.select & TFP_REC_SEL_SUCCESS) && fin && o.at_goal)
                                 || ((a.select & TFP_REC_SEL_NONFINITE) && !fin);
                     }
                 }
@@ -322,18 +331,12 @@ __global__ void __launch_bounds__(EV_THREADS) k_record_step(const TfpRecordArgs 
     if (!__syncthreads_or(rec || unarmed)) return;
 
     // ---- a workgroup with something to count: uniform control flow ----
-    const int wave = t >> 6, lane = t & 63;
-    const long long c0 = wave_count(ended), c1 = wave_count(froze), c2 = wave_count(unarmed), c3 = wave_count(rec);
-    if (lane == 0) {
-        s_part[wave][TFP_REC_ENDED_ARMED] = c0; s_part[wave][TFP_REC_FROZEN] = c1; s_part[wave][TFP_REC_UNARMED] = c2; s_part[wave][TFP_REC_RECORDS] = c3;
-    }
-    __syncthreads();
-    if (t < TFP_REC_ACC) {
-        long long s = 0;
-#pragma unroll
-        for (int w = 0; w < EV_WAVES; ++w) s += s_part[w][t];
-        if (s != 0) atomicAdd((u64*)&a.acc[t], (u64)s);
-    }
+    long long c[TFP_REC_ACC];
+    c[TFP_REC_ENDED_ARMED] = wave_count(ended);
+    c[TFP_REC_FROZEN] = wave_count(froze);
+    c[TFP_REC_UNARMED] = wave_count(unarmed);
+    c[TFP_REC_RECORDS] = wave_count(rec);
+    block_add(c, s_part, (u64*)a.acc, t);
 }
 
 extern "C" {

@@ -4,7 +4,7 @@
 are taken from the engine's own `reset_buf` (the public `dones` is `reset_buf & goal_reset_buf`, which the shipped configuration never sets although every
 env times out), the final errors from the state rows, which hold the final pose until the reset at the start of the next step.  On the GPU an update is one
 launch of csrc/tf_eval.hip (include/trifinger_ppo_eval.h has the definitions and the layout of the accumulator); the plain-torch form below has the same
-semantics, the same accumulator layout, the same bit-pattern bins and fixed-point conversions, and serves CPU tensors (the tests' oracle engines) and
+semantics, the same accumulator layout, the same bit-pattern bins, final errors (`step_errors`) and fixed-point conversions - the same bits -, and serves CPU tensors (the tests' oracle engines) and
 `fused=False`.  The accumulator holds integers only: integer sums commute, so the vector is bitwise the same on every run and after `merge` over ranks.
 """
 import math
@@ -13,7 +13,6 @@ import struct
 import torch
 
 from . import _capi as capi
-from .utils.torch_utils import quat_diff_rad
 
 # include/trifinger_ppo_eval.h
 ENV_RETURN, ENV_AT_GOAL_STEPS, ENV_FIRST_HIT, ENV_EPISODES, ENV_ROWS = 0, 1, 2, 3, 4
@@ -82,14 +81,20 @@ def _bins(x, q_lo, q_hi):
     return torch.where(q < q_lo, torch.zeros_like(q), torch.where(q >= q_hi, torch.full_like(q, 1 + q_hi - q_lo), 1 + q - q_lo))
 
 
-class EpisodeStats:
-    """Episode statistics of the envs of `engine` (a TrifingerEngine, or anything with its buffer attributes state / reward / reset_buf /
-    goal_reset_buf / steps): `reset()`, then `update()` after every env step - no host synchronisation -, `merge(group)` once in a distributed run,
-    `result()` for the one synchronising read.  Tolerances and the at-goal rule default to the engine's config.  `max_episodes_per_env`: an env that has
-    finished that many episodes goes on running, its further episodes are not counted (0: no cap).  `fused`: None = the kernel where the buffers live on
-    a GPU, plain torch otherwise."""
+# what a kernel of csrc/tf_eval.hip reads a per-env engine buffer as, one element per env (`state` is float32 [TF_STATE_ROWS, N])
+_KERNEL_READS = {"reward": (torch.float32,), "reset_buf": (torch.bool, torch.uint8), "goal_reset_buf": (torch.bool, torch.uint8), "steps": (torch.int64,)}
 
-    def __init__(self, engine, pos_tol=None, ori_tol=None, max_episodes_per_env=0, fused=None, rule=None):
+
+class EngineObserver:
+    """What EpisodeStats, EpisodeTracker and record.EpisodeRecorder share: they bind to the buffers of an engine (`engine_of`), judge an episode's end by
+    the same tolerances and at-goal rule (defaults: the engine's config, as the episode length), run ONE launch of csrc/tf_eval.hip behind an env step
+    where the buffers live on a GPU and the plain-torch statement of the same definitions otherwise (`fused`: None decides by the device), and keep an
+    int64 accumulator `acc` that sums over ranks.  A subclass names the per-env buffers its kernel reads besides `state` (`buffers`), the length of its
+    accumulator (`acc_size`), and provides `_launch()` and `_update_torch()`."""
+    buffers = ()
+    acc_size = 0
+
+    def __init__(self, engine, pos_tol=None, ori_tol=None, rule=None, fused=None, episode_length=None):
         self.engine = engine = engine_of(engine)
         cfg = getattr(engine, "cfg", None)
         if (pos_tol is None or ori_tol is None or rule is None) and cfg is None:
@@ -97,74 +102,81 @@ class EpisodeStats:
         self.pos_tol = float(cfg.position_tolerance if pos_tol is None else pos_tol)
         self.ori_tol = float(cfg.orientation_tolerance if ori_tol is None else ori_tol)
         self.rule = int(rule_of_difficulty(int(cfg.task_difficulty)) if rule is None else rule)
-        self.cap = int(max_episodes_per_env)
-        if self.rule not in (0, 1, 2) or self.cap < 0 or math.isnan(self.pos_tol) or math.isnan(self.ori_tol):
-            raise ValueError(f"rule {self.rule} (0, 1, 2), max_episodes_per_env {self.cap} (>= 0), tolerances {self.pos_tol}, {self.ori_tol}")
+        self.ep_len = int((getattr(cfg, "episode_length", 0) or 0) if episode_length is None else episode_length)
+        if self.rule not in (0, 1, 2) or math.isnan(self.pos_tol) or math.isnan(self.ori_tol) or self.ep_len < 0:
+            raise ValueError(f"rule {self.rule} (0, 1, 2), tolerances {self.pos_tol}, {self.ori_tol}, episode_length {self.ep_len} (>= 0)")
         st = engine.state
-        self.num_envs = int(st.shape[1])
-        on_gpu = st.is_cuda
-        self.fused = on_gpu if fused is None else bool(fused)
-        if self.fused and not on_gpu:
+        self.num_envs = n = int(st.shape[1])
+        self.fused = st.is_cuda if fused is None else bool(fused)
+        if self.fused and not st.is_cuda:
             raise ValueError("fused=True: the kernel reads device buffers, this engine lives on the CPU")
         if self.fused:
-            for k in _BUFFERS:
-                t = getattr(engine, k)
-                if not (t.is_cuda and t.is_contiguous() and t.device == st.device):
-                    raise ValueError(f"engine buffer '{k}' is not a contiguous tensor on {st.device}")
-            if tuple(st.shape) != (capi.TF_STATE_ROWS, self.num_envs) or st.dtype != torch.float32:
-                raise ValueError("engine buffer 'state' of another layout than include/trifinger.h: float32 [TF_STATE_ROWS, N]")
-            # what the kernel reads them as: float reward, one-byte flags, int64 step counts, one element per env
-            for k, ok in (("reward", (torch.float32,)), ("reset_buf", (torch.bool, torch.uint8)), ("goal_reset_buf", (torch.bool, torch.uint8)), ("steps", (torch.int64,))):
-                t = getattr(engine, k)
-                if t.dtype not in ok or tuple(t.shape) != (self.num_envs,):
-                    raise ValueError(f"engine buffer '{k}': {t.dtype} {tuple(t.shape)}, the kernel reads {' / '.join(str(d) for d in ok)} [{self.num_envs}]")
-        self.env_acc = torch.zeros((ENV_ROWS, self.num_envs), dtype=torch.int32, device=st.device)
-        self.acc = torch.zeros((ACC,), dtype=torch.int64, device=st.device)
+            if tuple(st.shape) != (capi.TF_STATE_ROWS, n) or st.dtype != torch.float32 or not st.is_contiguous():
+                raise ValueError("engine buffer 'state' of another layout than include/trifinger.h: contiguous float32 [TF_STATE_ROWS, N]")
+            for k in self.buffers:
+                t, ok = getattr(engine, k), _KERNEL_READS[k]
+                if t.dtype not in ok or tuple(t.shape) != (n,) or not t.is_contiguous() or t.device != st.device:
+                    raise ValueError(f"engine buffer '{k}': {t.dtype} {tuple(t.shape)} on {t.device}, the kernel reads contiguous "
+                                     f"{' / '.join(str(d) for d in ok)} [{n}] on {st.device}")
+        self.acc = torch.zeros((self.acc_size,), dtype=torch.int64, device=st.device)
         self.n_allreduce = 0
+
+    def update(self):
+        """account for the env step that has just run (on the stream it ran on); no host synchronisation"""
+        if not self.fused:
+            self._update_torch()
+        elif torch.cuda.current_device() != self.acc.device.index:
+            with torch.cuda.device(self.acc.device):
+                self._launch()
+        else:
+            self._launch()
+
+    def merge(self, group=None):
+        """sum the accumulator over the ranks of `group`: ONE all-reduce of the int64 vector, after which every rank holds the same bits"""
+        import torch.distributed as dist
+        dist.all_reduce(self.acc, op=dist.ReduceOp.SUM, group=group)
+        self.n_allreduce += 1
+
+
+class EpisodeStats(EngineObserver):
+    """Episode statistics of the envs of `engine` (a TrifingerEngine, or anything with its buffer attributes state / reward / reset_buf /
+    goal_reset_buf / steps): `reset()`, then `update()` after every env step - no host synchronisation -, `merge(group)` once in a distributed run,
+    `result()` for the one synchronising read.  Tolerances and the at-goal rule default to the engine's config.  `max_episodes_per_env`: an env that has
+    finished that many episodes goes on running, its further episodes are not counted (0: no cap).  `fused`: None = the kernel where the buffers live on
+    a GPU, plain torch otherwise."""
+
+    buffers = ("reward", "reset_buf", "goal_reset_buf", "steps")
+    acc_size = ACC
+
+    def __init__(self, engine, pos_tol=None, ori_tol=None, max_episodes_per_env=0, fused=None, rule=None):
+        super().__init__(engine, pos_tol, ori_tol, rule, fused)
+        self.cap = int(max_episodes_per_env)
+        if self.cap < 0:
+            raise ValueError(f"max_episodes_per_env {self.cap} (>= 0)")
+        self.env_acc = torch.zeros((ENV_ROWS, self.num_envs), dtype=torch.int32, device=self.acc.device)
 
     def reset(self):
         self.env_acc.zero_()
         self.acc.zero_()
 
-    def update(self):
-        """account for the env step that has just run (on the stream it ran on); no host synchronisation"""
+    def _launch(self):
+        from . import ppo_kernels as pk
         e = self.engine
-        if self.fused:
-            from . import ppo_kernels as pk
-            dev = e.state.device
-            if torch.cuda.current_device() != dev.index:
-                with torch.cuda.device(dev):
-                    pk.eval_step(e.state, e.reward, e.reset_buf, e.goal_reset_buf, e.steps, self.env_acc, self.acc, self.pos_tol, self.ori_tol, self.rule, self.cap)
-            else:
-                pk.eval_step(e.state, e.reward, e.reset_buf, e.goal_reset_buf, e.steps, self.env_acc, self.acc, self.pos_tol, self.ori_tol, self.rule, self.cap)
-        else:
-            self._update_torch()
+        pk.eval_step(e.state, e.reward, e.reset_buf, e.goal_reset_buf, e.steps, self.env_acc, self.acc, self.pos_tol, self.ori_tol, self.rule, self.cap)
 
     @torch.no_grad()
     def _update_torch(self):
         e, ea, acc = self.engine, self.env_acc, self.acc
-        st = e.state
-        cp, gp = st[capi.S_CUBE_P:capi.S_CUBE_P + 3], st[capi.S_GOAL_P:capi.S_GOAL_P + 3]
-        cq, gq = st[capi.S_CUBE_Q:capi.S_CUBE_Q + 4].t().contiguous(), st[capi.S_GOAL_Q:capi.S_GOAL_Q + 4].t().contiguous()
-        d = cp - gp
-        e_p = torch.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])
-        e_o = quat_diff_rad(cq, gq)
-        qfinite = torch.isfinite(cq).all(1) & torch.isfinite(gq).all(1)
-        pos_ok, ori_ok = e_p <= self.pos_tol, e_o <= self.ori_tol
-        at_goal = pos_ok if self.rule == 0 else ((pos_ok & ori_ok) if self.rule == 1 else ori_ok)
         ret = ea[ENV_RETURN].view(torch.float32) + e.reward
+        e_p, e_o, pos_ok, ori_ok, at_goal, fin = episode_outcome(e.state, ret, self.pos_tol, self.ori_tol, self.rule)
         atg = ea[ENV_AT_GOAL_STEPS] + at_goal.to(torch.int32)
         length = e.steps.to(torch.int64)
         first = torch.where((ea[ENV_FIRST_HIT] == 0) & at_goal, length.clamp(1, 2 ** 31 - 1).to(torch.int32), ea[ENV_FIRST_HIT])
         eps = ea[ENV_EPISODES]
         under = (eps < self.cap) if self.cap else torch.ones_like(at_goal)
         ends = e.reset_buf.to(torch.bool)
-        fin = torch.isfinite(ret) & torch.isfinite(e_p) & torch.isfinite(e_o) & qfinite
         counted, nonfin = ends & under & fin, ends & under & ~fin
         i64 = torch.int64
-
-        def fixed(x, lo, hi, scale):
-            return torch.round(x.clamp(lo, hi) * scale).to(i64)
         zero = torch.zeros_like(length)
         acc[EPISODES] += counted.sum()
         acc[NONFINITE] += nonfin.sum()
@@ -178,14 +190,11 @@ class EpisodeStats:
         acc[SUM_LENGTH] += torch.where(counted, length, zero).sum()
         acc[SUM_AT_GOAL_STEPS] += torch.where(counted, atg.to(i64), zero).sum()
         acc[SUM_FIRST_HIT] += torch.where(counted, first.to(i64), zero).sum()
-        clean = torch.zeros_like(ret)                                      # a non-finite value never reaches a conversion
-        acc[SUM_RETURN] += fixed(torch.where(counted, ret, clean), -RETURN_MAX, RETURN_MAX, S_RETURN).sum()
-        acc[SUM_POS_ERR] += fixed(torch.where(counted, e_p, clean), 0.0, POS_ERR_MAX, S_POS_ERR).sum()
-        acc[SUM_ORI_ERR] += fixed(torch.where(counted, e_o, clean), 0.0, ORI_ERR_MAX, S_ORI_ERR).sum()
+        acc[SUM_RETURN:SUM_ORI_ERR + 1] += torch.stack(fixed_sums(counted, ret, e_p, e_o))
         acc[HIST_POS:HIST_POS + POS_BINS] += torch.bincount(_bins(e_p, *POS_Q)[counted], minlength=POS_BINS)
         acc[HIST_ORI:HIST_ORI + ORI_BINS] += torch.bincount(_bins(e_o, *ORI_Q)[counted], minlength=ORI_BINS)
         izero = torch.zeros_like(atg)
-        ea[ENV_RETURN] = torch.where(ends, clean, ret).view(torch.int32)
+        ea[ENV_RETURN] = torch.where(ends, torch.zeros_like(ret), ret).view(torch.int32)
         ea[ENV_AT_GOAL_STEPS] = torch.where(ends, izero, atg)
         ea[ENV_FIRST_HIT] = torch.where(ends, izero, first)
         ea[ENV_EPISODES] = torch.where(ends & under, eps + 1, eps)
@@ -193,12 +202,6 @@ class EpisodeStats:
     def envs_complete(self):
         """the number of envs that have reached the cap; synchronises (one int64)"""
         return int(self.acc[ENVS_COMPLETE])
-
-    def merge(self, group=None):
-        """sum the accumulator over the ranks of `group`: ONE all-reduce of the int64 vector, after which every rank holds the same bits"""
-        import torch.distributed as dist
-        dist.all_reduce(self.acc, op=dist.ReduceOp.SUM, group=group)
-        self.n_allreduce += 1
 
     def result(self):
         """the statistics as a dict of Python numbers (the one synchronising read); a rate or mean over zero episodes is nan"""
@@ -234,7 +237,6 @@ def summarize(raw):
 # ---- the training-time episode tracker (include/trifinger_ppo_track.h) -------------------------------------------------------------------------------
 TRK_RETURN, TRK_ARMED, TRK_ROWS = 0, 1, 2
 (T_EPISODES, T_SUCCESS, T_POS_OK, T_ORI_OK, T_TIMEOUT, T_SUM_LENGTH, T_SUM_RETURN, T_SUM_POS_ERR, T_SUM_ORI_ERR, T_NONFINITE, T_UNARMED, TRACK_ACC) = range(12)
-_TRACK_BUFFERS = ("state", "reward", "reset_buf", "steps")
 
 
 def _fma32(a, b, c):
@@ -272,7 +274,7 @@ def step_asin(x):
 
 
 def step_errors(state):
-    """(e_p, e_o, both quaternions finite) per env from the state rows, in the step's own expressions (csrc/tf_eval.hip: eval_errors) - float32, every
+    """(e_p, e_o, both quaternions finite) per env from the state rows, in the step's own expressions (csrc/tf_eval.hip: eval_errors, behind episode_outcome) - float32, every
     operation rounded separately in the device code's order, the arcsine the step's polynomial (step_asin), so that the values are the kernel's"""
     from .utils.torch_utils import quat_conjugate, quat_mul
     cp, gp = state[capi.S_CUBE_P:capi.S_CUBE_P + 3], state[capi.S_GOAL_P:capi.S_GOAL_P + 3]
@@ -285,7 +287,27 @@ def step_errors(state):
     return e_p, e_o, torch.isfinite(cq).all(1) & torch.isfinite(gq).all(1)
 
 
-class EpisodeTracker:
+def episode_outcome(state, ret, pos_tol, ori_tol, rule):
+    """THE episode outcome per env, stated once for the three `_update_torch` (csrc/tf_eval.hip: episode_outcome is the same statement on the device):
+    (e_p, e_o, pos_ok, ori_ok, at_goal, fin) - the final errors of `step_errors`, the two predicates, the at-goal rule (0 position, 1 both,
+    2 orientation) and the finite test of an episode whose return is `ret`"""
+    e_p, e_o, qfinite = step_errors(state)
+    pos_ok, ori_ok = e_p <= pos_tol, e_o <= ori_tol
+    at_goal = pos_ok if rule == 0 else ((pos_ok & ori_ok) if rule == 1 else ori_ok)
+    return e_p, e_o, pos_ok, ori_ok, at_goal, torch.isfinite(ret) & torch.isfinite(e_p) & torch.isfinite(e_o) & qfinite
+
+
+def fixed_sums(counted, ret, e_p, e_o):
+    """the three fixed-point sums over the `counted` envs, int64 scalars: the return in 2^-16 (clamped to +-2^25), the position error in 2^-30 (to 2^10),
+    the orientation error in 2^-28 (to 4).  A non-finite value never reaches a conversion"""
+    clean = torch.zeros_like(ret)
+
+    def fixed(x, lo, hi, scale):
+        return torch.round(torch.where(counted, x, clean).clamp(lo, hi) * scale).to(torch.int64).sum()
+    return fixed(ret, -RETURN_MAX, RETURN_MAX, S_RETURN), fixed(e_p, 0.0, POS_ERR_MAX, S_POS_ERR), fixed(e_o, 0.0, ORI_ERR_MAX, S_ORI_ERR)
+
+
+class EpisodeTracker(EngineObserver):
     """What an EPISODE is worth while the policy trains (`params.config.track_episodes`): returns, lengths and success of the episodes that end during
     the rollouts, accumulated on the device behind every env step with no host synchronisation.  include/trifinger_ppo_track.h has the definitions; in
     short, per env: the float32 return is summed in step order from the step with steps == 1 (which ARMS the env), and at a step with reset_buf set an
@@ -297,35 +319,15 @@ class EpisodeTracker:
     the return is summed in the same order.  `merge(group)` sums the accumulator over ranks, `take()` hands it out and clears it (no sync),
     `window_stats` turns integer vectors into the reported dict.  `episode_length` (for TIMEOUT) defaults to the engine's config; 0: no time limit."""
 
+    buffers = ("reward", "reset_buf", "steps")
+    acc_size = TRACK_ACC
+
     def __init__(self, engine, pos_tol=None, ori_tol=None, rule=None, fused=None, episode_length=None):
-        self.engine = engine = engine_of(engine)
-        cfg = getattr(engine, "cfg", None)
-        if (pos_tol is None or ori_tol is None or rule is None) and cfg is None:
-            raise ValueError("an engine without a config needs pos_tol, ori_tol and rule")
-        self.pos_tol = float(cfg.position_tolerance if pos_tol is None else pos_tol)
-        self.ori_tol = float(cfg.orientation_tolerance if ori_tol is None else ori_tol)
-        self.rule = int(rule_of_difficulty(int(cfg.task_difficulty)) if rule is None else rule)
-        self.ep_len = int((getattr(cfg, "episode_length", 0) or 0) if episode_length is None else episode_length)
-        if self.rule not in (0, 1, 2) or math.isnan(self.pos_tol) or math.isnan(self.ori_tol):
-            raise ValueError(f"rule {self.rule} (0, 1, 2), tolerances {self.pos_tol}, {self.ori_tol}")
-        st = engine.state
-        self.num_envs = n = int(st.shape[1])
-        on_gpu = st.is_cuda
-        self.fused = on_gpu if fused is None else bool(fused)
-        if self.fused and not on_gpu:
-            raise ValueError("fused=True: the kernel reads device buffers, this engine lives on the CPU")
+        super().__init__(engine, pos_tol, ori_tol, rule, fused, episode_length)
+        n, dev = self.num_envs, self.acc.device
         if self.fused:
-            if tuple(st.shape) != (capi.TF_STATE_ROWS, n) or st.dtype != torch.float32 or not st.is_contiguous():
-                raise ValueError("engine buffer 'state' of another layout than include/trifinger.h: contiguous float32 [TF_STATE_ROWS, N]")
-            for k, ok in (("reward", (torch.float32,)), ("reset_buf", (torch.bool, torch.uint8)), ("steps", (torch.int64,))):
-                t = getattr(engine, k)
-                if t.dtype not in ok or tuple(t.shape) != (n,) or not t.is_contiguous() or t.device != st.device:
-                    raise ValueError(f"engine buffer '{k}': {t.dtype} {tuple(t.shape)} on {t.device}, the kernel reads contiguous "
-                                     f"{' / '.join(str(d) for d in ok)} [{n}] on {st.device}")
-            self._scratch = torch.empty((3, n), dtype=torch.float32, device=st.device)       # the outputs of a launch nobody asked outputs of (`update`)
-        self.env_trk = torch.zeros((TRK_ROWS, n), dtype=torch.int32, device=st.device)
-        self.acc = torch.zeros((TRACK_ACC,), dtype=torch.int64, device=st.device)
-        self.n_allreduce = 0
+            self._scratch = torch.empty((3, n), dtype=torch.float32, device=dev)       # the outputs of a launch nobody asked outputs of (`update`)
+        self.env_trk = torch.zeros((TRK_ROWS, n), dtype=torch.int32, device=dev)
 
     def reset_envs(self):
         """forget every running episode (the accumulator stays): after `restore()` and at the end of `evaluate()`"""
@@ -341,52 +343,33 @@ class EpisodeTracker:
         pk.rollout_track(e.state, e.reward, e.reset_buf, e.steps, self.env_trk, self.acc, scale, self.ep_len, self.pos_tol, self.ori_tol, self.rule,
                          rew_t, done=done, done_t=done_t, end_t=end_t, tout_t=tout_t)
 
-    def update(self):
-        """account for the env step that has just run (on the stream it ran on); no host synchronisation"""
-        if self.fused:
-            s = self._scratch
-            dev = s.device
-            if torch.cuda.current_device() != dev.index:
-                with torch.cuda.device(dev):
-                    self.step_fused(1.0, s[0], end_t=s[1], tout_t=s[2])
-            else:
-                self.step_fused(1.0, s[0], end_t=s[1], tout_t=s[2])
-        else:
-            self._update_torch()
+    def _launch(self):
+        s = self._scratch
+        self.step_fused(1.0, s[0], end_t=s[1], tout_t=s[2])
 
     @torch.no_grad()
     def _update_torch(self):
         """the statement of include/trifinger_ppo_track.h in plain torch"""
         e, trk, acc = self.engine, self.env_trk, self.acc
-        st, r = e.state, e.reward
+        r = e.reward
         s = e.steps.to(torch.int64)
         ends = e.reset_buf.to(torch.bool)
         first = s == 1
         ret = torch.where(first, r, trk[TRK_RETURN].view(torch.float32) + r)
         armed = first | (trk[TRK_ARMED] != 0)
-        e_p, e_o, qfinite = step_errors(st)
-        pos_ok, ori_ok = e_p <= self.pos_tol, e_o <= self.ori_tol
-        at_goal = pos_ok if self.rule == 0 else ((pos_ok & ori_ok) if self.rule == 1 else ori_ok)
-        fin = torch.isfinite(ret) & torch.isfinite(e_p) & torch.isfinite(e_o) & qfinite
+        e_p, e_o, pos_ok, ori_ok, at_goal, fin = episode_outcome(e.state, ret, self.pos_tol, self.ori_tol, self.rule)
         counted, nonfin, unarmed = ends & armed & fin, ends & armed & ~fin, ends & ~armed
         tout = (s >= self.ep_len) if self.ep_len > 0 else torch.zeros_like(ends)
-        i64 = torch.int64
-
-        def fixed(x, lo, hi, scale):
-            return torch.round(x.clamp(lo, hi) * scale).to(i64)
-        clean = torch.zeros_like(ret)                                      # a non-finite value never reaches a conversion
         acc[T_EPISODES] += counted.sum()
         acc[T_SUCCESS] += (counted & at_goal).sum()
         acc[T_POS_OK] += (counted & pos_ok).sum()
         acc[T_ORI_OK] += (counted & ori_ok).sum()
         acc[T_TIMEOUT] += (counted & tout).sum()
         acc[T_SUM_LENGTH] += torch.where(counted, s, torch.zeros_like(s)).sum()
-        acc[T_SUM_RETURN] += fixed(torch.where(counted, ret, clean), -RETURN_MAX, RETURN_MAX, S_RETURN).sum()
-        acc[T_SUM_POS_ERR] += fixed(torch.where(counted, e_p, clean), 0.0, POS_ERR_MAX, S_POS_ERR).sum()
-        acc[T_SUM_ORI_ERR] += fixed(torch.where(counted, e_o, clean), 0.0, ORI_ERR_MAX, S_ORI_ERR).sum()
+        acc[T_SUM_RETURN:T_SUM_ORI_ERR + 1] += torch.stack(fixed_sums(counted, ret, e_p, e_o))
         acc[T_NONFINITE] += nonfin.sum()
         acc[T_UNARMED] += unarmed.sum()
-        trk[TRK_RETURN] = torch.where(ends, clean, ret).view(torch.int32)
+        trk[TRK_RETURN] = torch.where(ends, torch.zeros_like(ret), ret).view(torch.int32)
         trk[TRK_ARMED] = (armed & ~ends).to(torch.int32)
 
     def take(self):
@@ -394,12 +377,6 @@ class EpisodeTracker:
         v = self.acc.clone()
         self.acc.zero_()
         return v
-
-    def merge(self, group=None):
-        """sum the accumulator over the ranks of `group` (before `take`): ONE all-reduce of the int64 vector, after which every rank holds the same bits"""
-        import torch.distributed as dist
-        dist.all_reduce(self.acc, op=dist.ReduceOp.SUM, group=group)
-        self.n_allreduce += 1
 
     @staticmethod
     def window(vectors, games_to_track):

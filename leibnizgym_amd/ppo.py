@@ -59,7 +59,7 @@ adv_n = w (adv - mean) / (std + 1e-8) (`masked_advantage_norm`: torch, once per 
 value term, bounds term, KL statistic - and with it every per-sample gradient is multiplied by w_i; the divisor stays B, not sum(w) (the stale share is
 1 / episode_length, 0.13 % at 750 steps; a constant divisor needs no pre-pass over the minibatch); the batch-independent entropy term is unchanged.  The input
 records keep reading the whole rollout buffer (a stale observation is still a real observation).  `update()` reports `episodes_ended` = end.sum() of the epoch.
-On the GPU: include/trifinger_ppo_episode.h - one launch in place of the reward launch (`rollout_flags`), one in place of GAE (`gae_ends`), the weighted
+On the GPU: include/trifinger_ppo_episode.h - one launch in place of the reward launch (`rollout_flags`), one in place of GAE (`ppo_kernels.gae_ends`), the weighted
 instantiation of the objective kernel reading (adv, w) interleaved, so that the gather still carries at most eight arrays.
 Episode tracking (`params.config.track_episodes`, off by default; `games_to_track` and `score_to_win` are RL-Games' keys): what an EPISODE is worth, in the
 statistics of every epoch.  The trainer resolves the engine once (an env without one is refused) and keeps an `evaluate.EpisodeTracker` on it.  After every env
@@ -431,21 +431,48 @@ def denormalize_value(y, rec: "InputNorm"):
     return torch.clamp(y, -rec.clip, rec.clip) / rec.inv_std_f + rec.mean_f
 
 
-def gae_with_ends(rew, end, tout, val, last_end, gamma, tau, value_bootstrap):
-    """Generalised advantage estimation that sees episode ends (`episode_ends`; the module docstring has the definitions) - the SPECIFICATION of the loop,
-    what the torch path runs and what tfp_gae_ends reproduces bit for bit.  rew, end, tout [T, n]; val [T + 1, n] in reward units; last_end [n]: the end
-    row of the final step of the previous rollout.  Returns (adv, ret, w), each [T, n]; float32, every operation rounded separately in the order written."""
+def gae_spec(rew, val, gamma, tau, done=None, ends=None):
+    """Generalised advantage estimation - the SPECIFICATION of the loop in both its modes, what the torch path runs and what ppo_kernels.gae_buffers reproduces bit
+    for bit; float32, every operation rounded separately in the order written.  rew [T, n]; val [T + 1, n] in reward units; either `done` [T, n] (the
+    public flag stops the estimate and the bootstrap alike) or `ends` = (end [T, n], tout [T, n], last_end [n], value_bootstrap) (`episode_ends`; the
+    module docstring has the definitions; last_end: the end row of the final step of the previous rollout).  Returns adv and ret, and w with `ends`,
+    each [T, n]."""
     T = rew.shape[0]
-    term = end * (1.0 - tout) if value_bootstrap else end
-    w = torch.cat([(1.0 - last_end).unsqueeze(0), 1.0 - end[:T - 1]], dim=0)
+    if ends is None:
+        stop, term, w = done, done, None
+    else:
+        stop, tout, last_end, value_bootstrap = ends
+        term = stop * (1.0 - tout) if value_bootstrap else stop
+        w = torch.cat([(1.0 - last_end).unsqueeze(0), 1.0 - stop[:T - 1]], dim=0)
     adv, last = torch.zeros_like(rew), torch.zeros_like(rew[0])
     for t in reversed(range(T)):
-        cont = 1.0 - end[t]
+        cont = 1.0 - stop[t]
         boot = 1.0 - term[t]
         delta = rew[t] + gamma * val[t + 1] * boot - val[t]
         last = delta + gamma * tau * cont * last
-        adv[t] = last * w[t]
-    return adv, adv + val[:T], w
+        adv[t] = last if w is None else last * w[t]
+    out = dict(adv=adv, ret=adv + val[:T])
+    return out if w is None else dict(out, w=w)
+
+
+def gae_with_ends(rew, end, tout, val, last_end, gamma, tau, value_bootstrap):
+    """`gae_spec` with episode ends, as (adv, ret, w): the specification tfp_gae_ends names (include/trifinger_ppo_episode.h)"""
+    out = gae_spec(rew, val, gamma, tau, ends=(end, tout, last_end, value_bootstrap))
+    return out["adv"], out["ret"], out["w"]
+
+
+def gae_torch(rew, val, gamma, tau, done=None, ends=None, vnorm=None):
+    """ppo_kernels.gae_buffers in plain torch: the same arguments, the same named buffers, the same bits.  With `vnorm` (the returns' record) val is the value
+    network's raw NORMALISED output y: GAE runs on v = clamp(y, -clip, clip) / inv_std_f + mean_f (`denormalize_value`), which replaces y as `val` among
+    the buffers, next to v_old_n = clamp(y[:T], -clip, clip) and ret_n = clamp((ret - mean_f) * inv_std_f, -clip, clip)"""
+    out = {}
+    if vnorm is not None:
+        out["v_old_n"] = torch.clamp(val[:rew.shape[0]], -vnorm.clip, vnorm.clip)
+        out["val"] = val = denormalize_value(val, vnorm)
+    out.update(gae_spec(rew, val, gamma, tau, done, ends))
+    if vnorm is not None:
+        out["ret_n"] = torch.clamp((out["ret"] - vnorm.mean_f) * vnorm.inv_std_f, -vnorm.clip, vnorm.clip)
+    return out
 
 
 def masked_advantage_norm(adv, w):
@@ -950,8 +977,8 @@ class PPOTrainer:
         n = obs.shape[0]
         dev = self.device
         # with the hand-written kernels the bookkeeping of a step is two launches (ppo_kernels.rollout_record / rollout_reward) and the advantage
-        # estimate one (ppo_kernels.gae) instead of ~25 + 8 T elementwise launches; same arithmetic, same random numbers (torch.randn_like)
-        fused = self.fused_loss and obs.is_cuda and obs.dtype == torch.float32
+        # estimate one (ppo_kernels.gae_buffers) instead of ~25 + 8 T elementwise launches; same arithmetic, same random numbers (torch.randn_like)
+        fused, pk = self.fused_loss and obs.is_cuda and obs.dtype == torch.float32, None
         if fused:
             from . import ppo_kernels as pk
         A = self.net.log_std.numel()
@@ -960,9 +987,7 @@ class PPOTrainer:
                    states=torch.zeros(T, n, states.shape[1], device=dev) if states is not None else None,
                    act=torch.zeros(T, n, A, device=dev), nlp=torch.zeros(T, n, device=dev), val=torch.zeros(T + 1, n, device=dev),
                    rew=torch.zeros(T, n, device=dev), mu=torch.zeros(T, n, A, device=dev))
-        ends, eng, ep_len = self.ends, self.ends_engine, self.ends_ep_len
-        trk = self.tracker                                   # `track_episodes`: its launch stands where rollout_flags / rollout_reward stand (one launch either way)
-        if ends:                                             # `end` replaces `done` (module docstring)
+        if self.ends:                                        # `end` replaces `done` (module docstring)
             buf["end"], buf["tout"] = torch.zeros(T, n, device=dev), torch.zeros(T, n, device=dev)
         else:
             buf["done"] = torch.zeros(T, n, device=dev)
@@ -978,7 +1003,7 @@ class PPOTrainer:
                 buf["nlp"][t] = neglogp(a, mu, ls)
                 buf["val"][t] = val_t
             out, r, d, extra = self.env.step(a)
-            last_step, tracked = t == T - 1, False
+            last_step = t == T - 1
             # an env that DECLARES its buffers stable until its next step (`buffers_stable_until_next_step`: RlGamesGpuEnvAdapter hands out the
             # engine's own tensors) is read in place - they are filed above before the next step overwrites them, only what outlives the loop is cloned;
             # any other env gets a snapshot per step (it may refresh its observation asynchronously or on another stream)
@@ -986,72 +1011,51 @@ class PPOTrainer:
             obs, states = ((out["obs"], out["states"]) if isinstance(out, dict) else (out, None)) if live else self._unpack(out)
             if isinstance(extra, (list, tuple)) and len(extra) > 1 and isinstance(extra[1], dict):
                 self.last_info = extra[1]                   # RL-Games convention: [[], info] (direct logging from the env)
-            if ends:
-                # the engine's buffers behind the step: stable until its next step, read in place (one launch where the reward launch stands)
-                rb, st = eng.reset_buf, eng.steps
-                if (fused and r.is_cuda and r.dtype == torch.float32 and r.is_contiguous() and rb.device == r.device and rb.dtype in (torch.bool, torch.uint8)
-                        and rb.is_contiguous() and st.device == r.device and st.dtype == torch.int64 and st.is_contiguous()):
-                    if trk is not None and trk.fused and r.data_ptr() == eng.reward.data_ptr() and dev == r.device:
-                        trk.step_fused(c.reward_scale, buf["rew"][t], end_t=buf["end"][t], tout_t=buf["tout"][t])
-                        tracked = True
-                    else:
-                        pk.rollout_flags(r, rb, st, c.reward_scale, ep_len, buf["rew"][t], buf["end"][t], buf["tout"][t])
-                else:
-                    buf["rew"][t] = r.to(dev) * c.reward_scale
-                    buf["end"][t] = (rb != 0).to(dev).float()
-                    if ep_len > 0:
-                        buf["tout"][t] = (st >= ep_len).to(dev).float()
-            elif fused and r.is_cuda and r.dtype == torch.float32 and r.is_contiguous() and d.is_cuda and d.dtype in (torch.bool, torch.uint8) and d.is_contiguous():
-                if trk is not None and trk.fused and r.data_ptr() == trk.engine.reward.data_ptr() and d.device == r.device and dev == r.device:
-                    trk.step_fused(c.reward_scale, buf["rew"][t], done=d, done_t=buf["done"][t])
-                    tracked = True
-                else:
-                    pk.rollout_reward(r, d, c.reward_scale, buf["rew"][t], buf["done"][t])
-            else:
-                buf["rew"][t] = r.to(dev) * c.reward_scale
-                buf["done"][t] = d.to(dev).float()
-            if trk is not None and not tracked:             # the fused conditions do not hold: the tracker's own update (the torch statement on CPU tensors)
-                trk.update()
+            self._file_step(pk, buf, t, r, d)
         buf["val"][T] = self.net.value(obs, states)
         self.last = (obs, states)
-        vn = self.value_norm
-        if ends:
-            if fused and vn is not None:                     # as below: buf["val"] keeps the raw normalised output y on this path
-                buf["adv"], buf["ret"], buf["w"], buf["ret_n"], buf["v_old_n"] = pk.gae_ends(buf["rew"], buf["end"], buf["tout"], buf["val"], self.last_end, c.gamma,
-                                                                                             c.tau, c.value_bootstrap, vn.mean_f, vn.inv_std_f, vn.clip)
-            elif fused:
-                buf["adv"], buf["ret"], buf["w"] = pk.gae_ends(buf["rew"], buf["end"], buf["tout"], buf["val"], self.last_end, c.gamma, c.tau, c.value_bootstrap)
-            else:
-                if vn is not None:
-                    buf["v_old_n"] = torch.clamp(buf["val"][:T], -vn.clip, vn.clip)
-                    buf["val"] = denormalize_value(buf["val"], vn)
-                buf["adv"], buf["ret"], buf["w"] = gae_with_ends(buf["rew"], buf["end"], buf["tout"], buf["val"], self.last_end, c.gamma, c.tau, c.value_bootstrap)
-                if vn is not None:
-                    buf["ret_n"] = torch.clamp((buf["ret"] - vn.mean_f) * vn.inv_std_f, -vn.clip, vn.clip)
-            self.last_end = buf["end"][T - 1].clone()        # w[0] of the next rollout
-        elif vn is not None and fused:
-            # buf["val"] holds the network's raw output y, a NORMALISED value: GAE runs on v = clamp(y, -5, 5) / inv_std_f + mean_f (module docstring), which
-            # the kernel forms on the way - buf["val"] keeps y on this path, the torch form below replaces it by v
-            buf["adv"], buf["ret"], buf["ret_n"], buf["v_old_n"] = pk.gae_vnorm(buf["rew"], buf["done"], buf["val"], vn.mean_f, vn.inv_std_f, vn.clip, c.gamma, c.tau)
-        elif fused:
-            buf["adv"], buf["ret"] = pk.gae(buf["rew"], buf["done"], buf["val"], c.gamma, c.tau)
-        else:
-            if vn is not None:
-                buf["v_old_n"] = torch.clamp(buf["val"][:T], -vn.clip, vn.clip)
-                buf["val"] = denormalize_value(buf["val"], vn)
-            adv = torch.zeros(T, n, device=dev)
-            last = torch.zeros(n, device=dev)
-            for t in reversed(range(T)):
-                nd = 1.0 - buf["done"][t]
-                delta = buf["rew"][t] + c.gamma * buf["val"][t + 1] * nd - buf["val"][t]
-                last = delta + c.gamma * c.tau * nd * last
-                adv[t] = last
-            buf["ret"] = adv + buf["val"][:T]
-            buf["adv"] = adv
-            if vn is not None:
-                buf["ret_n"] = torch.clamp((buf["ret"] - vn.mean_f) * vn.inv_std_f, -vn.clip, vn.clip)
+        self._advantages(pk, buf)
         self.frames += T * n
         return buf
+
+    def _file_step(self, pk, buf, t, r, d):
+        """file what env step t returned into slot t of the rollout buffers: rew = r * reward_scale and the public `done` as a float or, with
+        `episode_ends`, `end` / `tout` from the engine's own buffers behind the step (stable until its next step, read in place).  ONE launch where the
+        kernels can read the tensors (ppo_kernels.rollout_reward / rollout_flags), torch expressions otherwise.  `track_episodes`: the tracker's launch
+        stands where that launch stands - one launch either way - when it reads the very reward the env returned; otherwise its own update() follows.
+        `pk`: ppo_kernels on the hand-written path, None on the torch path"""
+        c, dev, ends, eng, trk = self.cfg, self.device, self.ends, self.ends_engine, self.tracker
+        fused = pk is not None and pk.readable(r, r, torch.float32) and (
+            (pk.readable(eng.reset_buf, r, torch.bool, torch.uint8) and pk.readable(eng.steps, r, torch.int64)) if ends
+            else pk.readable(d, r, torch.bool, torch.uint8))
+        tracked = bool(fused and trk is not None and trk.fused and r.data_ptr() == trk.engine.reward.data_ptr() and dev == r.device)
+        if tracked and ends:
+            trk.step_fused(c.reward_scale, buf["rew"][t], end_t=buf["end"][t], tout_t=buf["tout"][t])
+        elif tracked:
+            trk.step_fused(c.reward_scale, buf["rew"][t], done=d, done_t=buf["done"][t])
+        elif fused and ends:
+            pk.rollout_flags(r, eng.reset_buf, eng.steps, c.reward_scale, self.ends_ep_len, buf["rew"][t], buf["end"][t], buf["tout"][t])
+        elif fused:
+            pk.rollout_reward(r, d, c.reward_scale, buf["rew"][t], buf["done"][t])
+        else:
+            buf["rew"][t] = r.to(dev) * c.reward_scale
+            if ends:
+                buf["end"][t] = (eng.reset_buf != 0).to(dev).float()
+                if self.ends_ep_len > 0:
+                    buf["tout"][t] = (eng.steps >= self.ends_ep_len).to(dev).float()
+            else:
+                buf["done"][t] = d.to(dev).float()
+        if trk is not None and not tracked:                 # the tracker's launch could not stand in: its own update (the torch statement on CPU tensors)
+            trk.update()
+
+    def _advantages(self, pk, buf):
+        """the advantage pass over a filled rollout: adv and ret, w with `episode_ends`, ret_n and v_old_n with `normalize_value` - ONE launch
+        (ppo_kernels.gae_buffers; buf["val"] keeps the network's raw normalised output y there) or the torch statement (`gae_torch`, which replaces it by v)"""
+        c = self.cfg
+        mode = dict(ends=(buf["end"], buf["tout"], self.last_end, c.value_bootstrap)) if self.ends else dict(done=buf["done"])
+        buf.update((pk.gae_buffers if pk is not None else gae_torch)(buf["rew"], buf["val"], c.gamma, c.tau, vnorm=self.value_norm, **mode))
+        if self.ends:
+            self.last_end = buf["end"][c.horizon - 1].clone()       # w[0] of the next rollout
 
     # ---- one minibatch step, split at the gradient exchange ----
     def _mb_backward(self, d, idx, acc):

@@ -422,31 +422,70 @@ def eval_test_predicates(state, pos_tol, ori_tol):
     return out
 
 
+def readable(t, like, *dtypes):
+    """the kernels can read `t` in place: a contiguous GPU tensor of one of `dtypes` on the device of `like`"""
+    return t.is_cuda and t.device == like.device and t.dtype in dtypes and t.is_contiguous()
+
+
 def rollout_reward(r, d, scale, rew_t, done_t):
     """rew_t = r * scale, done_t = float(d) in one launch; d: torch.bool / uint8"""
     assert d.dtype in (torch.bool, torch.uint8) and d.is_contiguous() and r.is_contiguous() and r.dtype == torch.float32
     _chk(load().tfp_rollout_reward(r.data_ptr(), d.data_ptr(), float(scale), r.numel(), rew_t.data_ptr(), done_t.data_ptr(), _stream(r)), "tfp_rollout_reward")
 
 
-def gae(rew, done, val, gamma, tau):
-    """(adv, ret) over the horizon in one launch: rew, done [T, n], val [T + 1, n] -> adv, ret [T, n]; the arithmetic of the backward loop it replaces"""
+def _gae_launch(rew, end, val, gamma, tau, tout=None, last_end=None, boot=None, mean_f=None, inv_std_f=None, clip=0.0):
+    """the checks, the allocation and the launch behind `gae`, `gae_vnorm` and `gae_ends` (`boot` None: the `done` instantiations, `end` holds the done
+    rows; mean_f None: plain values); the outputs in the order adv, ret, [w], [ret_n, v_old_n]"""
     T, n = rew.shape
-    adv, ret = torch.empty_like(rew), torch.empty_like(rew)
-    _chk(load().tfp_gae(rew.data_ptr(), done.data_ptr(), val.data_ptr(), float(gamma), float(gamma * tau), T, n, adv.data_ptr(), ret.data_ptr(), _stream(rew)), "tfp_gae")
-    return adv, ret
+    ends, vnorm = boot is not None, mean_f is not None
+    ins = (rew, val, end) + ((tout, last_end) if ends else ()) + ((mean_f, inv_std_f) if vnorm else ())
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.device == rew.device for t in ins)
+    assert val.shape == (T + 1, n) and end.shape == (T, n) and (not ends or (tout.shape == (T, n) and last_end.shape == (n,)))
+    assert not vnorm or (mean_f.numel() == 1 and inv_std_f.numel() == 1 and float(clip) > 0.0)
+    out = {k: torch.empty_like(rew) for k in ("adv", "ret") + (("w",) if ends else ()) + (("ret_n", "v_old_n") if vnorm else ())}
+    p = {k: t.data_ptr() for k, t in out.items()}
+    g, gt, st = float(gamma), float(gamma * tau), _stream(rew)
+    norm = (mean_f.data_ptr(), inv_std_f.data_ptr(), float(clip)) if vnorm else (None, None, float(clip))
+    if ends:
+        _chk(load().tfp_gae_ends(rew.data_ptr(), end.data_ptr(), tout.data_ptr(), val.data_ptr(), last_end.data_ptr(), 1 if boot else 0, *norm, g, gt, T, n,
+                                 p["adv"], p["ret"], p["w"], p.get("ret_n"), p.get("v_old_n"), st), "tfp_gae_ends")
+    elif vnorm:
+        _chk(load().tfp_gae_vnorm(rew.data_ptr(), end.data_ptr(), val.data_ptr(), *norm, g, gt, T, n, p["adv"], p["ret"], p["ret_n"], p["v_old_n"], st), "tfp_gae_vnorm")
+    else:
+        _chk(load().tfp_gae(rew.data_ptr(), end.data_ptr(), val.data_ptr(), g, gt, T, n, p["adv"], p["ret"], st), "tfp_gae")
+    return tuple(out.values())
+
+
+# the three entry points of k_gae, one binding each (the tests and the cost tools call and count them by name); `gae_buffers` is what the trainer calls
+def gae(rew, done, val, gamma, tau):
+    """tfp_gae: (adv, ret), each [T, n], from rew, done [T, n] and val [T + 1, n]"""
+    return _gae_launch(rew, done, val, gamma, tau)
 
 
 def gae_vnorm(rew, done, y, mean_f, inv_std_f, clip, gamma, tau):
-    """(adv, ret, ret_n, v_old_n), each [T, n], in one launch for a value network whose raw output y [T + 1, n] is in normalised units (`normalize_value`):
-    v = clamp(y, -clip, clip) / inv_std_f + mean_f, `gae` on v, ret_n = clamp((ret - mean_f) * inv_std_f, -clip, clip), v_old_n = clamp(y[:T], -clip, clip);
-    mean_f / inv_std_f: the float32 [1] device tensors a ppo.InputNorm(1) publishes.  The bits of the torch expressions (tfp_gae_vnorm)."""
-    T, n = rew.shape
-    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.device == rew.device for t in (rew, done, y, mean_f, inv_std_f))
-    assert done.shape == (T, n) and y.shape == (T + 1, n) and mean_f.numel() == 1 and inv_std_f.numel() == 1 and float(clip) > 0.0
-    adv, ret, ret_n, v_old_n = (torch.empty_like(rew) for _ in range(4))
-    _chk(load().tfp_gae_vnorm(rew.data_ptr(), done.data_ptr(), y.data_ptr(), mean_f.data_ptr(), inv_std_f.data_ptr(), float(clip), float(gamma), float(gamma * tau),
-                              T, n, adv.data_ptr(), ret.data_ptr(), ret_n.data_ptr(), v_old_n.data_ptr(), _stream(rew)), "tfp_gae_vnorm")
-    return adv, ret, ret_n, v_old_n
+    """tfp_gae_vnorm: (adv, ret, ret_n, v_old_n) for a value network whose raw output y [T + 1, n] is in normalised units (`normalize_value`);
+    mean_f / inv_std_f: the float32 [1] device tensors a ppo.InputNorm(1) publishes"""
+    return _gae_launch(rew, done, y, gamma, tau, mean_f=mean_f, inv_std_f=inv_std_f, clip=clip)
+
+
+def gae_ends(rew, end, tout, val, last_end, gamma, tau, value_bootstrap, mean_f=None, inv_std_f=None, clip=0.0):
+    """tfp_gae_ends (`episode_ends`): (adv, ret, w), and with mean_f / inv_std_f / clip (adv, ret, w, ret_n, v_old_n); last_end [n]"""
+    return _gae_launch(rew, end, val, gamma, tau, tout, last_end, bool(value_bootstrap), mean_f, inv_std_f, clip)
+
+
+def gae_buffers(rew, val, gamma, tau, done=None, ends=None, vnorm=None):
+    """Generalised advantage estimation over the horizon in ONE launch (ppo.gae_spec is the specification, bit for bit) - the ONE wrapper of the trainer:
+    rew [T, n], val [T + 1, n], and either `done` [T, n] or `ends` = (end [T, n], tout [T, n], last_end [n], value_bootstrap) (`episode_ends`).  `vnorm`:
+    the returns' record (ppo.InputNorm(1): mean_f, inv_std_f, clip) - val is then the value network's raw normalised output.  Returns the named buffers
+    of the rollout, each [T, n], so that the caller can `buf.update()` them: adv and ret, w with `ends`, ret_n and v_old_n with `vnorm`."""
+    assert (done is None) != (ends is None)
+    norm = (vnorm.mean_f, vnorm.inv_std_f, vnorm.clip) if vnorm is not None else ()
+    if ends is not None:
+        end, tout, last_end, boot = ends
+        return dict(zip(("adv", "ret", "w", "ret_n", "v_old_n"), gae_ends(rew, end, tout, val, last_end, gamma, tau, boot, *norm)))
+    if vnorm is not None:
+        return dict(zip(("adv", "ret", "ret_n", "v_old_n"), gae_vnorm(rew, done, val, *norm, gamma, tau)))
+    return dict(zip(("adv", "ret"), gae(rew, done, val, gamma, tau)))
 
 
 # ---- episode ends (include/trifinger_ppo_episode.h; ppo.PPOTrainer with `episode_ends`) --------------------------------------------------------
@@ -460,25 +499,6 @@ def rollout_flags(r, reset_buf, steps, scale, episode_length, rew_t, end_t, tout
         assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n and t.device == r.device
     _chk(load().tfp_rollout_flags(r.data_ptr(), reset_buf.data_ptr(), steps.data_ptr(), float(scale), int(episode_length), n, rew_t.data_ptr(), end_t.data_ptr(),
                                   tout_t.data_ptr(), _stream(r)), "tfp_rollout_flags")
-
-
-def gae_ends(rew, end, tout, val, last_end, gamma, tau, value_bootstrap, mean_f=None, inv_std_f=None, clip=0.0):
-    """`gae` with episode ends in one launch (ppo.gae_with_ends is the specification): rew, end, tout [T, n], val [T + 1, n], last_end [n] ->
-    (adv, ret, w), each [T, n].  With mean_f / inv_std_f (the float32 [1] tensors of the returns' record) and clip, val is the value network's raw
-    normalised output and the result is (adv, ret, w, ret_n, v_old_n): `gae_vnorm` with episode ends."""
-    T, n = rew.shape
-    vnorm = mean_f is not None
-    ins = (rew, end, tout, val, last_end) + ((mean_f, inv_std_f) if vnorm else ())
-    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.device == rew.device for t in ins)
-    assert end.shape == (T, n) and tout.shape == (T, n) and val.shape == (T + 1, n) and last_end.shape == (n,)
-    assert not vnorm or (mean_f.numel() == 1 and inv_std_f.numel() == 1 and float(clip) > 0.0)
-    adv, ret, w = (torch.empty_like(rew) for _ in range(3))
-    ret_n, v_old_n = (torch.empty_like(rew), torch.empty_like(rew)) if vnorm else (None, None)
-    _chk(load().tfp_gae_ends(rew.data_ptr(), end.data_ptr(), tout.data_ptr(), val.data_ptr(), last_end.data_ptr(), 1 if value_bootstrap else 0,
-                             mean_f.data_ptr() if vnorm else None, inv_std_f.data_ptr() if vnorm else None, float(clip), float(gamma), float(gamma * tau), T, n,
-                             adv.data_ptr(), ret.data_ptr(), w.data_ptr(), ret_n.data_ptr() if vnorm else None, v_old_n.data_ptr() if vnorm else None,
-                             _stream(rew)), "tfp_gae_ends")
-    return (adv, ret, w, ret_n, v_old_n) if vnorm else (adv, ret, w)
 
 
 # ---- the training-time episode tracker (include/trifinger_ppo_track.h; evaluate.EpisodeTracker, ppo.PPOTrainer with `track_episodes`) ---------------------

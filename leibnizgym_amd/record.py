@@ -8,13 +8,12 @@ nothing is handed from one workgroup to another and nothing depends on their ord
 definitions - same buffers, same bits - and serves CPU tensors (the tests' oracle engines) and `fused=False`.  `replay_frames` renders a harvested episode
 through the offscreen renderer, whose state matrix does not care whether its columns are envs or time steps.
 """
-import math
 import os
 
 import torch
 
 from . import _capi as capi
-from .evaluate import engine_of, rule_of_difficulty, step_errors
+from .evaluate import EngineObserver, episode_outcome
 
 # include/trifinger_ppo_record.h
 REC_STATE_ROWS = 59
@@ -50,29 +49,24 @@ def decode_outcome(bits):
     return {k: bool(bits & b) for k, b in _OUT_NAMES}
 
 
-class EpisodeRecorder:
+class EpisodeRecorder(EngineObserver):
     """The last `length` recorded steps of the episodes of the first `watch` envs of `engine` (a TrifingerEngine, or anything with its buffer attributes)
     that end as `select` says: `update()` after every env step - no host synchronisation -, `take()` to harvest the frozen episodes, `counts()` for the
     integer counters, `reset()` to clear everything.  `every`: record the steps 1, 1 + every, ... of an episode and always its final step.  `length`
     defaults to ceil(episode_length / every) + 1: a whole episode; the tolerances, the at-goal rule and the episode length default to the engine's config
     as in `EpisodeStats`.  `fused`: None = the kernel where the buffers live on a GPU, the torch statement otherwise."""
 
+    buffers = ("reward", "reset_buf", "steps")
+    acc_size = ACC
+
     def __init__(self, engine, select="failure", every=1, length=None, watch=None, pos_tol=None, ori_tol=None, rule=None, fused=None, max_bytes=8 << 30,
                  episode_length=None):
-        self.engine = engine = engine_of(engine)
-        cfg = getattr(engine, "cfg", None)
-        if (pos_tol is None or ori_tol is None or rule is None) and cfg is None:
-            raise ValueError("an engine without a config needs pos_tol, ori_tol and rule")
-        self.pos_tol = float(cfg.position_tolerance if pos_tol is None else pos_tol)
-        self.ori_tol = float(cfg.orientation_tolerance if ori_tol is None else ori_tol)
-        self.rule = int(rule_of_difficulty(int(cfg.task_difficulty)) if rule is None else rule)
-        self.ep_len = int((getattr(cfg, "episode_length", 0) or 0) if episode_length is None else episode_length)
+        super().__init__(engine, pos_tol, ori_tol, rule, fused, episode_length)
         self.select = parse_select(select)
         self.every = int(every)
-        if self.rule not in (0, 1, 2) or math.isnan(self.pos_tol) or math.isnan(self.ori_tol) or self.every < 1 or self.ep_len < 0:
-            raise ValueError(f"rule {self.rule} (0, 1, 2), tolerances {self.pos_tol}, {self.ori_tol}, every {self.every} (>= 1), episode_length {self.ep_len} (>= 0)")
-        st = engine.state
-        self.num_envs = n = int(st.shape[1])
+        if self.every < 1:
+            raise ValueError(f"every {self.every} (>= 1)")
+        n, dev = self.num_envs, self.acc.device
         self.watch = w = n if watch is None else int(watch)
         if not 1 <= w <= n:
             raise ValueError(f"watch = {watch}: the first `watch` of {n} envs, 1 .. {n}")
@@ -87,22 +81,9 @@ class EpisodeRecorder:
         if nbytes > int(max_bytes):
             raise ValueError(f"the ring would take {nbytes} bytes ({nbytes / 2 ** 30:.2f} GiB = 4 x length {L} x {REC_ROWS} x watch {w}), more than "
                              f"max_bytes = {int(max_bytes)}: lower `watch` or `length`, raise `every`, or raise `max_bytes`")
-        on_gpu = st.is_cuda
-        self.fused = on_gpu if fused is None else bool(fused)
-        if self.fused and not on_gpu:
-            raise ValueError("fused=True: the kernel reads device buffers, this engine lives on the CPU")
-        if self.fused:
-            if tuple(st.shape) != (capi.TF_STATE_ROWS, n) or st.dtype != torch.float32 or not st.is_contiguous():
-                raise ValueError("engine buffer 'state' of another layout than include/trifinger.h: contiguous float32 [TF_STATE_ROWS, N]")
-            for k, ok in (("reward", (torch.float32,)), ("reset_buf", (torch.bool, torch.uint8)), ("steps", (torch.int64,))):
-                t = getattr(engine, k)
-                if t.dtype not in ok or tuple(t.shape) != (n,) or not t.is_contiguous() or t.device != st.device:
-                    raise ValueError(f"engine buffer '{k}': {t.dtype} {tuple(t.shape)} on {t.device}, the kernel reads contiguous "
-                                     f"{' / '.join(str(d) for d in ok)} [{n}] on {st.device}")
-        self.ring = torch.zeros((L, REC_ROWS, w), dtype=torch.float32, device=st.device)
-        self.hdr = torch.zeros((capi.TF_NUM_DR, w), dtype=torch.float32, device=st.device)
-        self.env_rec = torch.zeros((ENV_ROWS, w), dtype=torch.int32, device=st.device)
-        self.acc = torch.zeros((ACC,), dtype=torch.int64, device=st.device)
+        self.ring = torch.zeros((L, REC_ROWS, w), dtype=torch.float32, device=dev)
+        self.hdr = torch.zeros((capi.TF_NUM_DR, w), dtype=torch.float32, device=dev)
+        self.env_rec = torch.zeros((ENV_ROWS, w), dtype=torch.int32, device=dev)
 
     def reset(self):
         """forget everything: rings, headers, per-env state (frozen episodes included) and counters"""
@@ -116,18 +97,6 @@ class EpisodeRecorder:
         e = self.engine
         pk.record_step(e.state, e.reward, e.reset_buf, e.steps, self.ring, self.hdr, self.env_rec, self.acc, self.every, self.select, self.ep_len,
                        self.pos_tol, self.ori_tol, self.rule)
-
-    def update(self):
-        """account for the env step that has just run (on the stream it ran on); no host synchronisation"""
-        if self.fused:
-            dev = self.ring.device
-            if torch.cuda.current_device() != dev.index:
-                with torch.cuda.device(dev):
-                    self._launch()
-            else:
-                self._launch()
-        else:
-            self._update_torch()
 
     @torch.no_grad()
     def _update_torch(self):
@@ -148,10 +117,7 @@ class EpisodeRecorder:
         cnt = torch.where(first, torch.zeros_like(st), er[ENV_COUNT])
         rec = armed & (rb | ((s32 - 1).to(torch.int64) % self.every == 0))
         ended = armed & rb
-        e_p, e_o, qfinite = step_errors(state)
-        pos_ok, ori_ok = e_p <= self.pos_tol, e_o <= self.ori_tol
-        at_goal = pos_ok if self.rule == 0 else ((pos_ok & ori_ok) if self.rule == 1 else ori_ok)
-        fin = torch.isfinite(ret) & torch.isfinite(e_p) & torch.isfinite(e_o) & qfinite
+        e_p, e_o, pos_ok, ori_ok, at_goal, fin = episode_outcome(state, ret, self.pos_tol, self.ori_tol, self.rule)
         tout = (s >= self.ep_len) if self.ep_len > 0 else torch.zeros_like(rb)
         i32 = torch.int32
         outcome = (at_goal.to(i32) * OUT_AT_GOAL + pos_ok.to(i32) * OUT_POS_OK + ori_ok.to(i32) * OUT_ORI_OK + tout.to(i32) * OUT_TIMEOUT
