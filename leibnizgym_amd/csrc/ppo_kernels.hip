@@ -227,21 +227,29 @@ int tfp_api_version(void) { return 3; }
 }  // extern "C"
 // (No launch of this file zeroes a small buffer any more - the objective and the optimiser keep their accumulators clean themselves.  When one did, it was a
 // kernel and not hipMemsetAsync: inside a captured HIP graph the memset / memcpy NODES of this ROCm stack proved unsafe, docs/HISTORY.md section 8.)
+// the ONE launch of the objective: k_ppo_loss<9 | 18, VCLIP, WGT>, VCLIP where old_v is given, WGT where `adv` is (adv_i, w_i) interleaved.  Every entry point
+// below is its own argument check (`ok`) and this call
+static int launch_ppo_loss(bool ok, const float* mu, const float* log_std, const float* act, const float* old_nlp, const float* adv, const float* old_mu,
+                           const float* v, const float* ret, const float* old_v, bool weighted, int32_t B, int32_t A, float e_clip, float v_coef,
+                           float ent_coef, float bounds_coef, float* d_mu, float* d_v, float* d_logstd, float* loss_out, float* stats, void* stream) {
+    if (!ok || B <= 0 || (A != 9 && A != 18)) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid((B + 255) / 256), block(256);
+#define LOSS(A_, V_, W_) hipLaunchKernelGGL((k_ppo_loss<A_, V_, W_>), grid, block, 0, s, mu, log_std, act, old_nlp, adv, old_mu, v, ret, B, e_clip, v_coef, ent_coef, \
+                                            bounds_coef, d_mu, d_v, d_logstd, loss_out, stats, old_v)
+#define LOSS_A(V_, W_) do { if (A == 9) LOSS(9, V_, W_); else LOSS(18, V_, W_); } while (0)
+    if (!weighted) { if (!old_v) LOSS_A(false, false); else LOSS_A(true, false); }
+    else { if (!old_v) LOSS_A(false, true); else LOSS_A(true, true); }
+#undef LOSS_A
+#undef LOSS
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
 extern "C" {
 int tfp_ppo_loss(const float* mu, const float* log_std, const float* act, const float* old_nlp, const float* adv, const float* old_mu,
                  const float* v, const float* ret, int32_t B, int32_t A, float e_clip, float v_coef, float ent_coef, float bounds_coef,
                  float* d_mu, float* d_v, float* d_logstd, float* loss_out, float* stats, void* stream) {
-    if (B <= 0 || (A != 9 && A != 18)) return -1;
-    hipStream_t s = (hipStream_t)stream;
-    dim3 grid((B + 255) / 256), block(256);
-    const float* no_old_v = nullptr;
-    if (A == 9)
-        hipLaunchKernelGGL((k_ppo_loss<9, false, false>), grid, block, 0, s, mu, log_std, act, old_nlp, adv, old_mu, v, ret, B, e_clip, v_coef, ent_coef,
-                           bounds_coef, d_mu, d_v, d_logstd, loss_out, stats, no_old_v);
-    else
-        hipLaunchKernelGGL((k_ppo_loss<18, false, false>), grid, block, 0, s, mu, log_std, act, old_nlp, adv, old_mu, v, ret, B, e_clip, v_coef, ent_coef,
-                           bounds_coef, d_mu, d_v, d_logstd, loss_out, stats, no_old_v);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_ppo_loss(true, mu, log_std, act, old_nlp, adv, old_mu, v, ret, nullptr, false, B, A, e_clip, v_coef, ent_coef, bounds_coef, d_mu, d_v, d_logstd,
+                           loss_out, stats, stream);
 }
 
 // include/trifinger_ppo_value.h: tfp_ppo_loss with the value term clipped around old_v [B] (the compile-time variant of the same kernel: its accumulators,
@@ -249,16 +257,8 @@ int tfp_ppo_loss(const float* mu, const float* log_std, const float* act, const 
 int tfp_ppo_loss_vclip(const float* mu, const float* log_std, const float* act, const float* old_nlp, const float* adv, const float* old_mu,
                        const float* v, const float* ret, const float* old_v, int32_t B, int32_t A, float e_clip, float v_coef, float ent_coef,
                        float bounds_coef, float* d_mu, float* d_v, float* d_logstd, float* loss_out, float* stats, void* stream) {
-    if (B <= 0 || (A != 9 && A != 18) || !old_v) return -1;
-    hipStream_t s = (hipStream_t)stream;
-    dim3 grid((B + 255) / 256), block(256);
-    if (A == 9)
-        hipLaunchKernelGGL((k_ppo_loss<9, true, false>), grid, block, 0, s, mu, log_std, act, old_nlp, adv, old_mu, v, ret, B, e_clip, v_coef, ent_coef,
-                           bounds_coef, d_mu, d_v, d_logstd, loss_out, stats, old_v);
-    else
-        hipLaunchKernelGGL((k_ppo_loss<18, true, false>), grid, block, 0, s, mu, log_std, act, old_nlp, adv, old_mu, v, ret, B, e_clip, v_coef, ent_coef,
-                           bounds_coef, d_mu, d_v, d_logstd, loss_out, stats, old_v);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_ppo_loss(old_v != nullptr, mu, log_std, act, old_nlp, adv, old_mu, v, ret, old_v, false, B, A, e_clip, v_coef, ent_coef, bounds_coef, d_mu, d_v,
+                           d_logstd, loss_out, stats, stream);
 }
 
 // include/trifinger_ppo_episode.h: the two entry points above with a weight per sample, adv_w [B, 2] = (adv_i, w_i) interleaved (8-byte aligned: one load);
@@ -266,31 +266,14 @@ int tfp_ppo_loss_vclip(const float* mu, const float* log_std, const float* act, 
 int tfp_ppo_loss_w(const float* mu, const float* log_std, const float* act, const float* old_nlp, const float* adv_w, const float* old_mu,
                    const float* v, const float* ret, int32_t B, int32_t A, float e_clip, float v_coef, float ent_coef, float bounds_coef,
                    float* d_mu, float* d_v, float* d_logstd, float* loss_out, float* stats, void* stream) {
-    if (B <= 0 || (A != 9 && A != 18) || !adv_w || ((uintptr_t)adv_w & 7) != 0) return -1;
-    hipStream_t s = (hipStream_t)stream;
-    dim3 grid((B + 255) / 256), block(256);
-    const float* no_old_v = nullptr;
-    if (A == 9)
-        hipLaunchKernelGGL((k_ppo_loss<9, false, true>), grid, block, 0, s, mu, log_std, act, old_nlp, adv_w, old_mu, v, ret, B, e_clip, v_coef, ent_coef,
-                           bounds_coef, d_mu, d_v, d_logstd, loss_out, stats, no_old_v);
-    else
-        hipLaunchKernelGGL((k_ppo_loss<18, false, true>), grid, block, 0, s, mu, log_std, act, old_nlp, adv_w, old_mu, v, ret, B, e_clip, v_coef, ent_coef,
-                           bounds_coef, d_mu, d_v, d_logstd, loss_out, stats, no_old_v);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_ppo_loss(adv_w && ((uintptr_t)adv_w & 7) == 0, mu, log_std, act, old_nlp, adv_w, old_mu, v, ret, nullptr, true, B, A, e_clip, v_coef, ent_coef,
+                           bounds_coef, d_mu, d_v, d_logstd, loss_out, stats, stream);
 }
 int tfp_ppo_loss_vclip_w(const float* mu, const float* log_std, const float* act, const float* old_nlp, const float* adv_w, const float* old_mu,
                          const float* v, const float* ret, const float* old_v, int32_t B, int32_t A, float e_clip, float v_coef, float ent_coef,
                          float bounds_coef, float* d_mu, float* d_v, float* d_logstd, float* loss_out, float* stats, void* stream) {
-    if (B <= 0 || (A != 9 && A != 18) || !old_v || !adv_w || ((uintptr_t)adv_w & 7) != 0) return -1;
-    hipStream_t s = (hipStream_t)stream;
-    dim3 grid((B + 255) / 256), block(256);
-    if (A == 9)
-        hipLaunchKernelGGL((k_ppo_loss<9, true, true>), grid, block, 0, s, mu, log_std, act, old_nlp, adv_w, old_mu, v, ret, B, e_clip, v_coef, ent_coef,
-                           bounds_coef, d_mu, d_v, d_logstd, loss_out, stats, old_v);
-    else
-        hipLaunchKernelGGL((k_ppo_loss<18, true, true>), grid, block, 0, s, mu, log_std, act, old_nlp, adv_w, old_mu, v, ret, B, e_clip, v_coef, ent_coef,
-                           bounds_coef, d_mu, d_v, d_logstd, loss_out, stats, old_v);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_ppo_loss(old_v && adv_w && ((uintptr_t)adv_w & 7) == 0, mu, log_std, act, old_nlp, adv_w, old_mu, v, ret, old_v, true, B, A, e_clip, v_coef,
+                           ent_coef, bounds_coef, d_mu, d_v, d_logstd, loss_out, stats, stream);
 }
 
 // the zero state of tfp_ppo_loss's accumulators (after a launch that failed or was aborted; a completed launch leaves them clean itself)
@@ -673,6 +656,26 @@ static void group_add(GemmGroup& g, int& total, const float* A, const float* B, 
     g.n = p + 1;
 }
 
+// host side: what the three tfp_*_group entry points share.  `prob(p, q)` describes problem p (false: a bad argument, -1); the n <= 8 problems are appended
+// in order - grid ceil(N / GT) x ceil(M / GT) x nz each -, first[] is padded, and the one-kind rule is applied: `vec` (the alignment class) for all or for
+// none, Y given for all or for none, -4 otherwise.  nvec / ny: how many have each, for the entry point's own template selection
+struct GemmProb { const float *A, *B, *bias, *Y, *E; float* C; int M, N, K, lda, ldb, chunk, nz; bool vec; };
+template <class F>
+static int group_build(GemmGroup& g, int& total, int& nvec, int& ny, int n, F prob) {
+    if (n <= 0 || n > 8) return -1;
+    memset(&g, 0, sizeof(g));
+    total = nvec = ny = 0;
+    for (int p = 0; p < n; ++p) {
+        GemmProb q;
+        if (!prob(p, q)) return -1;
+        nvec += q.vec ? 1 : 0;
+        ny += q.Y ? 1 : 0;
+        group_add(g, total, q.A, q.B, q.bias, q.Y, q.C, q.M, q.N, q.K, q.lda, q.ldb, q.chunk, (q.N + GT - 1) / GT, (q.M + GT - 1) / GT, q.nz, q.E);
+    }
+    for (int p = n; p < 9; ++p) g.first[p] = total;
+    return ((nvec != 0 && nvec != n) || (ny != 0 && ny != n)) ? -4 : 0;
+}
+
 // gw[N1, N2] and gb[N1] from `splits` slabs of [N1, N2 + 1] (fixed summation order: deterministic)
 __global__ void __launch_bounds__(256) k_sum_partials(const float* __restrict__ part, float* __restrict__ gw, float* __restrict__ gb, int splits,
                                                       int N1, int N2) {
@@ -733,17 +736,14 @@ int tfp_gemm_tn_bias(const float* A, const float* Y, const float* B, float* part
 // (the caller then launches them one by one) ----
 int tfp_linear_fwd_group(const void* const* A, const void* const* W, const void* const* bias, void* const* C, const int32_t* M, const int32_t* N, const int32_t* K,
                          int32_t act, int32_t n, void* stream) {
-    if (n <= 0 || n > 8) return -1;
-    GemmGroup g; memset(&g, 0, sizeof(g));
-    int total = 0, nvec = 0;
-    for (int p = 0; p < n; ++p) {
-        if (M[p] <= 0 || N[p] <= 0 || K[p] <= 0) return -1;
-        nvec += ((K[p] & 3) == 0 && (((uintptr_t)A[p] | (uintptr_t)W[p]) & 15) == 0) ? 1 : 0;
-        group_add(g, total, (const float*)A[p], (const float*)W[p], (const float*)bias[p], nullptr, (float*)C[p], M[p], N[p], K[p], K[p], K[p], 0,
-                  (N[p] + GT - 1) / GT, (M[p] + GT - 1) / GT, 1);
-    }
-    for (int p = n; p < 9; ++p) g.first[p] = total;
-    if (nvec != 0 && nvec != n) return -4;
+    GemmGroup g;
+    int total, nvec, ny_;
+    const int rc = group_build(g, total, nvec, ny_, n, [&](int p, GemmProb& q) {
+        q = {(const float*)A[p], (const float*)W[p], (const float*)bias[p], nullptr, nullptr, (float*)C[p], M[p], N[p], K[p], K[p], K[p], 0, 1,
+             (K[p] & 3) == 0 && (((uintptr_t)A[p] | (uintptr_t)W[p]) & 15) == 0};
+        return M[p] > 0 && N[p] > 0 && K[p] > 0;
+    });
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
 #define FWDG(V, ACT_) hipLaunchKernelGGL((k_gemm_group<false, false, V, V, ACT_, false, false, false>), dim3(total), dim3(512), 0, s, g)
     if (nvec) { if (act) FWDG(true, 1); else FWDG(true, 0); }
@@ -753,21 +753,16 @@ int tfp_linear_fwd_group(const void* const* A, const void* const* W, const void*
 }
 int tfp_gemm_nn_dz_group(const void* const* A, const void* const* Y, const void* const* B, const void* const* Yout, void* const* C, const int32_t* M,
                          const int32_t* N, const int32_t* K, int32_t n, void* stream) {
-    if (n <= 0 || n > 8) return -1;
-    GemmGroup g; memset(&g, 0, sizeof(g));
-    int total = 0, nvec = 0, ny_ = 0;
-    for (int p = 0; p < n; ++p) {
-        if (M[p] <= 0 || N[p] <= 0 || K[p] <= 0) return -1;
+    GemmGroup g;
+    int total, nvec, ny_;
+    const int rc = group_build(g, total, nvec, ny_, n, [&](int p, GemmProb& q) {
         const float* y = Y ? (const float*)Y[p] : nullptr;
-        nvec += ((K[p] & 3) == 0 && (((uintptr_t)A[p] | (uintptr_t)y) & 15) == 0) ? 1 : 0;
-        ny_ += y ? 1 : 0;
         const float* e = Yout ? (const float*)Yout[p] : nullptr;
-        if (e && (N[p] & 3) == 0 && ((uintptr_t)e & 15) != 0) return -1;
-        group_add(g, total, (const float*)A[p], (const float*)B[p], nullptr, y, (float*)C[p], M[p], N[p], K[p], K[p], N[p], 0,
-                  (N[p] + GT - 1) / GT, (M[p] + GT - 1) / GT, 1, e);
-    }
-    for (int p = n; p < 9; ++p) g.first[p] = total;
-    if ((nvec != 0 && nvec != n) || (ny_ != 0 && ny_ != n)) return -4;
+        q = {(const float*)A[p], (const float*)B[p], nullptr, y, e, (float*)C[p], M[p], N[p], K[p], K[p], N[p], 0, 1,
+             (K[p] & 3) == 0 && (((uintptr_t)A[p] | (uintptr_t)y) & 15) == 0};
+        return M[p] > 0 && N[p] > 0 && K[p] > 0 && !(e && (N[p] & 3) == 0 && ((uintptr_t)e & 15) != 0);
+    });
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
 #define NNG(V, DZ_) hipLaunchKernelGGL((k_gemm_group<false, true, V, false, -1, DZ_, false, false>), dim3(total), dim3(512), 0, s, g)
     if (nvec) { if (ny_) NNG(true, true); else NNG(true, false); }
@@ -781,18 +776,15 @@ int tfp_gemm_nn_group(const void* const* A, const void* const* Y, const void* co
 }
 int tfp_gemm_tn_partials_group(const void* const* A, const void* const* Y, const void* const* B, void* const* part, const int32_t* rows, const int32_t* N1,
                                const int32_t* N2, int32_t chunk, int32_t n, void* stream) {
-    if (n <= 0 || n > 8 || chunk <= 0 || (chunk % GK) != 0) return -1;
-    GemmGroup g; memset(&g, 0, sizeof(g));
-    int total = 0, ny_ = 0;
-    for (int p = 0; p < n; ++p) {
-        if (rows[p] <= 0 || N1[p] <= 0 || N2[p] <= 0) return -1;
-        const float* y = Y ? (const float*)Y[p] : nullptr;
-        ny_ += y ? 1 : 0;
-        group_add(g, total, (const float*)A[p], (const float*)B[p], nullptr, y, (float*)part[p], N1[p], N2[p] + 1, rows[p], N1[p], N2[p], chunk,
-                  (N2[p] + 1 + GT - 1) / GT, (N1[p] + GT - 1) / GT, (rows[p] + chunk - 1) / chunk);
-    }
-    for (int p = n; p < 9; ++p) g.first[p] = total;
-    if (ny_ != 0 && ny_ != n) return -4;
+    if (chunk <= 0 || (chunk % GK) != 0) return -1;
+    GemmGroup g;
+    int total, nvec, ny_;
+    const int rc = group_build(g, total, nvec, ny_, n, [&](int p, GemmProb& q) {          // no alignment class: the operands are staged by scalars
+        q = {(const float*)A[p], (const float*)B[p], nullptr, Y ? (const float*)Y[p] : nullptr, nullptr, (float*)part[p], N1[p], N2[p] + 1, rows[p], N1[p], N2[p],
+             chunk, (rows[p] + chunk - 1) / chunk, false};
+        return rows[p] > 0 && N1[p] > 0 && N2[p] > 0;
+    });
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (ny_) hipLaunchKernelGGL((k_gemm_group<true, true, false, false, -1, true, true, true>), dim3(total), dim3(512), 0, s, g);
     else hipLaunchKernelGGL((k_gemm_group<true, true, false, false, -1, false, true, true>), dim3(total), dim3(512), 0, s, g);

@@ -29,10 +29,9 @@ network; without one the critic takes the actor's keys).  RL-Games is not instal
 RL-Games' network builder and D2RLNet as far as can be stated without it.  `activation`: relu, tanh, sigmoid, elu, selu, swish, gelu, softplus or None (`ACTIVATIONS`),
 behind every hidden layer and never behind the output layer; anything else raises a ValueError naming the key.  `d2rl: True` (`D2RLMLP`): h_1 = act(x W_1^T + b_1),
 h_l = act([h_{l-1} | x] W_l^T + b_l) with W_l [u_l, u_{l-1} + D0] (torch.cat([h, x], 1): the hidden output first), the output layer reads h_last alone, the
-concatenated x is the normalised one, the initialisers see the real fan-in; `d2rl: False` keeps FusedMLP and the state-dict keys checkpoints have.  On a GPU all of
-it runs on the network walk (one launch per direction for both networks: include/trifinger_ppo_net.h) - except swish and gelu, whose derivative cannot be formed from
-the layer output the backward walk keeps, and shapes the walk declines: such a trainer prints ONE message at construction and runs its whole update on plain torch,
-as with `fused_kernels=False` (the per-layer kernels are ELU only and are never applied to a network that asked for something else).
+concatenated x is the normalised one, the initialisers see the real fan-in; `d2rl: False` keeps FusedMLP and the state-dict keys checkpoints have.  Which tier runs a network on a GPU - the
+network walk, the per-layer kernels, plain torch - is decided in ppo_kernels.forward_nets / backward_nets and, once per trainer with ONE message, in
+PPOTrainer.__init__ (`_fused_refusal`: swish, gelu and shapes the walk declines put the whole update on plain torch, as with `fused_kernels=False`).
 `truncate_grads: False` / `central_value_config.truncate_grads: False`: no gradient-norm truncation for that optimiser.  `lr_schedule`: adaptive (the KL rule),
 identity / None (the actor's rate stays; the KL statistic is still logged), linear (1e-6 + (learning_rate - 1e-6) * max(0, max_epochs - epoch) / max_epochs, set once
 per epoch); the central value network's rate is constant throughout.  Not built and refused by name (ValueError): `fixed_sigma: False`, `mu_activation` /
@@ -521,9 +520,23 @@ class ActorCritic(nn.Module):
         """the record in front of the critic: the central value network's own; without one the critic reads `obs` and shares the actor's"""
         return self.state_norm if self.central else self.obs_norm
 
+    def _forward(self, xs, nets, runner=False):
+        """the ONE place that answers, for a call: which record stands in front of which network of `nets` ("actor" / "critic", inputs `xs`), and whether the
+        hand-written path may take it - every network on the MFMA kernels, float32 rows on the GPU, no autograd.  Returns the networks' outputs.
+        `runner`: the hand-written path is ONE call of ppo_kernels.forward_nets - the walk, else the per-layer kernels (its docstring has the order) - on the
+        raw rows with the records' statistics, no hidden output stored.  Otherwise, and whenever that path may not take the call, each network's own forward
+        (FusedMLP.forward: the per-layer kernels, or torch) behind InputNorm.normalize"""
+        recs = [self.obs_norm if n == "actor" else self.critic_norm() for n in nets]
+        mods, x = [getattr(self, n) for n in nets], xs[0]
+        if runner and all(m.mfma for m in mods) and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and all(x.dim() == 2 for x in xs):
+            from . import ppo_kernels as pk
+            ys = pk.forward_nets([(x.contiguous(), m.layer_list()) for x, m in zip(xs, mods)], store_hidden=False,
+                                 norms=[r.stats() if r is not None else None for r in recs])
+            return [y[-1] for y in ys]
+        return [m(r.normalize(x) if r is not None else x) for x, m, r in zip(xs, mods, recs)]
+
     def value(self, obs, states):
-        x, nm = (states if self.central else obs), self.critic_norm()
-        return self.critic(nm.normalize(x) if nm is not None else x).squeeze(-1)
+        return self._forward([states if self.central else obs], ["critic"])[0].squeeze(-1)
 
     def value_denorm(self, obs, states):
         """the value in reward units, whether or not the network works in normalised ones"""
@@ -531,42 +544,20 @@ class ActorCritic(nn.Module):
         return denormalize_value(y, self.value_norm) if self.value_norm is not None else y
 
     def dist(self, obs):
-        mu = self.actor(self.obs_norm.normalize(obs) if self.obs_norm is not None else obs)
+        mu = self._forward([obs], ["actor"])[0]
         return mu, self.log_std.expand_as(mu)
 
     def dist_and_value(self, obs, states):
-        """(mu, log_std, value) of one batch: on the hand-written kernels and without autograd (the rollout) layer k of the two networks is ONE launch
-        (ppo_kernels.mlp_forward_pair: four launches instead of eight per environment step)"""
-        xc = states if self.central else obs
-        na, nc = self.obs_norm, self.critic_norm()
-        if self.actor.mfma and self.critic.mfma and obs.is_cuda and obs.dtype == torch.float32 and not torch.is_grad_enabled():
-            from . import ppo_kernels as pk
-            if na is None and nc is None:
-                ya, yc = pk.mlp_forward_pair(obs.contiguous(), self.actor.layer_list(), xc.contiguous(), self.critic.layer_list(), store_hidden=False)
-            else:                              # raw rows in, normalised where the walk stages them: no launch of its own
-                ya, yc = pk.mlp_forward_pair(obs.contiguous(), self.actor.layer_list(), xc.contiguous(), self.critic.layer_list(), store_hidden=False,
-                                             norms=(na.stats() if na is not None else None, nc.stats() if nc is not None else None))
-            mu, v = ya[-1], yc[-1].squeeze(-1)
-        else:
-            mu = self.actor(na.normalize(obs) if na is not None else obs)
-            v = self.critic(nc.normalize(xc) if nc is not None else xc).squeeze(-1)
-        return mu, self.log_std.expand_as(mu), v
+        """(mu, log_std, value) of one batch: on the hand-written kernels and without autograd (the rollout) both networks are ONE launch of the walk,
+        else layer k of the two is one (ppo_kernels.forward_nets)"""
+        mu, v = self._forward([obs, states if self.central else obs], ["actor", "critic"], runner=True)
+        return mu, self.log_std.expand_as(mu), v.squeeze(-1)
 
     def mean_action(self, obs):
         """the deterministic action: bit for bit the `mu` of dist_and_value.  On the hand-written kernels and without autograd it is ONE launch of the
         network walk with the actor alone (no hidden output stored, the actor's input record applied where the walk stages its rows); a shape the walk
         declines runs on the per-layer kernels; plain torch otherwise."""
-        na = self.obs_norm
-        if self.actor.mfma and obs.is_cuda and obs.dtype == torch.float32 and obs.dim() == 2 and not torch.is_grad_enabled():
-            from . import ppo_kernels as pk
-            x, layers = obs.contiguous(), self.actor.layer_list()
-            out = pk.mlp_walk_forward([(x, layers)], store_hidden=False, norms=[na.stats()] if na is not None else None) if pk.USE_WALK else None
-            if out is not None:
-                return out[0][-1]
-            if pk.needs_net_walk(layers):
-                raise RuntimeError("a network with an activation other than ELU or with d2rl runs on the network walk only, and the walk declined these shapes")
-            return pk.mlp_forward(pk.normalize_rows(x, *na.stats()) if na is not None else x, layers)[-1]
-        return self.actor(na.normalize(obs) if na is not None else obs)
+        return self._forward([obs], ["actor"], runner=True)[0]
 
 
 def neglogp(x, mu, log_std):
@@ -598,26 +589,29 @@ class PPOTrainer:
         self.opt = torch.optim.Adam(groups, eps=1e-8, **kw)
         self.lr = c.lr
         # The hand-written kernels serve a network the walk can run (module docstring): decided ONCE, here, with one message - otherwise the whole update
-        # runs on plain torch, as with fused_kernels=False; no ELU kernel is ever applied to a network that asked for something else
+        # runs on plain torch, as with fused_kernels=False; no ELU kernel is ever applied to a network that asked for something else.  `fk` is the one
+        # answer everything below takes: the objective kernel and the minibatch step, the MFMA layers, the records, the flat optimiser, the tracker
         fk = bool(fused and c.fused_kernels)
         self.torch_path_reason = self._fused_refusal() if fk else None
         if self.torch_path_reason:
             print(f"[ppo] {self.torch_path_reason}: this trainer runs on the plain torch path (as with fused_kernels=False)", flush=True)
             fk = False
-        self.fused_loss = fk                               # hand-written objective kernel (GPU only)
-        self.net.actor.mfma = self.net.critic.mfma = fk    # ... and the MFMA linear layers
+        self.fused_loss = self.net.actor.mfma = self.net.critic.mfma = fk
+        if fk:
+            self._mb_backward = self._mb_backward_fused
+        norm = lambda dim: InputNorm(dim, self.device, fused=fk)  # noqa: E731
         # which optimiser truncates its gradient norm (`truncate_grads` / central_value_config.truncate_grads; one optimiser without a central value network)
         self.trunc = (bool(c.truncate_grads), bool(c.value_truncate_grads if self.net.central else c.truncate_grads))
         # normalize_input / central_value_config.normalize_input: one record per normalised input, frozen during an epoch (module docstring)
         if c.normalize_input:
-            self.net.obs_norm = InputNorm(obs_dim, self.device, fused=fk)
+            self.net.obs_norm = norm(obs_dim)
         if c.normalize_input_value and self.net.central:
-            self.net.state_norm = InputNorm(state_dim, self.device, fused=fk)
+            self.net.state_norm = norm(state_dim)
         # the value side: which clip_value key applies depends on who is the critic; the returns' record exists only when normalize_value is on
         self.clip_v = bool(c.clip_value_central if self.net.central else c.clip_value)
         self.value_norm = None
         if c.normalize_value:
-            self.value_norm = self.net.value_norm = InputNorm(1, self.device, fused=fk)
+            self.value_norm = self.net.value_norm = norm(1)
         self.dist_on = False
         self.n_grad_allreduce = self.n_kl_allreduce = 0       # collectives issued so far (what a test of the distributed path counts)
         self.n_norm_allgather = 0
@@ -652,6 +646,8 @@ class PPOTrainer:
                 for m in net:
                     if isinstance(m, nn.Linear):
                         m._grad_out = (self.flat_opt.grad_view(m.weight), self.flat_opt.grad_view(m.bias))
+            # the minibatch step's view of the two networks, built ONCE: the parameters and their gradient slots stay where they are from here on
+            self._layer_lists = (self.net.actor.layer_list(), self.net.critic.layer_list())
         # exploration noise and minibatch order must differ between ranks (the same env index of two shards would
         # otherwise receive the same noise sequence): re-seed with the rank after the weights are in place
         torch.manual_seed(c.seed + 7919 * rank)
@@ -672,8 +668,7 @@ class PPOTrainer:
         if c.track_episodes:
             from .evaluate import EpisodeTracker, engine_of
             eng = self.ends_engine if self.ends_engine is not None else engine_of(env)
-            fused_trk = bool(fk and eng.state.is_cuda)
-            self.tracker = EpisodeTracker(eng, fused=fused_trk)
+            self.tracker = EpisodeTracker(eng, fused=bool(fk and eng.state.is_cuda))
         self.frames = 0
         self.epoch = 0
         self.last_info = {}
@@ -825,7 +820,6 @@ class PPOTrainer:
         return sd
 
     def save(self, path: str):
-        import os
         os.makedirs(os.path.dirname(os.path.abspath(path)) or ".", exist_ok=True)
         torch.save(self.state_dict(), path)
         return path
@@ -1060,10 +1054,9 @@ class PPOTrainer:
     # ---- one minibatch step, split at the gradient exchange ----
     def _mb_backward(self, d, idx, acc):
         """gather the minibatch, forward, losses, backward; returns nothing - gradients sit in p.grad, the running
-        sums of the logged quantities in `acc` (device tensors, no host sync)"""
+        sums of the logged quantities in `acc` (device tensors, no host sync).  The torch statement; a trainer on the hand-written kernels binds
+        `_mb_backward_fused` under this name at construction"""
         c = self.cfg
-        if self.fused_loss:
-            return self._mb_backward_fused(d, idx, acc, None)
         obs = d["obs"][idx]
         mu, ls = self.net.dist(obs)
         nlp = neglogp(d["act"][idx], mu, ls)
@@ -1092,7 +1085,7 @@ class PPOTrainer:
             acc["kl"] += kl
             acc["loss"] += loss.detach(); acc["a_loss"] += a_loss.detach(); acc["c_loss"] += c_loss.detach()
 
-    def _mb_backward_fused(self, d, idx, acc, obs):
+    def _mb_backward_fused(self, d, idx, acc):
         """the same step on the hand-written kernels: one gather launch for the seven minibatch arrays (eight with `clip_value`: old_v), the MFMA layers, the objective
         and its gradients in ONE launch (ppo_kernels.ppo_loss_and_grads), the backward pass started at the network outputs with those
         gradients (no loss node), the chunk sums of all weight gradients in one launch.  Every parameter gradient lands in its slot of
@@ -1100,35 +1093,33 @@ class PPOTrainer:
         statistics accumulate on the device in `acc["_fused"]` = (loss, a_loss, c_loss, kl)"""
         from . import ppo_kernels as pk
         c = self.cfg
-        srcs = [d["obs"], d["act"], d["old_nlp"], d["adv_w"] if self.ends else d["adv"], d["ret"], d["old_mu"]] + ([d["old_v"]] if self.clip_v else []) + \
-               ([d["states"]] if d["states"] is not None else [])
-        assert len(srcs) <= pk.GATHER_MAX                  # obs, act, old_nlp, adv (or (adv, w) interleaved), ret (or ret_n), old_mu, old_v, states: exactly one launch's worth
         na, ns = self.net.obs_norm, self.net.state_norm
-        if na is None and ns is None:
-            g = pk.gather_rows(srcs, idx)
-        else:                                      # the same launch writes obs / states normalised: what the forward AND the first layers' weight gradients read
-            nm = [na.stats() if na is not None else None] + [None] * (len(srcs) - 1)
-            if d["states"] is not None:
-                nm[-1] = ns.stats() if ns is not None else None
-            g = pk.gather_rows(srcs, idx, norm=nm)
-        obs, act, old_nlp, adv, ret, old_mu = g[:6]
-        old_v = g[6] if self.clip_v else None
-        states = g[-1] if d["states"] is not None else None
+        # what the ONE gather launch carries, in order: (key, source, statistics or None) - with statistics the same launch writes obs / states normalised: what
+        # the forward AND the first layers' weight gradients read.  adv is (adv_i, w_i) interleaved with `episode_ends`, ret is ret_n with `normalize_value`
+        ent = [("obs", d["obs"], na.stats() if na is not None else None), ("act", d["act"], None), ("old_nlp", d["old_nlp"], None),
+               ("adv", d["adv_w"] if self.ends else d["adv"], None), ("ret", d["ret"], None), ("old_mu", d["old_mu"], None)]
+        if self.clip_v:
+            ent.append(("old_v", d["old_v"], None))
+        if d["states"] is not None:
+            ent.append(("states", d["states"], ns.stats() if ns is not None else None))
+        assert len(ent) <= pk.GATHER_MAX                   # with every option on exactly one launch's worth
+        g = dict(zip([e[0] for e in ent], pk.gather_rows([e[1] for e in ent], idx, norm=[e[2] for e in ent])))
         for p in self.net.parameters():
             p.grad = None
         # no autograd: the structure is fixed (two Linear / ELU stacks), so the step is a straight sequence of kernel launches from this
         # thread - forward of both networks, the objective with its gradients, the two backward walks, one launch for all chunk sums
         with torch.no_grad():
-            la, lc = self.net.actor.layer_list(), self.net.critic.layer_list()
-            xc = states if self.net.central else obs
+            la, lc = self._layer_lists
+            obs = g["obs"]
+            xc = g["states"] if self.net.central else obs
             ya, yc = pk.mlp_forward_pair(obs, la, xc, lc)        # layer k of both networks in one launch
             mu, v = ya[-1], yc[-1].squeeze(-1)
             v_coef = 1.0 if self.net.central else 0.5 * c.critic_coef
-            kw = {"old_v": old_v} if self.clip_v else {}
+            kw = {"old_v": g["old_v"]} if self.clip_v else {}
             if self.ends:                                  # the gathered array is (adv_i, w_i): the weighted instantiation of the objective
-                kw["adv_w"], adv = adv, None
-            _, d_mu, d_v, _ = pk.ppo_loss_and_grads(mu, self.net.log_std, v, act, old_nlp, adv, ret, old_mu, acc["_fused"], c.e_clip, v_coef,
-                                                    c.entropy_coef, c.bounds_loss_coef, d_ls_out=self.flat_opt.grad_view(self.net.log_std), **kw)
+                kw["adv_w"] = g.pop("adv")
+            _, d_mu, d_v, _ = pk.ppo_loss_and_grads(mu, self.net.log_std, v, g["act"], g["old_nlp"], g.get("adv"), g["ret"], g["old_mu"], acc["_fused"], c.e_clip,
+                                                    v_coef, c.entropy_coef, c.bounds_loss_coef, d_ls_out=self.flat_opt.grad_view(self.net.log_std), **kw)
             try:
                 pk.mlp_backward_pair(obs, ya, d_mu, la, xc, yc, d_v.unsqueeze(-1), lc)
                 pk.flush_partial_sums()
@@ -1235,10 +1226,8 @@ class PPOTrainer:
                 elif kl < 0.5 * c.kl_threshold:
                     lr = min(lr * 1.5, 1e-2)
                 self._set_actor_lr(lr)
-        if vn is not None:
-            self._update_value_norm(src, buf)
-        else:
-            self._update_input_norm(src)
+        # `normalize_value`: the epoch's de-normalised returns buf["ret"] (T n samples) join the end-of-epoch merge of the input records
+        self._update_input_norm(src, returns=buf["ret"].reshape(-1, 1) if vn is not None else None)
         for k in ("loss", "a_loss", "c_loss"):
             stats[k] = float(acc[k]) / max(count, 1)
         stats["lr"] = self.lr
@@ -1262,17 +1251,11 @@ class PPOTrainer:
         return out
 
     @torch.no_grad()
-    def _update_value_norm(self, src, buf):
-        """`normalize_value`: the epoch's de-normalised returns buf["ret"] (T n samples) join the end-of-epoch merge of the input records - their moments
-        travel in the same vector, hence in the same all_gather"""
-        self._update_input_norm(src, returns=buf["ret"].reshape(-1, 1))
-
-    @torch.no_grad()
     def _update_input_norm(self, src, returns=None):
         """the end of an epoch: the moments of its RAW rollout buffer (T n rows) merged into the running records, which then serve the next epoch.
         One pass over the buffer (ppo_kernels.moments: both inputs in one call) and one merge launch; a distributed run gathers every rank's batch vector
         [1 + 2 Do (+ 1 + 2 Ds)] (float64) with ONE all_gather and merges them in rank order, so that all ranks keep the same record bit for bit.
-        `returns` [T n, 1] (only from `_update_value_norm`): the returns' record [3] is appended to the vector - one more moments call and one more merge
+        `returns` [T n, 1] (`normalize_value`: the epoch's de-normalised returns): the returns' record [3] is appended to the vector - one more moments call and one more merge
         launch (the kernels take up to two arrays per call), the same single all_gather."""
         recs = dict(self._norm_records())
         n_in = len(recs)
@@ -1318,13 +1301,13 @@ class PPOTrainer:
         at the end, `<name>_best.pth` whenever the mean reward improves after `save_best_after` epochs.  With `track_episodes` the best is judged by
         `episode_return` once a window exists (RL-Games' criterion), and an `episode_return` above `score_to_win` saves `<name>.pth`, marks `won` in the
         epoch's statistics and stops - on every rank in the same epoch, since every rank holds the all-reduced vector."""
-        import os
         out = []
         for _ in range(epochs):
             st = self.update(self.rollout())
             self.epoch += 1
             st["epoch"], st["frames"] = self.epoch - 1, self.frames
-            if self.tracker is not None and st.get("episode_return", -float("inf")) > self.cfg.score_to_win:
+            won = self.tracker is not None and st.get("episode_return", -float("inf")) > self.cfg.score_to_win
+            if won:
                 st["won"] = True
             out.append(st)
             if log:
@@ -1336,9 +1319,7 @@ class PPOTrainer:
                 if self.epoch >= self.cfg.save_best_after and score is not None and score > self.best_reward:
                     self.best_reward = score
                     self.save(os.path.join(checkpoint_dir, f"{self.cfg.name}_best.pth"))
-            if self.tracker is not None and st.get("episode_return", -float("inf")) > self.cfg.score_to_win:
-                break                                        # the final save below writes <name>.pth
-            if self.epoch >= self.cfg.max_epochs:
+            if won or self.epoch >= self.cfg.max_epochs:     # won: the final save below writes <name>.pth
                 break
         if checkpoint_dir:
             self.save(os.path.join(checkpoint_dir, f"{self.cfg.name}.pth"))

@@ -19,97 +19,50 @@ def library_path():
     return os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libtrifinger_ppo.so")
 
 
+_P, _I, _L, _R = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+_LOSS = [_P] * 8 + [_I, _I] + [_R] * 4 + [_P] * 6          # the objective; its clip variants take old_v behind `ret`
+_WALK = [_P, _I, _I, _P]
+# every entry point the binding calls: name -> argument types (include/trifinger_ppo*.h).  All return int but tfp_moments_part_doubles (int64)
+_ARGTYPES = {
+    # include/trifinger_ppo.h
+    "tfp_api_version": [], "tfp_reset_state": [_P], "tfp_ppo_loss": _LOSS,
+    "tfp_clip_adam": [_P] * 4 + [_I, _I] + [_P] * 3 + [_R] * 5 + [_P],
+    "tfp_linear_fwd": [_P] * 4 + [_I] * 4 + [_P], "tfp_gemm_nn": [_P] * 4 + [_I] * 3 + [_P], "tfp_gemm_nn_dz": [_P] * 5 + [_I] * 3 + [_P],
+    "tfp_gemm_tn_bias": [_P] * 6 + [_I] * 4 + [_P], "tfp_gemm_tn_partials": [_P] * 4 + [_I] * 4 + [_P],
+    "tfp_linear_fwd_group": [_P] * 7 + [_I, _I, _P], "tfp_gemm_nn_group": [_P] * 7 + [_I, _P], "tfp_gemm_nn_dz_group": [_P] * 8 + [_I, _P],
+    "tfp_gemm_tn_partials_group": [_P] * 7 + [_I, _I, _P], "tfp_sum_partials_multi": [_P] * 6 + [_I, _P],
+    "tfp_gemm_tn_partials_direct_chunk": [], "tfp_gemm_tn_partials_direct": [_P] * 6 + [_I, _P],
+    "tfp_rollout_record": [_P, _I, _P, _I] + [_P] * 5 + [_I, _I] + [_P] * 7, "tfp_rollout_reward": [_P, _P, _R, _I, _P, _P, _P],
+    "tfp_gae": [_P] * 3 + [_R, _R, _I, _I, _P, _P, _P], "tfp_gather_rows": [_P] * 3 + [_I, _P, _I, _P],
+    "tfp_mlp_forward": _WALK, "tfp_mlp_backward": _WALK,
+    # input normalisation (include/trifinger_ppo_norm.h: csrc/ppo_norm.hip and the walk variant)
+    "tfp_moments_part_doubles": [_P, _I, _I], "tfp_moments": [_P, _P, _I, _I, _P, _L, _P, _P], "tfp_norm_merge": [_P] * 3 + [_I] * 3 + [_P] * 3,
+    "tfp_gather_rows_norm": [_P] * 6 + [_I, _P, _I, _P], "tfp_mlp_forward_norm": [_P, _P, _I, _I, _P],
+    # the value side (include/trifinger_ppo_value.h)
+    "tfp_ppo_loss_vclip": [_P] + _LOSS, "tfp_gae_vnorm": [_P] * 5 + [_R, _R, _R, _I, _I] + [_P] * 5,
+    # the network-shape keys (include/trifinger_ppo_net.h: activation codes, d2rl)
+    "tfp_net_forward": _WALK, "tfp_net_backward": _WALK, "tfp_net_fits": [_P, _I, _I],
+    # the checkpoint evaluator (include/trifinger_ppo_eval.h: csrc/tf_eval.hip)
+    "tfp_eval_step": [_P] * 7 + [_I, _R, _R, _I, _I, _P], "tfp_eval_test_predicates": [_P, _I, _R, _R, _P, _P],
+    # episode ends (include/trifinger_ppo_episode.h)
+    "tfp_rollout_flags": [_P] * 3 + [_R, _L, _I] + [_P] * 4, "tfp_gae_ends": [_P] * 5 + [_I, _P, _P, _R, _R, _R, _I, _I] + [_P] * 6,
+    "tfp_ppo_loss_w": _LOSS, "tfp_ppo_loss_vclip_w": [_P] + _LOSS,
+    # the training-time episode tracker and the episode flight recorder (include/trifinger_ppo_track.h, include/trifinger_ppo_record.h: csrc/tf_eval.hip)
+    "tfp_rollout_track": [_P, _P], "tfp_record_step": [_P, _P],
+}
+
+
 def load():
+    """the library with every entry point of `_ARGTYPES` bound BY SYMBOL: a library built before one of them fails here, not with a fall-back"""
     global _LIB
     if _LIB is None:
         path = library_path()
         if not os.path.isfile(path):
             raise RuntimeError(f"{path} is missing: build it with `make -C leibnizgym_amd/csrc` (python __graft_entry__.py)")
         lib = C.CDLL(path)
-        lib.tfp_api_version.restype = C.c_int
-        lib.tfp_ppo_loss.restype = C.c_int
-        lib.tfp_ppo_loss.argtypes = [C.c_void_p] * 8 + [C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float] + [C.c_void_p] * 6
-        lib.tfp_clip_adam.restype = C.c_int
-        lib.tfp_clip_adam.argtypes = [C.c_void_p] * 4 + [C.c_int32, C.c_int32] + [C.c_void_p] * 3 + [C.c_float] * 5 + [C.c_void_p]
-        lib.tfp_linear_fwd.restype = C.c_int
-        lib.tfp_linear_fwd.argtypes = [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p]
-        lib.tfp_gemm_nn.restype = C.c_int
-        lib.tfp_gemm_nn.argtypes = [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_void_p]
-        lib.tfp_gemm_nn_dz.restype = C.c_int
-        lib.tfp_gemm_nn_dz.argtypes = [C.c_void_p] * 5 + [C.c_int32] * 3 + [C.c_void_p]
-        lib.tfp_gemm_nn_dz_group.restype = C.c_int
-        lib.tfp_gemm_nn_dz_group.argtypes = [C.c_void_p] * 8 + [C.c_int32, C.c_void_p]
-        lib.tfp_gemm_tn_bias.restype = C.c_int
-        lib.tfp_gemm_tn_bias.argtypes = [C.c_void_p] * 6 + [C.c_int32] * 4 + [C.c_void_p]
-        lib.tfp_gemm_tn_partials.restype = C.c_int
-        lib.tfp_gemm_tn_partials.argtypes = [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p]
-        lib.tfp_linear_fwd_group.restype = C.c_int
-        lib.tfp_linear_fwd_group.argtypes = [C.c_void_p] * 7 + [C.c_int32, C.c_int32, C.c_void_p]
-        lib.tfp_gemm_nn_group.restype = C.c_int
-        lib.tfp_gemm_nn_group.argtypes = [C.c_void_p] * 7 + [C.c_int32, C.c_void_p]
-        lib.tfp_gemm_tn_partials_group.restype = C.c_int
-        lib.tfp_gemm_tn_partials_group.argtypes = [C.c_void_p] * 7 + [C.c_int32, C.c_int32, C.c_void_p]
-        lib.tfp_sum_partials_multi.restype = C.c_int
-        lib.tfp_sum_partials_multi.argtypes = [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]
-        lib.tfp_rollout_record.restype = C.c_int
-        lib.tfp_rollout_record.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 5 + [C.c_int32, C.c_int32] + [C.c_void_p] * 7
-        lib.tfp_rollout_reward.restype = C.c_int
-        lib.tfp_rollout_reward.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.tfp_gae.restype = C.c_int
-        lib.tfp_gae.argtypes = [C.c_void_p] * 3 + [C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.tfp_gather_rows.restype = C.c_int
-        lib.tfp_gather_rows.argtypes = [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
-        lib.tfp_gemm_tn_partials_direct_chunk.restype = C.c_int
-        lib.tfp_gemm_tn_partials_direct_chunk.argtypes = []
-        lib.tfp_gemm_tn_partials_direct.restype = C.c_int
-        lib.tfp_gemm_tn_partials_direct.argtypes = [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]
-        lib.tfp_reset_state.restype = C.c_int
-        lib.tfp_reset_state.argtypes = [C.c_void_p]
-        for name in ("tfp_mlp_forward", "tfp_mlp_backward"):
-            getattr(lib, name).restype = C.c_int
-            getattr(lib, name).argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
-        # input normalisation (csrc/ppo_norm.hip and the walk variant): bound by symbol - a library built before them fails HERE, not with a fall-back
-        lib.tfp_moments_part_doubles.restype = C.c_int64
-        lib.tfp_moments_part_doubles.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
-        lib.tfp_moments.restype = C.c_int
-        lib.tfp_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-        lib.tfp_norm_merge.restype = C.c_int
-        lib.tfp_norm_merge.argtypes = [C.c_void_p] * 3 + [C.c_int32] * 3 + [C.c_void_p] * 3
-        lib.tfp_gather_rows_norm.restype = C.c_int
-        lib.tfp_gather_rows_norm.argtypes = [C.c_void_p] * 6 + [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
-        lib.tfp_mlp_forward_norm.restype = C.c_int
-        lib.tfp_mlp_forward_norm.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
-        # the value side (include/trifinger_ppo_value.h), bound by symbol like the normalisation
-        lib.tfp_ppo_loss_vclip.restype = C.c_int
-        lib.tfp_ppo_loss_vclip.argtypes = [C.c_void_p] * 9 + [C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float] + [C.c_void_p] * 6
-        lib.tfp_gae_vnorm.restype = C.c_int
-        lib.tfp_gae_vnorm.argtypes = [C.c_void_p] * 5 + [C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32] + [C.c_void_p] * 5
-        # the network-shape keys (include/trifinger_ppo_net.h: activation codes, d2rl), bound by symbol like the rest: a library built before them fails HERE
-        for name in ("tfp_net_forward", "tfp_net_backward"):
-            getattr(lib, name).restype = C.c_int
-            getattr(lib, name).argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
-        lib.tfp_net_fits.restype = C.c_int
-        lib.tfp_net_fits.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
-        # the checkpoint evaluator (include/trifinger_ppo_eval.h: csrc/tf_eval.hip), bound by symbol like the rest
-        lib.tfp_eval_step.restype = C.c_int
-        lib.tfp_eval_step.argtypes = [C.c_void_p] * 7 + [C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_void_p]
-        lib.tfp_eval_test_predicates.restype = C.c_int
-        lib.tfp_eval_test_predicates.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
-        # episode ends (include/trifinger_ppo_episode.h), bound by symbol like the rest
-        lib.tfp_rollout_flags.restype = C.c_int
-        lib.tfp_rollout_flags.argtypes = [C.c_void_p] * 3 + [C.c_float, C.c_int64, C.c_int32] + [C.c_void_p] * 4
-        lib.tfp_gae_ends.restype = C.c_int
-        lib.tfp_gae_ends.argtypes = [C.c_void_p] * 5 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32] + [C.c_void_p] * 6
-        lib.tfp_ppo_loss_w.restype = C.c_int
-        lib.tfp_ppo_loss_w.argtypes = lib.tfp_ppo_loss.argtypes
-        lib.tfp_ppo_loss_vclip_w.restype = C.c_int
-        lib.tfp_ppo_loss_vclip_w.argtypes = lib.tfp_ppo_loss_vclip.argtypes
-        # the training-time episode tracker (include/trifinger_ppo_track.h: csrc/tf_eval.hip), bound by symbol like the rest
-        lib.tfp_rollout_track.restype = C.c_int
-        lib.tfp_rollout_track.argtypes = [C.c_void_p, C.c_void_p]
-        # the episode flight recorder (include/trifinger_ppo_record.h: csrc/tf_eval.hip), bound by symbol like the rest
-        lib.tfp_record_step.restype = C.c_int
-        lib.tfp_record_step.argtypes = [C.c_void_p, C.c_void_p]
+        for name, argtypes in _ARGTYPES.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = (C.c_int64 if name == "tfp_moments_part_doubles" else C.c_int), argtypes
         _LIB = lib
     return _LIB
 
@@ -126,16 +79,7 @@ def _chk(rc, what):
 class _FusedPPOLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, mu, log_std, v, act, old_nlp, adv, ret, old_mu, stats, e_clip, v_coef, ent_coef, bounds_coef):
-        lib = load()
-        mu, v = mu.contiguous(), v.contiguous()
-        B, A = mu.shape
-        d_mu, d_v = torch.empty_like(mu), torch.empty_like(v)
-        out = torch.empty(A + 1, device=mu.device, dtype=torch.float32)      # d_logstd [A] and the loss, zeroed by one fill
-        d_ls, loss = out[:A], out[A]
-        _chk(lib.tfp_ppo_loss(mu.data_ptr(), log_std.data_ptr(), act.data_ptr(), old_nlp.data_ptr(), adv.data_ptr(), old_mu.data_ptr(),
-                              v.data_ptr(), ret.data_ptr(), B, A, e_clip, v_coef, ent_coef, bounds_coef,
-                              d_mu.data_ptr(), d_v.data_ptr(), d_ls.data_ptr(), loss.data_ptr(), stats.data_ptr(), _stream(mu)),
-             "tfp_ppo_loss")
+        loss, d_mu, d_v, d_ls = ppo_loss_and_grads(mu, log_std, v, act, old_nlp, adv, ret, old_mu, stats, e_clip, v_coef, ent_coef, bounds_coef)
         ctx.save_for_backward(d_mu, d_v, d_ls)
         return loss
 
@@ -143,6 +87,10 @@ class _FusedPPOLoss(torch.autograd.Function):
     def backward(ctx, g):
         d_mu, d_v, d_ls = ctx.saved_tensors
         return d_mu * g, d_ls * g, d_v * g, None, None, None, None, None, None, None, None, None, None
+
+
+# the objective's entry point by (old_v given, adv_w given); the clip variants take old_v behind `ret`
+_LOSS_ENTRY = {(False, False): "tfp_ppo_loss", (True, False): "tfp_ppo_loss_vclip", (False, True): "tfp_ppo_loss_w", (True, True): "tfp_ppo_loss_vclip_w"}
 
 
 def ppo_loss_and_grads(mu, log_std, v, act, old_nlp, adv, ret, old_mu, stats, e_clip, v_coef, ent_coef, bounds_coef, d_ls_out=None, old_v=None, adv_w=None):
@@ -157,19 +105,15 @@ def ppo_loss_and_grads(mu, log_std, v, act, old_nlp, adv, ret, old_mu, stats, e_
     if adv_w is not None:
         assert adv is None and adv_w.dtype == torch.float32 and adv_w.is_contiguous() and tuple(adv_w.shape) == (B, 2) and adv_w.device == mu.device
         adv = adv_w
-    fn, fn_clip, tag = (lib.tfp_ppo_loss, lib.tfp_ppo_loss_vclip, "") if adv_w is None else (lib.tfp_ppo_loss_w, lib.tfp_ppo_loss_vclip_w, "_w")
-    d_mu, d_v = torch.empty_like(mu), torch.empty_like(v)
-    out = torch.empty(A + 1, device=mu.device, dtype=torch.float32)
-    d_ls, loss = (out[:A] if d_ls_out is None else d_ls_out), out[A]      # d_ls_out: e.g. the parameter's slot of a flat gradient buffer
     if old_v is not None:
         assert old_v.dtype == torch.float32 and old_v.is_contiguous() and old_v.numel() == B and old_v.device == mu.device
-        _chk(fn_clip(mu.data_ptr(), log_std.data_ptr(), act.data_ptr(), old_nlp.data_ptr(), adv.data_ptr(), old_mu.data_ptr(),
-                     v.data_ptr(), ret.data_ptr(), old_v.data_ptr(), B, A, float(e_clip), float(v_coef), float(ent_coef), float(bounds_coef),
-                     d_mu.data_ptr(), d_v.data_ptr(), d_ls.data_ptr(), loss.data_ptr(), stats.data_ptr(), _stream(mu)), "tfp_ppo_loss_vclip" + tag)
-        return loss, d_mu, d_v, d_ls
-    _chk(fn(mu.data_ptr(), log_std.data_ptr(), act.data_ptr(), old_nlp.data_ptr(), adv.data_ptr(), old_mu.data_ptr(),
-            v.data_ptr(), ret.data_ptr(), B, A, float(e_clip), float(v_coef), float(ent_coef), float(bounds_coef),
-            d_mu.data_ptr(), d_v.data_ptr(), d_ls.data_ptr(), loss.data_ptr(), stats.data_ptr(), _stream(mu)), "tfp_ppo_loss" + tag)
+    d_mu, d_v = torch.empty_like(mu), torch.empty_like(v)
+    out = torch.empty(A + 1, device=mu.device, dtype=torch.float32)      # d_logstd [A] and the loss
+    d_ls, loss = (out[:A] if d_ls_out is None else d_ls_out), out[A]      # d_ls_out: e.g. the parameter's slot of a flat gradient buffer
+    name = _LOSS_ENTRY[old_v is not None, adv_w is not None]
+    _chk(getattr(lib, name)(mu.data_ptr(), log_std.data_ptr(), act.data_ptr(), old_nlp.data_ptr(), adv.data_ptr(), old_mu.data_ptr(), v.data_ptr(), ret.data_ptr(),
+                            *((old_v.data_ptr(),) if old_v is not None else ()), B, A, float(e_clip), float(v_coef), float(ent_coef), float(bounds_coef),
+                            d_mu.data_ptr(), d_v.data_ptr(), d_ls.data_ptr(), loss.data_ptr(), stats.data_ptr(), _stream(mu)), name)
     return loss, d_mu, d_v, d_ls
 
 
@@ -715,31 +659,12 @@ def mfma_linear(x, w, b, act, grad_out=None):
 # ---- the two MLPs without autograd: forward keeps the layer outputs, backward walks them in reverse --------------------------------
 def mlp_forward(x, layers):
     """`layers`: [(weight, bias, act, grad_out)] in order.  Returns the list of layer outputs (the last one is the network output);
-    the inputs of the layers are `x` and the outputs before them."""
+    the inputs of the layers are `x` and the outputs before them.  The per-layer tier itself: one launch per layer, ELU / none only."""
     ys = []
     for w, b, act, _ in layers:
         x = linear_fwd(x, w, b, act)
         ys.append(x)
     return ys
-
-
-def mlp_backward(x, ys, gy, layers):
-    """gradients of every layer's weight and bias into its `grad_out` buffers (chunk sums deferred: call flush_partial_sums() after the
-    last network), given the gradient `gy` of the network output; the input gradient of the first layer is not formed"""
-    # gy is the gradient of layer k's OUTPUT at the top of the walk and the dZ of layer k - already times elu'(ys[k]) - below it: every input-gradient
-    # product leaves multiplied by the activation derivative of the layer it is the gradient of (tfp_gemm_nn_dz), so the two products that consume it
-    # stage plain operands.  Same bits as multiplying in their operand loads (one fp32 product either way).
-    if needs_net_walk(layers):
-        raise ValueError("the per-layer kernels form ELU's derivative or none: a network with another activation or with d2rl runs on the network walk or on torch")
-    is_dz = False
-    for k in range(len(layers) - 1, -1, -1):
-        w, _, act, grad_out = layers[k]
-        inp = ys[k - 1] if k > 0 else x
-        yy = ys[k] if (act and not is_dz) else None
-        gemm_tn_bias(gy, inp, yy, out=grad_out, defer=True)
-        if k > 0:
-            gy = gemm_nn(gy, w, yy, y_out=ys[k - 1] if layers[k - 1][2] else None)
-            is_dz = True
 
 
 # ---- the network walk (csrc/ppo_mlp_walk.hip): all layers of up to two networks in ONE launch per direction ------------------------------------
@@ -750,6 +675,16 @@ class TfpMlp(C.Structure):
     """include/trifinger_ppo.h: TfpMlp"""
     _fields_ = [("x", C.c_void_p), ("W", C.c_void_p * WALK_MAXL), ("b", C.c_void_p * WALK_MAXL), ("yin", C.c_void_p * WALK_MAXL),
                 ("y", C.c_void_p * WALK_MAXL), ("dim", C.c_int32 * (WALK_MAXL + 1)), ("act", C.c_int32 * WALK_MAXL), ("n_layers", C.c_int32)]
+
+
+class TfpNet(C.Structure):
+    """include/trifinger_ppo_net.h: TfpNet"""
+    _fields_ = [("mlp", TfpMlp), ("d2rl", C.c_int32), ("clip", C.c_float), ("mean", C.c_void_p), ("inv_std", C.c_void_p)]
+
+
+class TfpNorm(C.Structure):
+    """include/trifinger_ppo_norm.h: TfpNorm"""
+    _fields_ = [("mean", C.c_void_p), ("inv_std", C.c_void_p), ("clip", C.c_float)]
 
 
 # activation codes of include/trifinger_ppo_net.h (0 and 1 are the ones every kernel knows); swish and gelu have none (ACT_NO_KERNEL)
@@ -783,38 +718,61 @@ def _out_width(layers, l):
     return layers[l][0].shape[0] + (layers[0][0].shape[1] if (_d2rl(layers) and l <= len(layers) - 3) else 0)
 
 
-class TfpNet(C.Structure):
-    """include/trifinger_ppo_net.h: TfpNet"""
-    _fields_ = [("mlp", TfpMlp), ("d2rl", C.c_int32), ("clip", C.c_float), ("mean", C.c_void_p), ("inv_std", C.c_void_p)]
+def _walk_blocks(nets, ext, norms=None, check=False):
+    """the walk's argument blocks, the ONE place that fills them: nets = [(x or gy or None, layers, y, yin)] with y / yin the per-layer tensors (or None)
+    behind TfpMlp.y / .yin.  An array of TfpMlp, each wrapped in a TfpNet (d2rl, the statistics `norms[i]`) when the extended entry point is taken.
+    `check`: the weights' widths against the network description (a ValueError)"""
+    arr = ((TfpNet if ext else TfpMlp) * len(nets))()
+    for i, (x, layers, y, yin) in enumerate(nets):
+        net = arr[i]
+        m = net.mlp if ext else net
+        m.x = x.data_ptr() if x is not None else None
+        m.n_layers = len(layers)
+        m.dim[0] = layers[0][0].shape[1]
+        for l, (w, b, act, _) in enumerate(layers):
+            m.W[l], m.b[l] = w.data_ptr(), (b.data_ptr() if b is not None else None)
+            m.dim[l + 1], m.act[l] = w.shape[0], int(act)
+            if y is not None and l < len(y) and y[l] is not None:
+                m.y[l] = y[l].data_ptr()
+            if yin is not None and l < len(yin):
+                m.yin[l] = yin[l].data_ptr()
+            if check and w.shape[1] != (_out_width(layers, l - 1) if l > 0 else m.dim[0]):
+                raise ValueError(f"weight of layer {l} has {w.shape[1]} columns, the network description gives {_out_width(layers, l - 1) if l > 0 else m.dim[0]}")
+        if ext:
+            net.d2rl = 1 if _d2rl(layers) else 0
+            if norms is not None and norms[i] is not None:
+                net.mean, net.inv_std, net.clip = norms[i][0].data_ptr(), norms[i][1].data_ptr(), float(norms[i][2])
+    return arr
 
 
-def _net_struct(m, layers, norm=None):
-    n = TfpNet()
-    n.mlp, n.d2rl = m, 1 if _d2rl(layers) else 0
-    if norm is not None:
-        n.mean, n.inv_std, n.clip = norm[0].data_ptr(), norm[1].data_ptr(), float(norm[2])
-    return n
+# the walk's entry point by (direction, extended, statistics given).  The plain kernels keep their own argument block and entry points on purpose: their
+# timing is what DESIGN.md section 9 item 1 rests on
+_WALK_ENTRY = {("forward", False, False): "tfp_mlp_forward", ("forward", False, True): "tfp_mlp_forward_norm", ("forward", True, False): "tfp_net_forward",
+               ("forward", True, True): "tfp_net_forward", ("backward", False, False): "tfp_mlp_backward", ("backward", True, False): "tfp_net_backward"}
 
 
-def _shape_struct(layers):
-    m = TfpMlp()
-    m.n_layers = len(layers)
-    m.dim[0] = layers[0][0].shape[1]
-    for l, (w, _, act, _) in enumerate(layers):
-        m.dim[l + 1] = w.shape[0]
-        m.act[l] = int(act)
-        if w.shape[1] != (_out_width(layers, l - 1) if l > 0 else m.dim[0]):
-            raise ValueError(f"weight of layer {l} has {w.shape[1]} columns, the network description gives {_out_width(layers, l - 1) if l > 0 else m.dim[0]}")
-    return m
+def _walk_launch(direction, nets, ext, norms, M, stream):
+    """ONE launch of the walk over `nets` (as _walk_blocks takes them); False when the kernel declines the shapes"""
+    name = _WALK_ENTRY[direction, bool(ext), norms is not None]
+    args = [C.cast(_walk_blocks(nets, ext, norms, check=ext and direction == "forward"), C.c_void_p)]
+    if norms is not None and not ext:                               # the plain walk takes the statistics as a block of their own
+        nm = (TfpNorm * len(nets))()
+        for i, e in enumerate(norms):
+            if e is not None:
+                nm[i].mean, nm[i].inv_std, nm[i].clip = e[0].data_ptr(), e[1].data_ptr(), float(e[2])
+        args.append(C.cast(nm, C.c_void_p))
+    rc = getattr(load(), name)(*args, len(nets), M, stream)
+    if rc == -4:
+        return False
+    _chk(rc, name)
+    return True
 
 
 def net_fits(layer_lists, backward=False):
     """whether the SHAPES of one or two networks (LayerLists; activation codes 0 .. 6) fit the network walk in the given direction: tfp_net_fits, no launch"""
     if not (0 < len(layer_lists) <= 2) or any(not (0 < len(l) <= WALK_MAXL) or any(not (0 <= int(e[2]) <= 6) for e in l) for l in layer_lists):
         return False
-    arr = (TfpNet * len(layer_lists))()
-    for i, layers in enumerate(layer_lists):
-        arr[i] = _net_struct(_shape_struct(layers), layers)
+    arr = _walk_blocks([(None, layers, None, None) for layers in layer_lists], True, check=True)
     rc = load().tfp_net_fits(C.cast(arr, C.c_void_p), len(layer_lists), 1 if backward else 0)
     if rc == -4:
         return False
@@ -822,27 +780,9 @@ def net_fits(layer_lists, backward=False):
     return True
 
 
-def _walk_struct(x, layers):
-    m = TfpMlp()
-    m.x = x.data_ptr()
-    m.n_layers = len(layers)
-    m.dim[0] = layers[0][0].shape[1]
-    for l, (w, b, act, _) in enumerate(layers):
-        m.W[l] = w.data_ptr()
-        m.b[l] = b.data_ptr() if b is not None else None
-        m.dim[l + 1] = w.shape[0]
-        m.act[l] = int(act)
-    return m
-
-
 def _walkable(nets):
     return (0 < len(nets) <= 2 and all(0 < len(layers) <= WALK_MAXL for _, layers in nets)
             and all(x.dim() == 2 and x.is_contiguous() and x.shape[0] == nets[0][0].shape[0] for x, _ in nets))
-
-
-class TfpNorm(C.Structure):
-    """include/trifinger_ppo_norm.h: TfpNorm"""
-    _fields_ = [("mean", C.c_void_p), ("inv_std", C.c_void_p), ("clip", C.c_float)]
 
 
 def mlp_walk_forward(nets, store_hidden=True, norms=None, ext=None):
@@ -861,36 +801,10 @@ def mlp_walk_forward(nets, store_hidden=True, norms=None, ext=None):
     if norms is not None and not (len(norms) == len(nets) and all(e is None or _norm_ok(e, x.shape[1], x.device) for e, (x, _) in zip(norms, nets))):
         return None
     M = nets[0][0].shape[0]
-    arr = (TfpMlp * len(nets))()
-    outs = []
-    for i, (x, layers) in enumerate(nets):
-        m = _walk_struct(x, layers)
-        ys = []
-        for l, (w, _, _, _) in enumerate(layers):
-            keep = store_hidden or l == len(layers) - 1
-            y = torch.empty(M, _out_width(layers, l) if ext else w.shape[0], device=x.device, dtype=torch.float32) if keep else None
-            m.y[l] = y.data_ptr() if keep else None
-            ys.append(y)
-        arr[i] = m
-        outs.append(ys)
-    if ext:
-        ea = (TfpNet * len(nets))()
-        for i, (_, layers) in enumerate(nets):
-            _shape_struct(layers)                                    # the width check
-            ea[i] = _net_struct(arr[i], layers, norms[i] if norms is not None else None)
-        rc = load().tfp_net_forward(C.cast(ea, C.c_void_p), len(nets), M, _stream(nets[0][0]))
-    elif norms is not None:
-        nm = (TfpNorm * len(nets))()
-        for i, e in enumerate(norms):
-            if e is not None:
-                nm[i].mean, nm[i].inv_std, nm[i].clip = e[0].data_ptr(), e[1].data_ptr(), float(e[2])
-        rc = load().tfp_mlp_forward_norm(C.cast(arr, C.c_void_p), C.cast(nm, C.c_void_p), len(nets), M, _stream(nets[0][0]))
-    else:
-        rc = load().tfp_mlp_forward(C.cast(arr, C.c_void_p), len(nets), M, _stream(nets[0][0]))
-    if rc == -4:
-        return None
-    _chk(rc, "tfp_net_forward" if ext else ("tfp_mlp_forward_norm" if norms is not None else "tfp_mlp_forward"))
-    return outs
+    outs = [[torch.empty(M, _out_width(layers, l) if ext else w.shape[0], device=x.device, dtype=torch.float32)
+             if (store_hidden or l == len(layers) - 1) else None for l, (w, _, _, _) in enumerate(layers)] for x, layers in nets]
+    blocks = [(x, layers, ys, None) for (x, layers), ys in zip(nets, outs)]
+    return outs if _walk_launch("forward", blocks, ext, norms, M, _stream(nets[0][0])) else None
 
 
 def mlp_walk_backward(nets, ext=None):
@@ -901,67 +815,50 @@ def mlp_walk_backward(nets, ext=None):
     if ext is None:
         ext = any(needs_net_walk(layers) for _, _, layers in nets)
     M = nets[0][0].shape[0]
-    arr = (TfpMlp * len(nets))()
-    outs = []
-    for i, (gy, ys, layers) in enumerate(nets):
+    outs, blocks = [], []
+    for gy, ys, layers in nets:
         gy = gy if gy.is_contiguous() else gy.contiguous()
-        m = _walk_struct(gy, layers)
-        dz = []
-        for l in range(len(layers) - 1):
-            if not ext:
-                d = torch.empty_like(ys[l])
-            else:                                                    # dZ covers the hidden part only; ys[l] may be the wide rows [h | x]
-                if tuple(ys[l].shape) != (M, _out_width(layers, l)) or not ys[l].is_contiguous():
-                    raise ValueError(f"saved output of layer {l}: {tuple(ys[l].shape)}, contiguous {ys[l].is_contiguous()}; the walk stored and reads "
-                                     f"({M}, {_out_width(layers, l)}) contiguous")
-                d = torch.empty(M, layers[l][0].shape[0], device=gy.device, dtype=torch.float32)
-            m.y[l] = d.data_ptr()
-            m.yin[l] = ys[l].data_ptr()
-            dz.append(d)
-        dz.append(gy)
-        arr[i] = m
-        outs.append(dz)
-    if ext:
-        ea = (TfpNet * len(nets))()
-        for i, (_, _, layers) in enumerate(nets):
-            ea[i] = _net_struct(arr[i], layers)
-        rc = load().tfp_net_backward(C.cast(ea, C.c_void_p), len(nets), M, _stream(nets[0][0]))
-    else:
-        rc = load().tfp_mlp_backward(C.cast(arr, C.c_void_p), len(nets), M, _stream(nets[0][0]))
-    if rc == -4:
-        return None
-    _chk(rc, "tfp_net_backward" if ext else "tfp_mlp_backward")
-    return outs
+        for l in range(len(layers) - 1 if ext else 0):               # dZ covers the hidden part only; ys[l] may be the wide rows [h | x]
+            if tuple(ys[l].shape) != (M, _out_width(layers, l)) or not ys[l].is_contiguous():
+                raise ValueError(f"saved output of layer {l}: {tuple(ys[l].shape)}, contiguous {ys[l].is_contiguous()}; the walk stored and reads "
+                                 f"({M}, {_out_width(layers, l)}) contiguous")
+        dz = [torch.empty(M, layers[l][0].shape[0], device=gy.device, dtype=torch.float32) if ext else torch.empty_like(ys[l]) for l in range(len(layers) - 1)]
+        blocks.append((gy, layers, dz, ys[:len(layers) - 1]))
+        outs.append(dz + [gy])
+    return outs if _walk_launch("backward", blocks, ext, None, M, _stream(nets[0][0])) else None
 
 
 USE_WALK = True       # tools / tests switch it off to time or check the per-layer launches
 
 
-# ---- the actor and the central value network side by side: layer k of both in one launch, all weight gradients in two ----------------------
+# ---- the ONE place that decides how networks run: the walk, else grouped or per-layer launches (plain torch is decided by the caller: ppo.ActorCritic) ----
+_WALK_ONLY = "a network with an activation other than ELU or with d2rl runs on the network walk only, and the walk declined these shapes"
+
+
 def _pairable(la, lc):
     return len(la) == len(lc) and all(a[2] == c[2] for a, c in zip(la, lc))
 
 
-def mlp_forward_pair(xa, la, xc, lc, store_hidden=True, norms=None):
-    """the forward of two networks over the same rows: ONE launch on the network walk (any activation code, d2rl: LayerLists), else - Linear / ELU stacks
-    of the same depth and activations only - one grouped launch per layer (4 launches instead of 8 for the trainer's MLPs).
-    `norms` = (actor's, critic's), each None or (mean_f, inv_std_f, clip): the inputs are RAW and normalised on the way in - inside the walk, or by one
-    normalize_rows launch per network in front of the per-layer path."""
+def forward_nets(nets, store_hidden=True, norms=None):
+    """the forward of one or two networks [(x, layers)] over the same rows; returns the list of layer outputs per network.  In this order: ONE launch on the
+    network walk (any activation code, d2rl: LayerLists); a network that needs the walk and was declined raises - the per-layer launches are ELU / none
+    stacks and are never applied to a network that asked for something else (the trainer asks net_fits() once and runs such a network on torch); else the
+    per-layer tier - two Linear / ELU stacks of the same depth and activations one grouped launch per layer (4 launches instead of 8 for the trainer's
+    MLPs), anything else layer by layer.  `norms`: per network None or (mean_f, inv_std_f, clip): the inputs are RAW and normalised on the way in - inside
+    the walk, or by one normalize_rows launch per network in front of the per-layer tier."""
     if norms is not None and not any(e is not None for e in norms):
         norms = None
     if USE_WALK:
-        out = mlp_walk_forward([(xa, la), (xc, lc)], store_hidden, norms)
+        out = mlp_walk_forward(nets, store_hidden, norms)
         if out is not None:
-            return out[0], out[1]
-    if needs_net_walk(la) or needs_net_walk(lc):
-        # the per-layer launches are ELU / none stacks: never applied to a network that asked for something else (the trainer asks net_fits() once and runs
-        # such a network on torch when the walk declines it)
-        raise RuntimeError("a network with an activation other than ELU or with d2rl runs on the network walk only, and the walk declined these shapes")
+            return out
+    if any(needs_net_walk(layers) for _, layers in nets):
+        raise RuntimeError(_WALK_ONLY)
     if norms is not None:
-        xa = normalize_rows(xa, *norms[0]) if norms[0] is not None else xa
-        xc = normalize_rows(xc, *norms[1]) if norms[1] is not None else xc
-    if not _pairable(la, lc):
-        return mlp_forward(xa, la), mlp_forward(xc, lc)
+        nets = [(normalize_rows(x, *e) if e is not None else x, layers) for (x, layers), e in zip(nets, norms)]
+    if len(nets) != 2 or not _pairable(nets[0][1], nets[1][1]):
+        return [mlp_forward(x, layers) for x, layers in nets]
+    (xa, la), (xc, lc) = nets
     ya, yc = [], []
     for (wa, ba, act, _), (wc, bc, _, _) in zip(la, lc):
         out = linear_fwd_group([xa, xc], [wa, wc], [ba, bc], act)
@@ -969,55 +866,83 @@ def mlp_forward_pair(xa, la, xc, lc, store_hidden=True, norms=None):
             out = [linear_fwd(xa, wa, ba, act), linear_fwd(xc, wc, bc, act)]
         xa, xc = out
         ya.append(xa); yc.append(xc)
+    return [ya, yc]
+
+
+def mlp_forward_pair(xa, la, xc, lc, store_hidden=True, norms=None):
+    """forward_nets of the actor and the central value network side by side; `norms` = (actor's, critic's)"""
+    ya, yc = forward_nets([(xa, la), (xc, lc)], store_hidden, norms)
     return ya, yc
 
 
-def mlp_backward_pair(xa, ya, gya, la, xc, yc, gyc, lc):
-    """mlp_backward of both networks: the input-gradient products of layer k of both in one launch, and ALL weight / bias gradient products of the
-    step in two launches (layers with an ELU, layers without) behind them - 5 launches instead of 14 for the trainer's MLPs.  Chunk sums deferred
-    as in mlp_backward: call flush_partial_sums() afterwards."""
-    if USE_WALK:
-        dz = mlp_walk_backward([(gya, ya, la), (gyc, yc, lc)])
-        if dz is not None:
-            # every dZ is in memory: all weight / bias gradients of the step are plain products dZ_l^T [input_l | 1] = one grouped launch
-            gys, inps, outs = [], [], []
-            for net_x, net_y, d, layers in ((xa, ya, dz[0], la), (xc, yc, dz[1], lc)):
-                for k in range(len(layers) - 1, -1, -1):
-                    gys.append(d[k]); inps.append(net_y[k - 1] if k > 0 else net_x); outs.append(layers[k][3])
-            for i in range(0, len(gys), 8):
-                sl = slice(i, i + 8)
-                if USE_DIRECT_DW and gemm_tn_bias_direct(gys[sl], inps[sl], outs[sl]):
-                    continue
-                if not gemm_tn_bias_group(gys[sl], inps[sl], None, outs[sl]):
-                    for g, x, o in zip(gys[sl], inps[sl], outs[sl]):
-                        gemm_tn_bias(g, x, None, out=o, defer=True)
-            return
-    if needs_net_walk(la) or needs_net_walk(lc):
-        raise RuntimeError("a network with an activation other than ELU or with d2rl runs on the network walk only, and the walk declined these shapes")
-    if not _pairable(la, lc):
-        mlp_backward(xa, ya, gya, la)
-        mlp_backward(xc, yc, gyc, lc)
-        return
+def _weight_grads(gys, inps, ys, outs, direct=False, grouped=True):
+    """the tail of a backward pass: the weight / bias gradient products (gy or dZ, layer input, grad_out) of the parallel lists, eight per launch - the
+    direct kernel (`direct`: every dZ is plain) -> one grouped launch -> one by one.  ys: None, or per product the ELU output whose derivative the operand
+    load forms.  Chunk sums deferred: flush_partial_sums()"""
+    for i in range(0, len(gys), 8):
+        sl = slice(i, i + 8)
+        if direct and USE_DIRECT_DW and gemm_tn_bias_direct(gys[sl], inps[sl], outs[sl]):
+            continue
+        if not (grouped and gemm_tn_bias_group(gys[sl], inps[sl], ys[sl] if ys is not None else None, outs[sl])):
+            for k in range(i, min(i + 8, len(gys))):
+                gemm_tn_bias(gys[k], inps[k], ys[k] if ys is not None else None, out=outs[k], defer=True)
+
+
+def _backward_per_layer(nets):
+    """the per-layer tier of backward_nets for one network or two pairable ones: the input-gradient product of layer k (of both in one launch), and the
+    weight / bias gradient products behind them in two groups - operand load with elu', and without: their bits differ"""
+    # gy is the gradient of layer k's OUTPUT at the top of the walk and the dZ of layer k - already times elu'(ys[k]) - below it: every input-gradient
+    # product leaves multiplied by the activation derivative of the layer it is the gradient of (tfp_gemm_nn_dz), so the two products that consume it
+    # stage plain operands.  Same bits as multiplying in their operand loads (one fp32 product either way).
+    pair, acts = len(nets) == 2, [l[2] for l in nets[0][3]]
+    gys = [gy for _, _, gy, _ in nets]
     dw = {True: ([], [], [], []), False: ([], [], [], [])}          # the operand load multiplies by elu' -> (gy, input, y, grad_out)
-    is_dz = False                                                    # as in mlp_backward: below the top layer gy arrives as dZ
-    for k in range(len(la) - 1, -1, -1):
-        act = la[k][2] and not is_dz
-        for net_x, net_y, gy, layers in ((xa, ya, gya, la), (xc, yc, gyc, lc)):
-            inp = net_y[k - 1] if k > 0 else net_x
-            slot = dw[bool(act)]
-            slot[0].append(gy); slot[1].append(inp); slot[2].append(net_y[k] if act else None); slot[3].append(layers[k][3])
+    is_dz = False
+    for k in range(len(acts) - 1, -1, -1):
+        act = bool(acts[k] and not is_dz)
+        for (x, ys, _, layers), gy in zip(nets, gys):
+            slot = dw[act]
+            slot[0].append(gy); slot[1].append(ys[k - 1] if k > 0 else x); slot[2].append(ys[k]); slot[3].append(layers[k][3])
         if k > 0:
-            yy = [ya[k], yc[k]] if act else None
-            eo = [ya[k - 1], yc[k - 1]] if la[k - 1][2] else None
-            out = gemm_nn_group([gya, gyc], [la[k][0], lc[k][0]], yy, eo)
+            ws = [layers[k][0] for _, _, _, layers in nets]
+            yy = [ys[k] if act else None for _, ys, _, _ in nets]
+            eo = [ys[k - 1] if acts[k - 1] else None for _, ys, _, _ in nets]
+            out = gemm_nn_group(gys, ws, yy if act else None, eo if acts[k - 1] else None) if pair else None
             if out is None:
-                out = [gemm_nn(gya, la[k][0], ya[k] if act else None, y_out=eo[0] if eo else None),
-                       gemm_nn(gyc, lc[k][0], yc[k] if act else None, y_out=eo[1] if eo else None)]
-            gya, gyc = out
-            is_dz = True
-    for has_elu, (gys, inps, ys, outs) in dw.items():
-        for i in range(0, len(gys), 8):
-            sl = slice(i, i + 8)
-            if not gemm_tn_bias_group(gys[sl], inps[sl], ys[sl] if has_elu else None, outs[sl]):
-                for g, x, y, o in zip(gys[sl], inps[sl], ys[sl], outs[sl]):
-                    gemm_tn_bias(g, x, y, out=o, defer=True)
+                out = [gemm_nn(gy, w, y, y_out=e) for gy, w, y, e in zip(gys, ws, yy, eo)]
+            gys, is_dz = out, True
+    for has_elu, (g, inps, ys, outs) in dw.items():
+        _weight_grads(g, inps, ys if has_elu else None, outs, grouped=pair)
+
+
+def backward_nets(nets, walk=True):
+    """gradients of every layer's weight and bias of one or two networks [(x, ys, gy, layers)] into the layers' `grad_out` buffers, given the gradient
+    `gy` of each network output; the input gradient of the first layer is not formed.  The counterpart of forward_nets, same order: the walk - ONE launch
+    for every dZ, then all weight / bias gradients of the step as plain products dZ_l^T [input_l | 1] -, the refusal, the per-layer tier (5 launches
+    instead of 14 for the trainer's MLPs).  Chunk sums deferred: call flush_partial_sums() afterwards."""
+    if walk and USE_WALK:
+        dz = mlp_walk_backward([(gy, ys, layers) for _, ys, gy, layers in nets])
+        if dz is not None:
+            gys, inps, outs = [], [], []
+            for (x, ys, _, layers), d in zip(nets, dz):
+                for k in range(len(layers) - 1, -1, -1):
+                    gys.append(d[k]); inps.append(ys[k - 1] if k > 0 else x); outs.append(layers[k][3])
+            _weight_grads(gys, inps, None, outs, direct=True)
+            return
+    if any(needs_net_walk(layers) for _, _, _, layers in nets):
+        raise RuntimeError(_WALK_ONLY)
+    if len(nets) == 2 and not _pairable(nets[0][3], nets[1][3]):
+        for net in nets:
+            _backward_per_layer([net])
+        return
+    _backward_per_layer(nets)
+
+
+def mlp_backward_pair(xa, ya, gya, la, xc, yc, gyc, lc):
+    """backward_nets of the actor and the central value network side by side"""
+    backward_nets([(xa, ya, gya, la), (xc, yc, gyc, lc)])
+
+
+def mlp_backward(x, ys, gy, layers):
+    """backward_nets of one network on the per-layer launches (the walk is not asked)"""
+    backward_nets([(x, ys, gy, layers)], walk=False)

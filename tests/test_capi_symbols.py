@@ -175,6 +175,32 @@ def test_ppo_library_exports_every_symbol_its_header_declares():
         assert getattr(bound, n).restype is C.c_int, n
 
 
+def test_ppo_binding_covers_every_declared_entry_point_with_its_argument_count():
+    """every tfp_* function declared in ANY include/trifinger_ppo*.h header is exported by libtrifinger_ppo.so and bound by ppo_kernels.load() with as many
+    argument types as the declaration has parameters (no GPU needed: the library only has to load)."""
+    import glob
+    from leibnizgym_amd import ppo_kernels as pk
+    decls = {}
+    headers = sorted(glob.glob(os.path.join(REPO, "include", "trifinger_ppo*.h")))
+    assert len(headers) >= 8, headers
+    for h in headers:
+        src = re.sub(r"/\*.*?\*/", "", open(h).read(), flags=re.S)
+        for name, params in re.findall(r"\b(tfp_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+            params = params.strip()
+            decls[name] = 0 if params in ("", "void") else params.count(",") + 1
+    assert len(decls) >= 40 and decls["tfp_api_version"] == 0 and decls["tfp_ppo_loss"] == 20 and decls["tfp_ppo_loss_vclip_w"] == 21, decls
+    path = pk.library_path()
+    if not os.path.isfile(path):
+        subprocess.check_call(["make", "-C", os.path.dirname(path), "-s"])
+    raw, bound = C.CDLL(path), pk.load()
+    for name, count in sorted(decls.items()):
+        assert hasattr(raw, name), f"{name} is declared but not exported"
+        fn = getattr(bound, name)
+        assert fn.argtypes is not None, f"{name}: load() sets no argtypes"
+        assert len(fn.argtypes) == count, f"{name}: {len(fn.argtypes)} argument types bound, {count} parameters declared"
+        assert fn.restype is (C.c_int64 if name == "tfp_moments_part_doubles" else C.c_int), name
+
+
 def test_developer_library_refuses_what_it_does_not_carry():
     """variants/libtf_min.so carries the headline kernels only: tf_create answers TF_ERR_UNSUPPORTED for the extended domain randomisation, the
     general box and the surface normal of the cube corners (refused before any device allocation: no GPU needed)."""

@@ -553,3 +553,34 @@ def test_rollout_bookkeeping_kernels_hold_the_bits_of_the_torch_expressions(hip)
         adv[t] = last
     got_adv, got_ret = pk.gae(rews, dones, vals, gamma, tau)
     assert torch.equal(got_adv, adv) and torch.equal(got_ret, adv + vals[:T])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("use_walk", [True, False])
+@pytest.mark.parametrize("with_stats", [False, True])
+@pytest.mark.parametrize("dims", [[41, 48, 20, 9], [41, 420, 9]])
+def test_one_network_forward_runner_is_its_definition_bit_for_bit(hip, monkeypatch, dims, with_stats, use_walk):
+    """forward_nets with ONE network (what ActorCritic.mean_action calls), 33 rows: where the walk takes the call - 41 -> 48 -> 20 -> 9, USE_WALK on - the
+    result is mlp_walk_forward called directly; everywhere else - USE_WALK off, or 41 -> 420 -> 9, a layer wider than 416, which the walk declines - it
+    is mlp_forward(normalize_rows(x), layers)[-1].  Identical bits, with and without statistics.  A network only the walk runs (activation code 3) that
+    the walk declines raises."""
+    dev = "cuda:0"
+    g = torch.Generator(device=dev).manual_seed(sum(dims))
+    r = lambda *s: torch.randn(*s, device=dev, generator=g)                                   # noqa: E731
+    n = len(dims) - 1
+    layers = [(r(dims[i + 1], dims[i]) * dims[i] ** -0.5, r(dims[i + 1]) * 0.3, 1 if i < n - 1 else 0, None) for i in range(n)]
+    x = r(33, dims[0]) * 2.0 + 0.5
+    stats = (r(dims[0]) * 0.5, torch.rand(dims[0], device=dev, generator=g) + 0.5, 5.0) if with_stats else None
+    monkeypatch.setattr(pk, "USE_WALK", use_walk)
+    got = pk.forward_nets([(x, layers)], store_hidden=False, norms=[stats])
+    assert len(got) == 1 and tuple(got[0][-1].shape) == (33, dims[-1])
+    direct = pk.mlp_walk_forward([(x, layers)], store_hidden=False, norms=[stats])
+    assert (direct is None) == (max(dims) > 416)
+    if use_walk and direct is not None:
+        assert all(y is None for y in got[0][:-1]) and torch.equal(got[0][-1], direct[0][-1])
+    else:
+        assert torch.equal(got[0][-1], pk.mlp_forward(pk.normalize_rows(x, *stats) if with_stats else x, layers)[-1])
+    walk_only = pk.LayerList([(w, b, 3 if act else 0, o) for w, b, act, o in layers])
+    if max(dims) > 416:
+        with pytest.raises(RuntimeError, match="runs on the network walk only"):
+            pk.forward_nets([(x, walk_only)], store_hidden=False, norms=[stats])

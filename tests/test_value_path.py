@@ -88,7 +88,8 @@ def test_off_is_off(oracle, monkeypatch):
     monkeypatch.setattr(pk, "gae_vnorm", boom)
     monkeypatch.setattr(ppo, "clipped_value_loss", boom)
     monkeypatch.setattr(ppo, "denormalize_value", boom)
-    monkeypatch.setattr(PPOTrainer, "_update_value_norm", boom)
+    merge = PPOTrainer._update_input_norm                  # the returns join the end-of-epoch merge through its `returns` argument
+    monkeypatch.setattr(PPOTrainer, "_update_input_norm", lambda self, src, returns=None: boom() if returns is not None else merge(self, src))
     tr = trainer(oracle)
     assert tr.value_norm is None and tr.net.value_norm is None and not tr.clip_v
     seen = []

@@ -212,7 +212,8 @@ def test_off_is_off_on_the_gpu(hip, monkeypatch):
     loss = pk.ppo_loss_and_grads
     monkeypatch.setattr(pk, "gae_vnorm", boom)
     monkeypatch.setattr(pk, "ppo_loss_and_grads", lambda *a, **k: boom() if "old_v" in k else loss(*a, **k))
-    monkeypatch.setattr(PPOTrainer, "_update_value_norm", boom)
+    merge = PPOTrainer._update_input_norm                  # the returns join the end-of-epoch merge through its `returns` argument
+    monkeypatch.setattr(PPOTrainer, "_update_input_norm", lambda self, src, returns=None: boom() if returns is not None else merge(self, src))
     tr = hip_trainer(256)
     stats = tr.train(2)
     assert tr.frames == 2 * 4 * 256 and all(math.isfinite(st["loss"]) for st in stats)
