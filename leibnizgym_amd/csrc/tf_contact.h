@@ -219,6 +219,39 @@ DEV void seg_seg_s(const float p1[3], const float q1[3], const float p2[3], cons
     s_out = s;
 }
 
+// ---- Pieces of the finger-finger pre-pass, stated once for every placement of its rows (tf_roles.h: finger_role, helper_role, cube_role and
+// tf_ff_distal.inc).  Straight-line arithmetic only: the compiler simplifies a function on its own before it inlines it, and every piece here leaves
+// the machine code of every built unit as it was when the same lines stood in the roles.  The middle frame, the two sides' Jacobians, the mailbox
+// ladders and the distal pass as a whole do not (they change the order of instructions or the shape of branches: profiles/r21_ff_row_pieces.txt), so
+// they stay written out in the roles. ----
+// Geometry of the middle-distal row: the middle link of finger fm (axis aw -> bw, frame ex, ey, base frame ym) against the distal capsule axis Ad -> Bd
+// of another finger.  n points from the middle link to the distal capsule, nm is n in fm's base frame, ext the extent of the tapered rounded box
+// (shape2) along n at the closest point's parameter, gap the distance of the two surfaces.  Meaningful where dist2 > 1e-12 (the callers test it).
+struct FFRow { float Pm[3], Pd[3], n[3], nm[3], ext, gap, dist2; };
+DEV void ff_row_geometry(const DevModel& m, const Yaw& ym, const float aw[3], const float bw[3], const float Ad[3], const float Bd[3],
+                         const float ex[3], const float ey[3], FFRow& r) {
+    const TfLinkShape& sh = m.shape2;
+    float sp;
+    seg_seg_s(aw, bw, Ad, Bd, r.Pm, r.Pd, sp);
+    const float dv[3] = {r.Pd[0] - r.Pm[0], r.Pd[1] - r.Pm[1], r.Pd[2] - r.Pm[2]};
+    r.dist2 = dot3(dv, dv);
+    const float inv = f_rsqrt(f_max(r.dist2, 1e-12f));
+    const float dist = r.dist2 * inv;
+    r.n[0] = dv[0] * inv; r.n[1] = dv[1] * inv; r.n[2] = dv[2] * inv;
+    dir_world_to_base(ym, r.n, r.nm);
+    const float u1 = dot3(r.nm, ex), u2 = dot3(r.nm, ey);
+    const float rho = FMA(sp, sh.rho[1] - sh.rho[0], sh.rho[0]);
+    const float h1 = FMA(sp, sh.w1[1] - sh.w1[0], sh.w1[0]) - rho, h2 = FMA(sp, sh.w2[1] - sh.w2[0], sh.w2[0]) - rho;
+    const float o1 = FMA(sp, sh.o1[1] - sh.o1[0], sh.o1[0]), o2 = FMA(sp, sh.o2[1] - sh.o2[0], sh.o2[0]);
+    r.ext = FMA(o2, u2, FMA(o1, u1, FMA(h2, f_abs(u2), FMA(h1, f_abs(u1), rho))));
+    r.gap = dist - r.ext - m.cap_radius;
+}
+// The impulse of a single frictionless row between two fingers, solved exactly by one projection: J, W = M^-1 J of either side
+DEV float ff_lambda(const DevModel& m, float gap, float vn0, float inv_h, float rest_ff, const float Ja[3], const float Wa[3], const float Jb[3], const float Wb[3]) {
+    const float bias = contact_bias(m, gap, vn0, inv_h, rest_ff);
+    return f_max(-(vn0 + bias) * f_rcp2(dot3(Ja, Wa) + dot3(Jb, Wb)), 0.0f);
+}
+
 // inner radius of the boundary at height z: the piecewise-linear profile through the knots (wall_z[i], wall_r[i]) - a vertical ring below
 // the first knot, the flaring cone of the stage above it (slopes wall_s precomputed at tf_create), nothing above the last knot (1e3)
 DEV float wall_radius_at(const DevParams& P, float z) {

@@ -1,7 +1,7 @@
 // tf_ff_distal.inc - the distal finger-finger pass: the pairs (0,1), (1,2), (2,0) in turn, one frictionless normal row each, resolved before the sweeps
 // on the free velocities, which live in LDS (L_VQFF) while the pairs are visited.  Reads what the fingers published before S1 (LDS only) - run by the
-// cube role between S1 and S1b, or, in the instantiation with helper wavefronts, by wavefront 7 (tf_roles.h includes it at both places).  Textual
-// inclusion; uses m, h, inv_h, rest_ff, lds, lane.
+// cube role between S1 and S1b (tf_roles.h includes it there and nowhere else); in the instantiation with helper wavefronts, wavefront 7 runs the same
+// rows in a layout of its own (helper_role).  Textual inclusion; uses m, h, inv_h, rest_ff, lds, lane.
 #pragma unroll
             for (int f = 0; f < 3; ++f) {
 #pragma unroll
@@ -47,8 +47,7 @@
                     }
                     float vn0 = dot3(Ja, va) - dot3(Jb, vb);
                     if (contact_live(m, gap, vn0, h)) {
-                        float bias = contact_bias(m, gap, vn0, inv_h, rest_ff);
-                        float lam = f_max(-(vn0 + bias) * f_rcp2(dot3(Ja, Wa) + dot3(Jb, Wb)), 0.0f);
+                        float lam = ff_lambda(m, gap, vn0, inv_h, rest_ff, Ja, Wa, Jb, Wb);
 #pragma unroll
                         for (int j = 0; j < 3; ++j) {
                             LD(L_VQFF + 3 * fa + j) = FMA(Wa[j], lam, va[j]);

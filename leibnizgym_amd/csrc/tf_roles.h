@@ -810,7 +810,8 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
             // each other finger.  Since API 8 these six rows are solved on the FREE velocities (oracle/tf_oracle.c: a Jacobi step), so a row needs only
             // what the fingers published before S1: this wavefront builds the two rows of its own middle link - out of its own frames, where the cube
             // role had to rebuild the middle frame from what is published - while the cube role runs the distal pairs, keeps its own velocity change
-            // and posts the other finger's (ffm_mbox).  The same lines as the cube role's placement, the same bits. ----
+            // and posts the other finger's (ffm_mbox).  The row's geometry and its impulse are stated once for every placement (tf_contact.h: ff_row_geometry,
+            // ff_lambda); the middle frame and the two sides' Jacobians are the lines of the cube role's placement, the same bits. ----
             float ffm_own[2][3] = {{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}};
             // Placement is a choice per instantiation (same bits either way): the 256-register cube kernels build the rows HERE (8192 envs: 46.9 -> 43.1 us;
             // one wavefront per SIMD, the cube wavefront is the long pole before the sweeps); the 128-register kernels keep them on the cube wavefront
@@ -845,28 +846,15 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
                 for (int o = FFM_O_FIRST; o >= 1; --o) {
                     const int fd = (f + o >= 3) ? f + o - 3 : f + o;
                     float dd[3] = {0.0f, 0.0f, 0.0f};
-                    float Pm[3], Pd[3], sp;
+                    FFRow r;
                     {
                         float Ad[3], Bd[3];
 #pragma unroll
                         for (int j = 0; j < 3; ++j) { Ad[j] = LD(L_REC(fd) + P_AW + j); Bd[j] = LD(L_REC(fd) + P_BW + j); }
-                        seg_seg_s(aw, bw, Ad, Bd, Pm, Pd, sp);
+                        ff_row_geometry(m, yw, aw, bw, Ad, Bd, ex, ey, r);
                     }
-                    const float dv[3] = {Pd[0] - Pm[0], Pd[1] - Pm[1], Pd[2] - Pm[2]};
-                    const float dist2 = dot3(dv, dv);
-                    const float inv = f_rsqrt(f_max(dist2, 1e-12f));
-                    const float dist = dist2 * inv;
-                    const float n[3] = {dv[0] * inv, dv[1] * inv, dv[2] * inv};      // from the middle link to the distal capsule
-                    float nm[3];
-                    dir_world_to_base(yw, n, nm);
-                    const float u1 = dot3(nm, ex), u2 = dot3(nm, ey);
-                    const float rho = FMA(sp, sh.rho[1] - sh.rho[0], sh.rho[0]);
-                    const float h1 = FMA(sp, sh.w1[1] - sh.w1[0], sh.w1[0]) - rho, h2 = FMA(sp, sh.w2[1] - sh.w2[0], sh.w2[0]) - rho;
-                    const float o1 = FMA(sp, sh.o1[1] - sh.o1[0], sh.o1[0]), o2 = FMA(sp, sh.o2[1] - sh.o2[0], sh.o2[0]);
-                    const float ext = FMA(o2, u2, FMA(o1, u1, FMA(h2, f_abs(u2), FMA(h1, f_abs(u1), rho))));
-                    const float gap_ff = dist - ext - m.cap_radius;
                     // (the gate in the place of gap < contact_margin, which contact_live repeats; s_mid is this finger's own, re-read: no register across S1)
-                    const bool near_ff = WIDE ? ((dist2 > 1e-12f) && (gap_ff < m.contact_margin)) : (ff_gate(m, gap_ff, LD(L_REC(fd) + P_GD), LD(L_REC(f) + P_GM), h) && (dist2 > 1e-12f));
+                    const bool near_ff = WIDE ? ((r.dist2 > 1e-12f) && (r.gap < m.contact_margin)) : (ff_gate(m, r.gap, LD(L_REC(fd) + P_GD), LD(L_REC(f) + P_GM), h) && (r.dist2 > 1e-12f));
                     if (__builtin_amdgcn_ballot_w64(near_ff) != 0ull) {
                         float Jd[3], Wd[3], Jm[3], Wm[3], vd[3];
                         // the record address of fd, formed again: left to itself the compiler keeps the one of the loads above in scratch and reloads it twice
@@ -878,28 +866,27 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
                             read_pub<WIDE>(m, lds, lane, fdn, pd);
                             float C[3], Cb_[3], L1[3], L2[3], L3[3], nb[3];
 #pragma unroll
-                            for (int j = 0; j < 3; ++j) C[j] = FMA(-m.cap_radius, n[j], Pd[j]);
+                            for (int j = 0; j < 3; ++j) C[j] = FMA(-m.cap_radius, r.n[j], r.Pd[j]);
                             world_to_base(yd, C, Cb_);
                             levers(pd.k, Cb_, L1, L2, L3);
-                            dir_world_to_base(yd, n, nb);
+                            dir_world_to_base(yd, r.n, nb);
                             Jd[0] = dot3(L1, nb); Jd[1] = dot3(L2, nb); Jd[2] = dot3(L3, nb);
                             sym3_mul(pd.k.Minv, Jd, Wd);
                         }
                         {   // middle side: joints 1 and 2 move it, joint 3 does not
                             float C[3], Cb_[3], L1[3], L2[3], L3[3];
 #pragma unroll
-                            for (int j = 0; j < 3; ++j) C[j] = FMA(ext, n[j], Pm[j]);
+                            for (int j = 0; j < 3; ++j) C[j] = FMA(r.ext, r.n[j], r.Pm[j]);
                             world_to_base(yw, C, Cb_);
                             levers(k, Cb_, L1, L2, L3);
-                            Jm[0] = dot3(L1, nm); Jm[1] = dot3(L2, nm); Jm[2] = 0.0f;
+                            Jm[0] = dot3(L1, r.nm); Jm[1] = dot3(L2, r.nm); Jm[2] = 0.0f;
                             sym3_mul(k.Minv, Jm, Wm);
                         }
 #pragma unroll
                         for (int j = 0; j < 3; ++j) vd[j] = LD(L_REC(fdn) + P_VQ + j);          // free velocities on both sides
                         const float vn0 = dot3(Jd, vd) - dot3(Jm, vq);
-                        if (near_ff && contact_live(m, gap_ff, vn0, h)) {
-                            const float bias = contact_bias(m, gap_ff, vn0, inv_h, rest_ff);
-                            const float lam = f_max(-(vn0 + bias) * f_rcp2(dot3(Jd, Wd) + dot3(Jm, Wm)), 0.0f);
+                        if (near_ff && contact_live(m, r.gap, vn0, h)) {
+                            const float lam = ff_lambda(m, r.gap, vn0, inv_h, rest_ff, Jd, Wd, Jm, Wm);
 #pragma unroll
                             for (int j = 0; j < 3; ++j) { dd[j] = Wd[j] * lam; ffm_own[o - 1][j] = Wm[j] * lam; }
                         }
@@ -1419,7 +1406,8 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
 // Up to 16384 envs a 256-register workgroup has a CU to itself and one wavefront on each SIMD: the second wavefront slot of a SIMD is empty, and the six
 // middle-distal finger-finger rows - independent of everything else between S1 and S1b, functions of what the fingers published before S1 - sat on the
 // finger wavefronts' critical path (contact generation).  Here wavefront 4 + fm builds the two rows of finger fm's middle link with the cube role's
-// formulation of them (the middle frame rebuilt from what finger fm publishes: the lines of cube_role's block, the same bits) and posts the velocity
+// formulation of them (the middle frame rebuilt from what finger fm publishes: the lines of cube_role's block, the same bits; the row's geometry
+// and its impulse are tf_contact.h's ff_row_geometry and ff_lambda there as here) and posts the velocity
 // changes; the finger roles add them behind S1b in the listed order exactly as they add the ones they computed themselves.  Apart from that the role
 // only keeps the workgroup's barriers company - every BAR() of the other roles has its twin here, in the same order under the same conditions.
 template <bool ASYM, int MODE, int X, bool DR = true>
@@ -1495,8 +1483,7 @@ DEV void helper_role(const DevParams& P, const StepArgs& sa, float* lds, const C
                     if (nearp[p]) {
                         const float vn0 = dot3(Ja[p], vel[fa]) - dot3(Jb[p], vel[fb]);
                         if (contact_live(m, gapp[p], vn0, h)) {
-                            const float bias = contact_bias(m, gapp[p], vn0, inv_h, rest_ff);
-                            const float lam = f_max(-(vn0 + bias) * f_rcp2(dot3(Ja[p], Wa[p]) + dot3(Jb[p], Wb[p])), 0.0f);
+                            const float lam = ff_lambda(m, gapp[p], vn0, inv_h, rest_ff, Ja[p], Wa[p], Jb[p], Wb[p]);
 #pragma unroll
                             for (int j = 0; j < 3; ++j) {
                                 vel[fa][j] = FMA(Wa[p][j], lam, vel[fa][j]);
@@ -1537,27 +1524,14 @@ DEV void helper_role(const DevParams& P, const StepArgs& sa, float* lds, const C
                 for (int o = 2; o >= 1; --o) {
                     const int fd = (fm + o >= 3) ? fm + o - 3 : fm + o;
                     float dd[3] = {0.0f, 0.0f, 0.0f}, dm[3] = {0.0f, 0.0f, 0.0f};
-                    float Pm[3], Pd[3], sp;
+                    FFRow r;
                     {
                         float Ad[3], Bd[3];
 #pragma unroll
                         for (int j = 0; j < 3; ++j) { Ad[j] = LD(L_REC(fd) + P_AW + j); Bd[j] = LD(L_REC(fd) + P_BW + j); }
-                        seg_seg_s(aw, bw, Ad, Bd, Pm, Pd, sp);
+                        ff_row_geometry(m, ym, aw, bw, Ad, Bd, ex, ey, r);
                     }
-                    const float dv[3] = {Pd[0] - Pm[0], Pd[1] - Pm[1], Pd[2] - Pm[2]};
-                    const float dist2 = dot3(dv, dv);
-                    const float inv = f_rsqrt(f_max(dist2, 1e-12f));
-                    const float dist = dist2 * inv;
-                    const float n[3] = {dv[0] * inv, dv[1] * inv, dv[2] * inv};      // from the middle link to the distal capsule
-                    float nm[3];
-                    dir_world_to_base(ym, n, nm);
-                    const float u1 = dot3(nm, ex), u2 = dot3(nm, ey);
-                    const float rho = FMA(sp, sh.rho[1] - sh.rho[0], sh.rho[0]);
-                    const float h1 = FMA(sp, sh.w1[1] - sh.w1[0], sh.w1[0]) - rho, h2 = FMA(sp, sh.w2[1] - sh.w2[0], sh.w2[0]) - rho;
-                    const float o1 = FMA(sp, sh.o1[1] - sh.o1[0], sh.o1[0]), o2 = FMA(sp, sh.o2[1] - sh.o2[0], sh.o2[0]);
-                    const float ext = FMA(o2, u2, FMA(o1, u1, FMA(h2, f_abs(u2), FMA(h1, f_abs(u1), rho))));
-                    const float gap = dist - ext - m.cap_radius;
-                    const bool near_ff = (dist2 > 1e-12f) && (gap < m.contact_margin);
+                    const bool near_ff = (r.dist2 > 1e-12f) && (r.gap < m.contact_margin);
                     if (__builtin_amdgcn_ballot_w64(near_ff) != 0ull) {
                         float Jd[3], Wd[3], Jm[3], Wm[3], vd[3];
                         {   // distal side: the point of the capsule surface that faces the middle link
@@ -1566,28 +1540,27 @@ DEV void helper_role(const DevParams& P, const StepArgs& sa, float* lds, const C
                             read_pub<true>(m, lds, lane, fd, pd);
                             float C[3], Cb_[3], L1[3], L2[3], L3[3], nb[3];
 #pragma unroll
-                            for (int j = 0; j < 3; ++j) C[j] = FMA(-m.cap_radius, n[j], Pd[j]);
+                            for (int j = 0; j < 3; ++j) C[j] = FMA(-m.cap_radius, r.n[j], r.Pd[j]);
                             world_to_base(yd, C, Cb_);
                             levers(pd.k, Cb_, L1, L2, L3);
-                            dir_world_to_base(yd, n, nb);
+                            dir_world_to_base(yd, r.n, nb);
                             Jd[0] = dot3(L1, nb); Jd[1] = dot3(L2, nb); Jd[2] = dot3(L3, nb);
                             sym3_mul(pd.k.Minv, Jd, Wd);
                         }
                         {   // middle side: joints 1 and 2 move it, joint 3 does not
                             float C[3], Cb_[3], L1[3], L2[3], L3[3];
 #pragma unroll
-                            for (int j = 0; j < 3; ++j) C[j] = FMA(ext, n[j], Pm[j]);
+                            for (int j = 0; j < 3; ++j) C[j] = FMA(r.ext, r.n[j], r.Pm[j]);
                             world_to_base(ym, C, Cb_);
                             levers(pm.k, Cb_, L1, L2, L3);
-                            Jm[0] = dot3(L1, nm); Jm[1] = dot3(L2, nm); Jm[2] = 0.0f;
+                            Jm[0] = dot3(L1, r.nm); Jm[1] = dot3(L2, r.nm); Jm[2] = 0.0f;
                             sym3_mul(pm.k.Minv, Jm, Wm);
                         }
 #pragma unroll
                         for (int j = 0; j < 3; ++j) vd[j] = LD(L_REC(fd) + P_VQ + j);
                         const float vn0 = dot3(Jd, vd) - dot3(Jm, vm);
-                        if (near_ff && contact_live(m, gap, vn0, h)) {
-                            const float bias = contact_bias(m, gap, vn0, inv_h, rest_ff);
-                            const float lam = f_max(-(vn0 + bias) * f_rcp2(dot3(Jd, Wd) + dot3(Jm, Wm)), 0.0f);
+                        if (near_ff && contact_live(m, r.gap, vn0, h)) {
+                            const float lam = ff_lambda(m, r.gap, vn0, inv_h, rest_ff, Jd, Wd, Jm, Wm);
 #pragma unroll
                             for (int j = 0; j < 3; ++j) { dd[j] = Wd[j] * lam; dm[j] = Wm[j] * lam; }
                         }
@@ -2026,28 +1999,15 @@ DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restri
                     {
                         const int o = o_;
                         const int fd = (fm + o >= 3) ? fm + o - 3 : fm + o;
-                        float Pm[3], Pd[3], sp;
+                        FFRow r;
                         {
                             float Ad[3], Bd[3];
 #pragma unroll
                             for (int j = 0; j < 3; ++j) { Ad[j] = LD(L_REC(fd) + P_AW + j); Bd[j] = LD(L_REC(fd) + P_BW + j); }
-                            seg_seg_s(aw, bw, Ad, Bd, Pm, Pd, sp);
+                            ff_row_geometry(m, ym, aw, bw, Ad, Bd, ex, ey, r);
                         }
-                        const float dv[3] = {Pd[0] - Pm[0], Pd[1] - Pm[1], Pd[2] - Pm[2]};
-                        const float dist2 = dot3(dv, dv);
-                        const float inv = f_rsqrt(f_max(dist2, 1e-12f));
-                        const float dist = dist2 * inv;
-                        const float n[3] = {dv[0] * inv, dv[1] * inv, dv[2] * inv};      // from the middle link to the distal capsule
-                        float nm[3];
-                        dir_world_to_base(ym, n, nm);
-                        const float u1 = dot3(nm, ex), u2 = dot3(nm, ey);
-                        const float rho = FMA(sp, sh.rho[1] - sh.rho[0], sh.rho[0]);
-                        const float h1 = FMA(sp, sh.w1[1] - sh.w1[0], sh.w1[0]) - rho, h2 = FMA(sp, sh.w2[1] - sh.w2[0], sh.w2[0]) - rho;
-                        const float o1 = FMA(sp, sh.o1[1] - sh.o1[0], sh.o1[0]), o2 = FMA(sp, sh.o2[1] - sh.o2[0], sh.o2[0]);
-                        const float ext = FMA(o2, u2, FMA(o1, u1, FMA(h2, f_abs(u2), FMA(h1, f_abs(u1), rho))));
-                        const float gap = dist - ext - m.cap_radius;
                         // the link-speed gate (tf_contact.h: ff_gate) in the place of gap < contact_margin, which contact_live repeats
-                        if ((dist2 > 1e-12f) && ff_gate(m, gap, LD(L_REC(fd) + P_GD), LD(L_REC(fm) + P_GM), h)) {
+                        if ((r.dist2 > 1e-12f) && ff_gate(m, r.gap, LD(L_REC(fd) + P_GD), LD(L_REC(fm) + P_GM), h)) {
                             float Jd[3], Wd[3], Jm[3], Wm[3], vd[3], vm[3];
                             {   // distal side: the point of the capsule surface that faces the middle link
                                 const Yaw yd = {m.base_yaw_cos[fd], m.base_yaw_sin[fd], 0.0f, 0.0f, m.base_height};
@@ -2055,28 +2015,27 @@ DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restri
                                 read_pub<WIDE>(m, lds, lane, fd, pd);
                                 float C[3], Cb_[3], L1[3], L2[3], L3[3], nb[3];
 #pragma unroll
-                                for (int j = 0; j < 3; ++j) C[j] = FMA(-m.cap_radius, n[j], Pd[j]);
+                                for (int j = 0; j < 3; ++j) C[j] = FMA(-m.cap_radius, r.n[j], r.Pd[j]);
                                 world_to_base(yd, C, Cb_);
                                 levers(pd.k, Cb_, L1, L2, L3);
-                                dir_world_to_base(yd, n, nb);
+                                dir_world_to_base(yd, r.n, nb);
                                 Jd[0] = dot3(L1, nb); Jd[1] = dot3(L2, nb); Jd[2] = dot3(L3, nb);
                                 sym3_mul(pd.k.Minv, Jd, Wd);
                             }
                             {   // middle side: joints 1 and 2 move it, joint 3 does not
                                 float C[3], Cb_[3], L1[3], L2[3], L3[3];
 #pragma unroll
-                                for (int j = 0; j < 3; ++j) C[j] = FMA(ext, n[j], Pm[j]);
+                                for (int j = 0; j < 3; ++j) C[j] = FMA(r.ext, r.n[j], r.Pm[j]);
                                 world_to_base(ym, C, Cb_);
                                 levers(pm.k, Cb_, L1, L2, L3);
-                                Jm[0] = dot3(L1, nm); Jm[1] = dot3(L2, nm); Jm[2] = 0.0f;
+                                Jm[0] = dot3(L1, r.nm); Jm[1] = dot3(L2, r.nm); Jm[2] = 0.0f;
                                 sym3_mul(pm.k.Minv, Jm, Wm);
                             }
 #pragma unroll
                             for (int j = 0; j < 3; ++j) { vd[j] = LD(L_REC(fd) + P_VQ + j); vm[j] = LD(L_REC(fm) + P_VQ + j); }      // the FREE velocities (API 8)
                             const float vn0 = dot3(Jd, vd) - dot3(Jm, vm);
-                            if (contact_live(m, gap, vn0, h)) {
-                                const float bias = contact_bias(m, gap, vn0, inv_h, rest_ff);
-                                const float lam = f_max(-(vn0 + bias) * f_rcp2(dot3(Jd, Wd) + dot3(Jm, Wm)), 0.0f);
+                            if (contact_live(m, r.gap, vn0, h)) {
+                                const float lam = ff_lambda(m, r.gap, vn0, inv_h, rest_ff, Jd, Wd, Jm, Wm);
 #pragma unroll
                                 for (int j = 0; j < 3; ++j) {
                                     const float dd = Wd[j] * lam, dm = Wm[j] * lam;

@@ -1041,6 +1041,36 @@ static void seg_seg_s(const float p1[3], const float q1[3], const float p2[3], c
     *s_out = s;
 }
 
+/* ---- pieces of a finger-finger row (csrc/tf_contact.h: same names, same operations) ----
+ * Geometry of the middle-distal row: the middle link of finger fm (axis aw -> bw, frame ex, ey) against the distal capsule axis Ad -> Bd of another
+ * finger.  n points from the middle link to the distal capsule, nm is n in fm's base frame, ext the extent of the tapered rounded box (shape2)
+ * along n at the closest point's parameter, gap the distance of the two surfaces.  Meaningful where dist2 > 1e-12 (the caller tests it; there
+ * f_max(dist2, 1e-12f) is dist2 itself). */
+typedef struct { float Pm[3], Pd[3], n[3], nm[3], ext, gap, dist2; } FFRow;
+static void ff_row_geometry(const TfModel* m, int fm, const float aw[3], const float bw[3], const float Ad[3], const float Bd[3],
+                            const float ex[3], const float ey[3], FFRow* r) {
+    const TfLinkShape* sh = &m->shape2;
+    float sp;
+    seg_seg_s(aw, bw, Ad, Bd, r->Pm, r->Pd, &sp);
+    const float dv[3] = {r->Pd[0] - r->Pm[0], r->Pd[1] - r->Pm[1], r->Pd[2] - r->Pm[2]};
+    r->dist2 = dot3(dv, dv);
+    const float inv = f_rsqrt(f_max(r->dist2, 1e-12f));
+    const float dist = r->dist2 * inv;
+    r->n[0] = dv[0] * inv; r->n[1] = dv[1] * inv; r->n[2] = dv[2] * inv;
+    dir_world_to_base(m, fm, r->n, r->nm);
+    const float u1 = dot3(r->nm, ex), u2 = dot3(r->nm, ey);
+    const float rho = FMA(sp, sh->rho[1] - sh->rho[0], sh->rho[0]);
+    const float h1 = FMA(sp, sh->w1[1] - sh->w1[0], sh->w1[0]) - rho, h2 = FMA(sp, sh->w2[1] - sh->w2[0], sh->w2[0]) - rho;
+    const float o1 = FMA(sp, sh->o1[1] - sh->o1[0], sh->o1[0]), o2 = FMA(sp, sh->o2[1] - sh->o2[0], sh->o2[0]);
+    r->ext = FMA(o2, u2, FMA(o1, u1, FMA(h2, f_abs(u2), FMA(h1, f_abs(u1), rho))));
+    r->gap = dist - r->ext - m->cap_radius;
+}
+/* the impulse of a single frictionless row between two fingers, solved exactly by one projection: J, W = M^-1 J of either side */
+static float ff_lambda(const TfModel* m, float gap, float vn0, float inv_h, float rest_ff, const float Ja[3], const float Wa[3], const float Jb[3], const float Wb[3]) {
+    const float bias = contact_bias(m, gap, vn0, inv_h, rest_ff);
+    return f_max(-(vn0 + bias) * f_rcp2(dot3(Ja, Wa) + dot3(Jb, Wb)), 0.0f);
+}
+
 /* inner radius of the boundary at height z: piecewise-linear profile through the knots (wall_z[i], wall_r[i]); a vertical ring below
  * the first knot, nothing above the last (1e3) */
 static float wall_radius_at(const struct TfHandle_* H, float z) {
@@ -1542,8 +1572,7 @@ static void substep(const struct TfHandle_* H, Env* e, float h) {
         float* vb = vq_ff[fb];
         float vn0 = dot3(Ja, va) - dot3(Jb, vb);
         if (!contact_live(m, gap, vn0, h)) continue;
-        float bias = contact_bias(m, gap, vn0, inv_h, rest_ff);
-        float lam = f_max(-(vn0 + bias) * f_rcp2(dot3(Ja, Wa) + dot3(Jb, Wb)), 0.0f);
+        float lam = ff_lambda(m, gap, vn0, inv_h, rest_ff, Ja, Wa, Jb, Wb);
 #ifdef TF_FF_CENSUS
         if (lam > 0.0f) { ++fc_nd; fc_d[fa] = 1; fc_d[fb] = 1; }
 #endif
@@ -1583,47 +1612,33 @@ static void substep(const struct TfHandle_* H, Env* e, float h) {
             {
                 const int o = o_;
                 const int fd = (fm + o) % 3;
-                float Pm[3], Pd[3], sp;
-                seg_seg_s(aw, bw, fr[fd].Aw, fr[fd].Bw, Pm, Pd, &sp);
-                float dv[3] = {Pd[0] - Pm[0], Pd[1] - Pm[1], Pd[2] - Pm[2]};
-                float dist2 = dot3(dv, dv);
-                if (!(dist2 > 1e-12f)) continue;
-                float inv = f_rsqrt(dist2);
-                float dist = dist2 * inv;
-                float n[3] = {dv[0] * inv, dv[1] * inv, dv[2] * inv};      /* from the middle link to the distal capsule */
-                float nm[3];
-                dir_world_to_base(m, fm, n, nm);
-                const float u1 = dot3(nm, ex), u2 = dot3(nm, ey);
-                const float rho = FMA(sp, sh->rho[1] - sh->rho[0], sh->rho[0]);
-                const float h1 = FMA(sp, sh->w1[1] - sh->w1[0], sh->w1[0]) - rho, h2 = FMA(sp, sh->w2[1] - sh->w2[0], sh->w2[0]) - rho;
-                const float o1 = FMA(sp, sh->o1[1] - sh->o1[0], sh->o1[0]), o2 = FMA(sp, sh->o2[1] - sh->o2[0], sh->o2[0]);
-                const float ext = FMA(o2, u2, FMA(o1, u1, FMA(h2, f_abs(u2), FMA(h1, f_abs(u1), rho))));
-                float gap = dist - ext - m->cap_radius;
-                if (!(gap < m->contact_margin)) continue;
+                FFRow r;
+                ff_row_geometry(m, fm, aw, bw, fr[fd].Aw, fr[fd].Bw, ex, ey, &r);
+                if (!(r.dist2 > 1e-12f)) continue;
+                if (!(r.gap < m->contact_margin)) continue;
                 float Jd[3], Wd[3], Jm[3], Wm[3];
                 {   /* distal side: the point of the capsule surface that faces the middle link */
                     float C[3], Cb[3], L1[3], L2[3], L3[3], nb[3];
-                    for (int i = 0; i < 3; ++i) C[i] = FMA(-m->cap_radius, n[i], Pd[i]);
+                    for (int i = 0; i < 3; ++i) C[i] = FMA(-m->cap_radius, r.n[i], r.Pd[i]);
                     world_to_base(m, fd, C, Cb);
                     levers(&fr[fd].k, Cb, L1, L2, L3);
-                    dir_world_to_base(m, fd, n, nb);
+                    dir_world_to_base(m, fd, r.n, nb);
                     Jd[0] = dot3(L1, nb); Jd[1] = dot3(L2, nb); Jd[2] = dot3(L3, nb);
                     sym3_mul(fr[fd].k.Minv, Jd, Wd);
                 }
                 {   /* middle side: joints 1 and 2 move it, joint 3 does not */
                     float C[3], Cb[3], L1[3], L2[3], L3[3];
-                    for (int i = 0; i < 3; ++i) C[i] = FMA(ext, n[i], Pm[i]);
+                    for (int i = 0; i < 3; ++i) C[i] = FMA(r.ext, r.n[i], r.Pm[i]);
                     world_to_base(m, fm, C, Cb);
                     levers(km, Cb, L1, L2, L3);
-                    Jm[0] = dot3(L1, nm); Jm[1] = dot3(L2, nm); Jm[2] = 0.0f;
+                    Jm[0] = dot3(L1, r.nm); Jm[1] = dot3(L2, r.nm); Jm[2] = 0.0f;
                     sym3_mul(km->Minv, Jm, Wm);
                 }
                 const float* vd = fr[fd].vq;                        /* free velocities: not vq_ff */
                 const float* vm = fr[fm].vq;
                 float vn0 = dot3(Jd, vd) - dot3(Jm, vm);
-                if (!contact_live(m, gap, vn0, h)) continue;
-                float bias = contact_bias(m, gap, vn0, inv_h, rest_ff);
-                float lam = f_max(-(vn0 + bias) * f_rcp2(dot3(Jd, Wd) + dot3(Jm, Wm)), 0.0f);
+                if (!contact_live(m, r.gap, vn0, h)) continue;
+                float lam = ff_lambda(m, r.gap, vn0, inv_h, rest_ff, Jd, Wd, Jm, Wm);
 #ifdef TF_FF_CENSUS
                 if (lam > 0.0f) { ++fc_nm; ++fc_mb[fd]; ++fc_own[fm]; fc_grp[fd] |= (o == 2) ? 1 : 2; fc_grp[fm] |= (o == 2) ? 1 : 2; }
 #endif
