@@ -22,12 +22,16 @@
 // tfp_ppo_loss_w / tfp_ppo_loss_vclip_w (include/trifinger_ppo_episode.h; `episode_ends`) are the same kernel again with a weight per sample: `adv` is then
 // [B, 2], (adv_i, w_i) interleaved, and the sample's surrogate, value, bounds and KL terms and its d_mu, d_v and share of d_logstd are multiplied by w_i -
 // as the LAST operation on each, so that w = 1 leaves every bit of the unweighted expression; the divisor stays B and the entropy term is untouched.
+// tfp_ppo_loss_sym (include/trifinger_ppo_symmetry.h; `symmetry_augmentation`) is the same kernel once more with a row count of its own for the KL statistic
+// (KLR): the rows i >= kl_rows add nothing to it and its divisor is kl_rows - the augmented rows of a minibatch train, the statistic that drives the adaptive
+// learning rate reads the original rows alone.  With kl_rows == B every bit is that of the entry point (old_v, weighted) selects.
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include <stdint.h>
 #include <string.h>
 #include "../../include/trifinger_ppo_value.h"       // declares the value-side entry points (and trifinger_ppo.h): a definition that drifts fails here
 #include "../../include/trifinger_ppo_episode.h"     // ... and the episode-end entry points
+#include "../../include/trifinger_ppo_symmetry.h"    // ... and the objective with a KL row count
 
 #define MAX_A 18
 
@@ -42,14 +46,14 @@ __device__ __forceinline__ float wave_sum(float x) {
 // One objective at a time per device (the trainer's single stream); results as before up to the order of the atomic sums.
 __device__ float g_loss_acc[24];
 __device__ unsigned g_loss_ticket;
-template <int A, bool VCLIP, bool WGT>
+template <int A, bool VCLIP, bool WGT, bool KLR = false>
 __global__ void __launch_bounds__(256) k_ppo_loss(const float* __restrict__ mu, const float* __restrict__ log_std, const float* __restrict__ act,
                                                   const float* __restrict__ old_nlp, const float* __restrict__ adv,
                                                   const float* __restrict__ old_mu, const float* __restrict__ v,
                                                   const float* __restrict__ ret, int B, float e_clip, float v_coef, float ent_coef,
                                                   float bounds_coef, float* __restrict__ d_mu, float* __restrict__ d_v,
                                                   float* __restrict__ d_logstd, float* __restrict__ loss_out, float* __restrict__ stats,
-                                                  const float* __restrict__ old_v) {
+                                                  const float* __restrict__ old_v, int kl_rows) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const bool valid = i < B;
     const float invB = 1.0f / (float)B;
@@ -107,6 +111,7 @@ __global__ void __launch_bounds__(256) k_ppo_loss(const float* __restrict__ mu, 
             else { d_mu[(size_t)i * A + a] = g_mu; dls[a] = g_ls; }
         }
         if constexpr (WGT) { a_term *= wi; c_term *= wi; b_term *= wi; kl_term *= wi; }
+        if constexpr (KLR) { if (i >= kl_rows) kl_term = 0.0f; }
     }
     // reductions: wave shuffles, then the four waves of the block through LDS, ONE atomic per block and quantity (atomics on
     // the same address serialise at ~100 ns each: 128 waves on 14 addresses cost 13 us, 32 blocks cost 3)
@@ -119,7 +124,8 @@ __global__ void __launch_bounds__(256) k_ppo_loss(const float* __restrict__ mu, 
         const float s = wave_sum(dls[a]);
         if (lane == 0) red[wave][a] = s;
     }
-    const float sa = wave_sum(a_term) * invB, sc = wave_sum(c_term) * invB, sb = wave_sum(b_term) * invB, sk = wave_sum(kl_term) * invB;
+    const float sa = wave_sum(a_term) * invB, sc = wave_sum(c_term) * invB, sb = wave_sum(b_term) * invB;
+    const float sk = wave_sum(kl_term) * (KLR ? 1.0f / (float)kl_rows : invB);
     if (lane == 0) { red[wave][A] = sa; red[wave][A + 1] = sc; red[wave][A + 2] = sb; red[wave][A + 3] = sk; }
     __syncthreads();
     if (threadIdx.x < A + 4) {
@@ -227,20 +233,23 @@ int tfp_api_version(void) { return 3; }
 }  // extern "C"
 // (No launch of this file zeroes a small buffer any more - the objective and the optimiser keep their accumulators clean themselves.  When one did, it was a
 // kernel and not hipMemsetAsync: inside a captured HIP graph the memset / memcpy NODES of this ROCm stack proved unsafe, docs/HISTORY.md section 8.)
-// the ONE launch of the objective: k_ppo_loss<9 | 18, VCLIP, WGT>, VCLIP where old_v is given, WGT where `adv` is (adv_i, w_i) interleaved.  Every entry point
-// below is its own argument check (`ok`) and this call
+// the ONE launch of the objective: k_ppo_loss<9 | 18, VCLIP, WGT, KLR>, VCLIP where old_v is given, WGT where `adv` is (adv_i, w_i) interleaved, KLR where
+// the KL statistic has a row count of its own (kl_rows > 0: tfp_ppo_loss_sym alone).  Every entry point below is its own argument check (`ok`) and this call
 static int launch_ppo_loss(bool ok, const float* mu, const float* log_std, const float* act, const float* old_nlp, const float* adv, const float* old_mu,
                            const float* v, const float* ret, const float* old_v, bool weighted, int32_t B, int32_t A, float e_clip, float v_coef,
-                           float ent_coef, float bounds_coef, float* d_mu, float* d_v, float* d_logstd, float* loss_out, float* stats, void* stream) {
-    if (!ok || B <= 0 || (A != 9 && A != 18)) return -1;
+                           float ent_coef, float bounds_coef, float* d_mu, float* d_v, float* d_logstd, float* loss_out, float* stats, void* stream,
+                           int32_t kl_rows = 0) {
+    if (!ok || B <= 0 || (A != 9 && A != 18) || kl_rows < 0 || kl_rows > B) return -1;
     hipStream_t s = (hipStream_t)stream;
     dim3 grid((B + 255) / 256), block(256);
-#define LOSS(A_, V_, W_) hipLaunchKernelGGL((k_ppo_loss<A_, V_, W_>), grid, block, 0, s, mu, log_std, act, old_nlp, adv, old_mu, v, ret, B, e_clip, v_coef, ent_coef, \
-                                            bounds_coef, d_mu, d_v, d_logstd, loss_out, stats, old_v)
-#define LOSS_A(V_, W_) do { if (A == 9) LOSS(9, V_, W_); else LOSS(18, V_, W_); } while (0)
+#define LOSS(A_, V_, W_, K_) hipLaunchKernelGGL((k_ppo_loss<A_, V_, W_, K_>), grid, block, 0, s, mu, log_std, act, old_nlp, adv, old_mu, v, ret, B, e_clip, v_coef, \
+                                                ent_coef, bounds_coef, d_mu, d_v, d_logstd, loss_out, stats, old_v, kl_rows)
+#define LOSS_K(V_, W_, K_) do { if (A == 9) LOSS(9, V_, W_, K_); else LOSS(18, V_, W_, K_); } while (0)
+#define LOSS_A(V_, W_) do { if (kl_rows > 0) LOSS_K(V_, W_, true); else LOSS_K(V_, W_, false); } while (0)
     if (!weighted) { if (!old_v) LOSS_A(false, false); else LOSS_A(true, false); }
     else { if (!old_v) LOSS_A(false, true); else LOSS_A(true, true); }
 #undef LOSS_A
+#undef LOSS_K
 #undef LOSS
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
@@ -274,6 +283,16 @@ int tfp_ppo_loss_vclip_w(const float* mu, const float* log_std, const float* act
                          float bounds_coef, float* d_mu, float* d_v, float* d_logstd, float* loss_out, float* stats, void* stream) {
     return launch_ppo_loss(old_v && adv_w && ((uintptr_t)adv_w & 7) == 0, mu, log_std, act, old_nlp, adv_w, old_mu, v, ret, old_v, true, B, A, e_clip, v_coef,
                            ent_coef, bounds_coef, d_mu, d_v, d_logstd, loss_out, stats, stream);
+}
+
+// include/trifinger_ppo_symmetry.h: any of the four entry points above - old_v NULL or given, adv [B] or (adv_i, w_i) - with the KL statistic over the
+// rows i < kl_rows alone, divided by kl_rows (the compile-time variant KLR of the same kernel: its accumulators, its ticket, its one-call-at-a-time contract)
+int tfp_ppo_loss_sym(const float* mu, const float* log_std, const float* act, const float* old_nlp, const float* adv, const float* old_mu,
+                     const float* v, const float* ret, const float* old_v, int32_t weighted, int32_t kl_rows, int32_t B, int32_t A, float e_clip, float v_coef,
+                     float ent_coef, float bounds_coef, float* d_mu, float* d_v, float* d_logstd, float* loss_out, float* stats, void* stream) {
+    const bool ok = kl_rows >= 1 && (!weighted || (adv && ((uintptr_t)adv & 7) == 0));
+    return launch_ppo_loss(ok, mu, log_std, act, old_nlp, adv, old_mu, v, ret, old_v, weighted != 0, B, A, e_clip, v_coef, ent_coef, bounds_coef, d_mu, d_v,
+                           d_logstd, loss_out, stats, stream, kl_rows);
 }
 
 // the zero state of tfp_ppo_loss's accumulators (after a launch that failed or was aborted; a completed launch leaves them clean itself)

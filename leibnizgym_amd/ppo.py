@@ -86,6 +86,21 @@ before any episode has ended: no NaN goes into a log), `episodes` (the window's 
 `episodes_unarmed`.  `train()` then judges `<name>_best.pth` by `episode_return` and stops above `score_to_win` (its docstring).  Checkpoints carry the window and
 the cumulative counts; one written without tracking restores with an empty window and best_reward = -inf (a reward per step and an episode return are different
 units; likewise the other way round).  With the key off no tracker exists and every launch, buffer and statistic is what it was.
+Symmetry augmentation (`params.config.symmetry_augmentation`, the project's own key like `episode_ends`; off by default).  The robot has an exact three-fold
+symmetry - three copies of one finger at base yaw 0, -120 and -240 degrees, floor and boundary bodies of revolution, goals and resets from rotation-invariant
+distributions, a reward built from distances - so the turn G of a sample by -120 degrees about z, with finger f renamed f + 1, is another sample of the same
+MDP (leibnizgym_amd/symmetry.py states G on obs, states and actions as tables and `apply` as their torch expression).  With the key on every minibatch of B
+rows is trained as 3B rows: rows [k B, (k + 1) B) hold G^k of obs / states and P^k of act and old_mu (the finger permutation), k = 0, 1, 2, and keep the
+original sample's old_nlp, adv, ret, old_v and w; input statistics are applied AFTER the transform.  Surrogate, value, bounds and entropy terms run over all
+3B rows with divisor 3B; the KL statistic, which drives the adaptive learning rate, runs over the FIRST B rows with divisor B - an asymmetric policy would
+otherwise read as a large KL and the rate collapse to its floor.  Advantage normalisation, the input and return records, `mean_reward`, episode tracking and
+checkpoints are untouched; the networks' shapes do not change, so checkpoints move freely between on and off.  Per epoch the statistics gain `symmetry_gap`:
+the mean over i and k = 1, 2 of |P^-k mu[k B + i] - mu[i]| on the last minibatch's forward (torch, read with the epoch's other statistics; rank-local).  The
+trainer resolves the engine once and refuses by name (ValueError): an env without an engine; an obs / states width other than 32 + A / obs + 72 (or 0) with
+A in {9, 18}; an engine with `dr_enable` and a non-zero `dr_base_pos` or `dr_stage_pos` (such a scene is not invariant).  On the GPU: include/
+trifinger_ppo_symmetry.h - the augmenting gather writes the three images in the ONE gather launch (`ppo_kernels.gather_rows_sym`), the objective takes
+the KL row count (`tfp_ppo_loss_sym`); the step keeps its launch count on three times the rows.  With the key off no table is built and every launch, buffer
+and statistic is what it was.
 
 This is host-side training glue, NOT part of the measured hot path.  On a GPU the minibatch step runs on the hand-written kernels of
 csrc/ppo_kernels.hip (leibnizgym_amd/ppo_kernels.py): one gather launch, the Linear / ELU layers on fp32 MFMA, the objective with all
@@ -153,6 +168,7 @@ class PPOConfig:
     track_episodes: bool = False      # params.config.track_episodes: episode returns, lengths and success in the statistics (module docstring); off = as before
     games_to_track: int = 100         # params.config.games_to_track (RL-Games' key): the episodes the reported window holds at least, once that many have ended
     score_to_win: float = float("inf")    # params.config.score_to_win (RL-Games' key): train() stops when episode_return exceeds it; needs track_episodes
+    symmetry_augmentation: bool = False   # params.config.symmetry_augmentation: every minibatch with its two images under the robot's 120-degree turn (module docstring)
 
     def __post_init__(self):
         if self.value_bootstrap and not self.episode_ends:
@@ -192,7 +208,7 @@ class PPOConfig:
                   lr_schedule=lr_schedule_name(c.get("lr_schedule", "adaptive")),
                   episode_ends=bool(c.get("episode_ends", False)), value_bootstrap=bool(c.get("value_bootstrap", False)),
                   track_episodes=bool(c.get("track_episodes", False)), games_to_track=int(c.get("games_to_track", 100)),
-                  score_to_win=float(c.get("score_to_win", float("inf"))))
+                  score_to_win=float(c.get("score_to_win", float("inf"))), symmetry_augmentation=bool(c.get("symmetry_augmentation", False)))
         # without a central value network the critic takes the actor's keys
         kw.update(value_activation=kw["activation"], value_d2rl=kw["d2rl"], value_truncate_grads=kw["truncate_grads"])
         if cv:
@@ -669,10 +685,43 @@ class PPOTrainer:
             from .evaluate import EpisodeTracker, engine_of
             eng = self.ends_engine if self.ends_engine is not None else engine_of(env)
             self.tracker = EpisodeTracker(eng, fused=bool(fk and eng.state.is_cuda))
+        # `symmetry_augmentation`: the tables of the map, built ONCE for this env's widths (the refusals: module docstring).  Off: none of it exists
+        self.sym = self._symmetry_tables(obs_dim, state_dim, act_dim, fk) if c.symmetry_augmentation else None
+        self._sym_mu = None                                  # the last minibatch's mu [3B, A] (a reference, no launch): `symmetry_gap` is formed from it once per epoch
         self.frames = 0
         self.epoch = 0
         self.last_info = {}
         self.best_reward = -float("inf")
+
+    def _symmetry_tables(self, obs_dim, state_dim, act_dim, fused):
+        """`symmetry_augmentation`: refuse by name what the map is not stated for, then the tables of G and G^2 for obs, states and actions on the trainer's
+        device, and on the hand-written path their packed form per gathered array (symmetry.pack)"""
+        from .evaluate import engine_of
+        from . import symmetry as sy
+        eng = engine_of(self.env)
+        A = int(act_dim)
+        if A not in (9, 18) or int(obs_dim) != 32 + A or int(state_dim) not in (0, int(obs_dim) + 72):
+            raise ValueError(f"params.config.symmetry_augmentation: the map is stated for obs [32 + A], states [obs + 72] (or none) and A in (9, 18); this "
+                             f"trainer has obs {obs_dim}, states {state_dim}, actions {act_dim}")
+        ec = getattr(eng, "cfg", None)
+        if ec is not None and int(getattr(ec, "dr_enable", 0)) and any(float(x) != 0.0 for x in list(ec.dr_base_pos) + list(ec.dr_stage_pos)):
+            raise ValueError("params.config.symmetry_augmentation: domain_randomization.robot_base_position / stage_position are non-zero - a scene with a "
+                             "shifted robot base or stage is not invariant under the 120-degree turn")
+        tabs = sy.tables_to(sy.trifinger_symmetry(A, int(state_dim) > 0), self.device)
+        if fused:
+            pa = sy.pack(tabs["action"])
+            tabs["packed"] = {"obs": sy.pack(tabs["obs"]), "act": pa, "old_mu": pa}
+            if tabs["states"] is not None:
+                tabs["packed"]["states"] = sy.pack(tabs["states"])
+        return tabs
+
+    def _symmetry_gap(self):
+        """mean over i and k = 1, 2 of |P^-k mu[k B + i] - mu[i]| on the last minibatch's forward (P^-1 = P^2, P^-2 = P); a device scalar"""
+        from .symmetry import apply
+        mu = self._sym_mu
+        B = mu.shape[0] // 3
+        t = self.sym["action"]
+        return 0.5 * ((apply(mu[B:2 * B], t[1]) - mu[:B]).abs().mean() + (apply(mu[2 * B:], t[0]) - mu[:B]).abs().mean())
 
     def _fused_refusal(self):
         """None, or why this network cannot run on the hand-written kernels: an activation without a kernel (swish, gelu), or a network only the extended
@@ -1057,6 +1106,8 @@ class PPOTrainer:
         sums of the logged quantities in `acc` (device tensors, no host sync).  The torch statement; a trainer on the hand-written kernels binds
         `_mb_backward_fused` under this name at construction"""
         c = self.cfg
+        if self.sym is not None:                   # the 3B minibatch (module docstring); everything below reads it through `d` and `idx` as before
+            d, idx, B = self._sym_minibatch(d, idx), slice(None), idx.numel()
         obs = d["obs"][idx]
         mu, ls = self.net.dist(obs)
         nlp = neglogp(d["act"][idx], mu, ls)
@@ -1081,9 +1132,25 @@ class PPOTrainer:
             p.grad = None
         loss.backward()
         with torch.no_grad():      # KL between the old and new diagonal Gaussians (same sigma)
-            kl = wmean((0.5 * ((mu - d["old_mu"][idx]) / ls.exp()).pow(2)).sum(-1))
+            kl_i = (0.5 * ((mu - d["old_mu"][idx]) / ls.exp()).pow(2)).sum(-1)
+            if self.sym is not None:               # over the original rows alone, divisor B
+                kl = (w[:B] * kl_i[:B]).mean() if self.ends else kl_i[:B].mean()
+                self._sym_mu = mu.detach()
+            else:
+                kl = wmean(kl_i)
             acc["kl"] += kl
             acc["loss"] += loss.detach(); acc["a_loss"] += a_loss.detach(); acc["c_loss"] += c_loss.detach()
+
+    def _sym_minibatch(self, d, idx):
+        """the 3B minibatch of `symmetry_augmentation` in plain torch: rows [k B, (k + 1) B) = G^k of obs / states, P^k of act and old_mu, the rest repeated"""
+        from .symmetry import apply
+        t = self.sym
+        img = lambda x, tabs: torch.cat([x, apply(x, tabs[0]), apply(x, tabs[1])])        # noqa: E731
+        out = {k: (img(d[k][idx], t[name]) if d[k] is not None else None) for k, name in (("obs", "obs"), ("states", "states"), ("act", "action"), ("old_mu", "action"))}
+        for k in ("old_nlp", "adv", "ret", "old_v", "w"):
+            if k in d:
+                out[k] = d[k][idx].repeat(3)
+        return out
 
     def _mb_backward_fused(self, d, idx, acc):
         """the same step on the hand-written kernels: one gather launch for the seven minibatch arrays (eight with `clip_value`: old_v), the MFMA layers, the objective
@@ -1103,7 +1170,12 @@ class PPOTrainer:
         if d["states"] is not None:
             ent.append(("states", d["states"], ns.stats() if ns is not None else None))
         assert len(ent) <= pk.GATHER_MAX                   # with every option on exactly one launch's worth
-        g = dict(zip([e[0] for e in ent], pk.gather_rows([e[1] for e in ent], idx, norm=[e[2] for e in ent])))
+        if self.sym is not None:                           # the same ONE launch writes the three images: 3B rows per array, statistics behind the transform
+            g = dict(zip([e[0] for e in ent], pk.gather_rows_sym([e[1] for e in ent], idx, [self.sym["packed"].get(e[0]) for e in ent], norm=[e[2] for e in ent])))
+            kl_rows = {"kl_rows": idx.numel()}             # the KL statistic: the original rows alone
+        else:
+            g = dict(zip([e[0] for e in ent], pk.gather_rows([e[1] for e in ent], idx, norm=[e[2] for e in ent])))
+            kl_rows = {}
         for p in self.net.parameters():
             p.grad = None
         # no autograd: the structure is fixed (two Linear / ELU stacks), so the step is a straight sequence of kernel launches from this
@@ -1118,6 +1190,9 @@ class PPOTrainer:
             kw = {"old_v": g["old_v"]} if self.clip_v else {}
             if self.ends:                                  # the gathered array is (adv_i, w_i): the weighted instantiation of the objective
                 kw["adv_w"] = g.pop("adv")
+            kw.update(kl_rows)
+            if self.sym is not None:
+                self._sym_mu = mu
             _, d_mu, d_v, _ = pk.ppo_loss_and_grads(mu, self.net.log_std, v, g["act"], g["old_nlp"], g.get("adv"), g["ret"], g["old_mu"], acc["_fused"], c.e_clip,
                                                     v_coef, c.entropy_coef, c.bounds_loss_coef, d_ls_out=self.flat_opt.grad_view(self.net.log_std), **kw)
             try:
@@ -1236,6 +1311,8 @@ class PPOTrainer:
             stats["episodes_ended"] = int(ended)
         if self.tracker is not None:
             stats.update(self._track_stats(track_vec.tolist()))
+        if self.sym is not None and self._sym_mu is not None:
+            stats["symmetry_gap"] = float(self._symmetry_gap())
         return stats
 
     def _track_stats(self, vec):

@@ -49,6 +49,8 @@ _ARGTYPES = {
     "tfp_ppo_loss_w": _LOSS, "tfp_ppo_loss_vclip_w": [_P] + _LOSS,
     # the training-time episode tracker and the episode flight recorder (include/trifinger_ppo_track.h, include/trifinger_ppo_record.h: csrc/tf_eval.hip)
     "tfp_rollout_track": [_P, _P], "tfp_record_step": [_P, _P],
+    # symmetry augmentation (include/trifinger_ppo_symmetry.h: csrc/ppo_symmetry.hip and the KL-row variant of the objective)
+    "tfp_gather_rows_sym": [_P] * 7 + [_I, _P, _I, _P], "tfp_ppo_loss_sym": [_P] * 9 + [_I] * 4 + [_R] * 4 + [_P] * 6,
 }
 
 
@@ -93,12 +95,15 @@ class _FusedPPOLoss(torch.autograd.Function):
 _LOSS_ENTRY = {(False, False): "tfp_ppo_loss", (True, False): "tfp_ppo_loss_vclip", (False, True): "tfp_ppo_loss_w", (True, True): "tfp_ppo_loss_vclip_w"}
 
 
-def ppo_loss_and_grads(mu, log_std, v, act, old_nlp, adv, ret, old_mu, stats, e_clip, v_coef, ent_coef, bounds_coef, d_ls_out=None, old_v=None, adv_w=None):
+def ppo_loss_and_grads(mu, log_std, v, act, old_nlp, adv, ret, old_mu, stats, e_clip, v_coef, ent_coef, bounds_coef, d_ls_out=None, old_v=None, adv_w=None,
+                       kl_rows=None):
     """(loss, d loss / d mu, d loss / d v, d loss / d log_std) straight from the kernel - for a caller that starts the backward pass at
     the network outputs itself (`torch.autograd.backward((mu, v), (d_mu, d_v))`), without a loss node multiplying them by one.
     `old_v` [B] (the value recorded in the rollout): the value term is clipped around it with the surrogate's `e_clip` (tfp_ppo_loss_vclip: `clip_value`).
     `adv_w` [B, 2] = (adv_i, w_i) interleaved (`episode_ends`; `adv` is then None): every per-sample term and gradient times w_i, the divisor stays B
-    (tfp_ppo_loss_w / tfp_ppo_loss_vclip_w, include/trifinger_ppo_episode.h)"""
+    (tfp_ppo_loss_w / tfp_ppo_loss_vclip_w, include/trifinger_ppo_episode.h).
+    `kl_rows` (`symmetry_augmentation`; 1 .. B): the KL statistic sums over the first kl_rows rows alone and is divided by kl_rows, everything else is
+    untouched (tfp_ppo_loss_sym, include/trifinger_ppo_symmetry.h: ONE entry point for the four cases above; with kl_rows == B their bits)"""
     lib = load()
     mu, v = mu.contiguous(), v.contiguous()
     B, A = mu.shape
@@ -110,6 +115,14 @@ def ppo_loss_and_grads(mu, log_std, v, act, old_nlp, adv, ret, old_mu, stats, e_
     d_mu, d_v = torch.empty_like(mu), torch.empty_like(v)
     out = torch.empty(A + 1, device=mu.device, dtype=torch.float32)      # d_logstd [A] and the loss
     d_ls, loss = (out[:A] if d_ls_out is None else d_ls_out), out[A]      # d_ls_out: e.g. the parameter's slot of a flat gradient buffer
+    if kl_rows is not None:
+        if not 1 <= int(kl_rows) <= B:
+            raise ValueError(f"kl_rows = {kl_rows}: the KL statistic needs between 1 and B = {B} rows")
+        _chk(lib.tfp_ppo_loss_sym(mu.data_ptr(), log_std.data_ptr(), act.data_ptr(), old_nlp.data_ptr(), adv.data_ptr(), old_mu.data_ptr(), v.data_ptr(),
+                                  ret.data_ptr(), old_v.data_ptr() if old_v is not None else None, 1 if adv_w is not None else 0, int(kl_rows), B, A,
+                                  float(e_clip), float(v_coef), float(ent_coef), float(bounds_coef), d_mu.data_ptr(), d_v.data_ptr(), d_ls.data_ptr(),
+                                  loss.data_ptr(), stats.data_ptr(), _stream(mu)), "tfp_ppo_loss_sym")
+        return loss, d_mu, d_v, d_ls
     name = _LOSS_ENTRY[old_v is not None, adv_w is not None]
     _chk(getattr(lib, name)(mu.data_ptr(), log_std.data_ptr(), act.data_ptr(), old_nlp.data_ptr(), adv.data_ptr(), old_mu.data_ptr(), v.data_ptr(), ret.data_ptr(),
                             *((old_v.data_ptr(),) if old_v is not None else ()), B, A, float(e_clip), float(v_coef), float(ent_coef), float(bounds_coef),
@@ -297,6 +310,37 @@ def _gather_rows_norm(srcs, idx, outs, norm):
                                      _vp([e[1] if e is not None else None for e in norm]),
                                      (C.c_float * n)(*[float(e[2]) if e is not None else 0.0 for e in norm]), n,
                                      idx.data_ptr() if idx is not None else None, rows, _stream(srcs[0])), "tfp_gather_rows_norm")
+    return outs
+
+
+SYM_MAX_WIDTH, SYM_MAX_COLS = 128, 512        # include/trifinger_ppo_symmetry.h: columns of one array / of all arrays of one launch together
+
+
+def gather_rows_sym(srcs, idx, tables, outs=None, norm=None):
+    """the augmenting gather (`symmetry_augmentation`): per array [3 rows, ...] - rows [k rows, (k + 1) rows) hold the k-th image of s[idx], k = 0 the plain
+    gather - for up to 8 row-major float32 arrays in ONE launch (tfp_gather_rows_sym).  `tables`: one entry per array - None (copied for every k) or the
+    packed tables of that array (symmetry.pack: int32 [2, width, 4] on the device); `norm` as in gather_rows, applied after the transform: the bits of
+    gather_rows(norm=...) on symmetry.apply of the gathered rows.  `idx` may be None (every row in place)."""
+    n = len(srcs)
+    assert 0 < n <= GATHER_MAX and len(tables) == n and all(s.dtype == torch.float32 and s.is_contiguous() and s.is_cuda for s in srcs)
+    assert idx is None or (idx.dtype == torch.long and idx.is_contiguous() and idx.device == srcs[0].device)
+    rows = idx.numel() if idx is not None else srcs[0].shape[0]
+    assert idx is not None or all(s.shape[0] == rows for s in srcs)
+    widths = [int(s[0].numel()) for s in srcs]
+    norm = norm if norm is not None else [None] * n
+    assert len(norm) == n and all(e is None or _norm_ok(e, w, s.device) for e, w, s in zip(norm, widths, srcs)), "statistics of another width, type or device"
+    for t, w, s in zip(tables, widths, srcs):
+        if t is not None and not (t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (2, w, 4) and t.device == s.device):
+            raise ValueError(f"a symmetry table of another shape, type or device than its array (width {w})")
+    if any(w > SYM_MAX_WIDTH for w in widths) or sum(widths) > SYM_MAX_COLS:
+        raise ValueError(f"the augmenting gather takes rows of at most {SYM_MAX_WIDTH} columns, and {SYM_MAX_COLS} columns over the arrays of one launch")
+    if outs is None:
+        outs = [torch.empty((3 * rows,) + tuple(s.shape[1:]), device=s.device, dtype=torch.float32) for s in srcs]
+    assert all(o.dtype == torch.float32 and o.is_contiguous() and o.numel() == 3 * rows * w and o.device == s.device for o, w, s in zip(outs, widths, srcs))
+    _chk(load().tfp_gather_rows_sym(_vp(srcs), _vp(outs), _ip(widths), _vp([e[0] if e is not None else None for e in norm]),
+                                    _vp([e[1] if e is not None else None for e in norm]),
+                                    (C.c_float * n)(*[float(e[2]) if e is not None else 0.0 for e in norm]), _vp(tables), n,
+                                    idx.data_ptr() if idx is not None else None, rows, _stream(srcs[0])), "tfp_gather_rows_sym")
     return outs
 
 

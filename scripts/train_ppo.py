@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """End-to-end PPO on the native TriFinger env (BASELINE config 5: difficulty 4, 8192 envs per GPU).
 
-    python scripts/train_ppo.py gym=trifinger_difficulty_4 args.num_envs=8192 [epochs=20] [args.checkpoint=run/nn/trifinger.pth] [save_dir=run/nn]
+    python scripts/train_ppo.py gym=trifinger_difficulty_4 args.num_envs=8192 [epochs=20] [args.checkpoint=run/nn/trifinger.pth] [save_dir=run/nn] [--symmetry]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 scripts/train_ppo.py ...
 
 One process per GPU; envs are sharded (no data-path collective), gradients are averaged with one fused RCCL
-all-reduce per minibatch.  Uses RL-Games' hyper-parameters of resources/config/rlg/asymm.yaml (leibnizgym_amd/ppo.py)."""
+all-reduce per minibatch.  Uses RL-Games' hyper-parameters of resources/config/rlg/asymm.yaml (leibnizgym_amd/ppo.py).
+--symmetry: rlg.params.config.symmetry_augmentation=True - every minibatch with its two images under the robot's 120-degree turn (leibnizgym_amd/symmetry.py)."""
 import os
 import sys
 import time
@@ -29,6 +30,8 @@ def main(argv):
             epochs = int(a.split("=", 1)[1])
         elif a.startswith("save_dir="):
             save_dir = a.split("=", 1)[1]
+        elif a == "--symmetry":
+            rest.append("rlg.params.config.symmetry_augmentation=True")
         else:
             rest.append(a)
     cfg = compose(rest)
@@ -72,7 +75,8 @@ def main(argv):
             steady = (marks[-1][1] - back[1]) / max(now - back[0], 1e-9) if len(marks) > 1 else 0.0
             print(f"epoch {st['epoch']:4d} frames {st['frames'] * world:10d} reward/step {st['mean_reward']:9.3f} "
                   f"kl {st['kl']:.4f} lr {st['lr']:.2e} loss {st['loss']:.4f}  {st['frames'] * world / (now - t0):.3e} frames/s "
-                  f"since start, {steady:.3e} over the last {min(len(marks) - 1, 10)} epochs{episode_line(st)}", flush=True)
+                  f"since start, {steady:.3e} over the last {min(len(marks) - 1, 10)} epochs{episode_line(st)}"
+                  + (f" symmetry gap {st['symmetry_gap']:.4f}" if "symmetry_gap" in st else ""), flush=True)
     tr.train(epochs, log, checkpoint_dir=save_dir if rank == 0 else None)
     if world > 1 or launched:
         if rank == 0:
