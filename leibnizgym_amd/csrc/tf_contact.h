@@ -80,7 +80,9 @@ template <int LINK> DEV void link_point(const FK& k, const float local[3], float
 // Joint-space rows of a contact on link `link` (per-lane value) at base-frame point Pb for the three world directions
 // dirs[3d..3d+2]: J[3d..] = (L1.d, L2.d, L3.d) with the levers of the joints that do not move the link zeroed,
 // W[3d..] = M^-1 J, Dd[d] = J.W.
-DEV void finger_jac(const Yaw& y, const FK& k, int link, const float Pb[3], const float dirs[9], float J[9], float W[9], float Dd[3]) {
+// db_xy (the fingertip-floor rows of the 128-register kernels without domain randomisation; DevParams::tip_floor_db): x and y of the three directions in the
+// base frame where dirs is made of literals - dir_world_to_base of constants and the yaw, formed once by the host with the same operations.
+DEV void finger_jac(const Yaw& y, const FK& k, int link, const float Pb[3], const float dirs[9], float J[9], float W[9], float Dd[3], const float* db_xy = nullptr) {
     float L1[3], L2[3], L3[3];
     levers(k, Pb, L1, L2, L3);
     if (link < 2) { L2[0] = 0.0f; L2[1] = 0.0f; L2[2] = 0.0f; }
@@ -88,7 +90,8 @@ DEV void finger_jac(const Yaw& y, const FK& k, int link, const float Pb[3], cons
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
         float db[3];
-        dir_world_to_base(y, &dirs[3 * d], db);
+        if (db_xy) { db[0] = db_xy[2 * d]; db[1] = db_xy[2 * d + 1]; db[2] = dirs[3 * d + 2]; }
+        else dir_world_to_base(y, &dirs[3 * d], db);
         J[3 * d] = dot3(L1, db); J[3 * d + 1] = dot3(L2, db); J[3 * d + 2] = dot3(L3, db);
         sym3_mul(k.Minv, &J[3 * d], &W[3 * d]);
         Dd[d] = dot3(&J[3 * d], &W[3 * d]);

@@ -348,7 +348,16 @@ DEV void levers(const FK& k, const float P[3], float L1[3], float L2[3], float L
 // hence  dw x r + w x (w x r) = (w (2 a r_y - w r_x), -a^2 r_y, -(a^2 + w^2) r_z).  Only the components that reach
 // the three joint torques (n1_y, n2_x, n3_x) are formed.  tests/test_physics_analytic.py checks M against the fp64
 // kinetic energy and h against the Lagrangian derivatives of an independent model.
-DEV void finger_dynamics(const DevModel& m, const FK& k, const float qd[3], const float grav[3], float M[6], float bias[3]) {
+// FOLD (the 128-register kernels without domain randomisation): the subexpressions of M that hold model constants only come from the host (FdInvariants,
+// filled by tf_create with these very operations) instead of being formed here - the same bits, no vector register held through the substep.
+struct FdInvariants {
+    float c2x, c3x;          // x of COM 2 and COM 3 in frame A: j2_origin[0] + link_com[1][0], j2_origin[0] + (j3_origin[0] + link_com[2][0])
+    float m1c1;              // the link-1 term of M[0]: m1 * FMA(c1x, c1x, c1z * c1z)
+    float m2c2x, m3c3x;      // m2 * c2x, m3 * c3x (M[1], M[2])
+    float i23;               // I2[0] + I3[0] (M[3])
+};
+template <bool FOLD = false>
+DEV void finger_dynamics(const DevModel& m, const FK& k, const float qd[3], const float grav[3], float M[6], float bias[3], const FdInvariants* K = nullptr) {
     const float m1 = m.link_mass[0], m2 = m.link_mass[1], m3 = m.link_mass[2];
     const float* I1 = m.link_inertia[0];
     const float* I2 = m.link_inertia[1];
@@ -367,19 +376,24 @@ DEV void finger_dynamics(const DevModel& m, const FK& k, const float qd[3], cons
     e3[1] = FMA(k.c23, m.link_com[2][1], -(k.s23 * m.link_com[2][2]));
     e3[2] = FMA(k.s23, m.link_com[2][1], k.c23 * m.link_com[2][2]);
     e2[0] = d23[0] + e3[0]; e2[1] = d23[1] + e3[1]; e2[2] = d23[2] + e3[2];     /* joint 2 -> COM 3 */
-    const float c2x = p2[0] + b[0], c2z = p2[2] + b[2];                           /* COM 2 (x, z) */
-    const float c3x = p2[0] + e2[0], c3z = p2[2] + e2[2];                         /* COM 3 (x, z) */
+    const float c2x = FOLD ? K->c2x : p2[0] + b[0], c2z = p2[2] + b[2];           /* COM 2 (x, z) */
+    const float c3x = FOLD ? K->c3x : p2[0] + e2[0], c3z = p2[2] + e2[2];         /* COM 3 (x, z) */
     /* ---- mass matrix: linear part from the COM lever arms L1 = y x P = (P_z, 0, -P_x), L2/L3 = x x r = (0, -r_z, r_y);
      * angular part from the joint axes seen in the link frames, y -> (0, c, -s), x -> x ---- */
     const float u2I = FMA(k.s2 * k.s2, I2[2], FMA(k.c2 * k.c2, I2[1], ((-2.0f * k.c2) * k.s2) * I2[5]));
     const float u3I = FMA(k.s23 * k.s23, I3[2], FMA(k.c23 * k.c23, I3[1], ((-2.0f * k.c23) * k.s23) * I3[5]));
     const float u2x = FMA(k.c2, I2[3], -(k.s2 * I2[4]));
     const float u3x = FMA(k.c23, I3[3], -(k.s23 * I3[4]));
-    M[0] = FMA(m3, FMA(c3x, c3x, c3z * c3z), FMA(m2, FMA(c2x, c2x, c2z * c2z), m1 * FMA(c1[0], c1[0], c1[2] * c1[2])))
+    M[0] = FMA(m3, FMA(c3x, c3x, c3z * c3z), FMA(m2, FMA(c2x, c2x, c2z * c2z), FOLD ? K->m1c1 : m1 * FMA(c1[0], c1[0], c1[2] * c1[2])))
            + ((I1[1] + u2I) + u3I);
-    M[1] = (u2x + u3x) - FMA(m3 * c3x, e2[1], (m2 * c2x) * b[1]);
-    M[2] = FMA(-(m3 * c3x), e3[1], u3x);
-    M[3] = FMA(m3, FMA(e2[1], e2[1], e2[2] * e2[2]), FMA(m2, FMA(b[1], b[1], b[2] * b[2]), I2[0] + I3[0]));
+    if (FOLD) {
+        M[1] = (u2x + u3x) - FMA(K->m3c3x, e2[1], K->m2c2x * b[1]);
+        M[2] = FMA(-K->m3c3x, e3[1], u3x);
+    } else {
+        M[1] = (u2x + u3x) - FMA(m3 * c3x, e2[1], (m2 * c2x) * b[1]);
+        M[2] = FMA(-(m3 * c3x), e3[1], u3x);
+    }
+    M[3] = FMA(m3, FMA(e2[1], e2[1], e2[2] * e2[2]), FMA(m2, FMA(b[1], b[1], b[2] * b[2]), FOLD ? K->i23 : I2[0] + I3[0]));
     M[4] = FMA(m3, FMA(e2[1], e3[1], e2[2] * e3[2]), I3[0]);
     M[5] = FMA(m3, FMA(e3[1], e3[1], e3[2] * e3[2]), I3[0]);
     /* ---- recursive Newton-Euler with zero joint acceleration, base acceleration = -gravity (in frame A) ---- */

@@ -86,7 +86,20 @@ struct DevParams {
     float inv_hsub;          // 1 / hsub
     float inv_cube_mass;     // 1 / m.cube_mass: the kernels without domain randomisation (factor 1.0f)
     float ffm_inv_j;         // f_rcp(j3_y^2 + j3_z^2) of the middle frame of the middle-distal rows
+    // whole subexpressions of launch-invariant scalars (model, hsub) that the 128-register kernels without domain randomisation formed on the vector ALU before
+    // the substep loop and kept in spill slots through it: formed once by the host (tf_create: fill_invariants) with the same fp32 operations in the same order
+    float inv_cube_inertia;  // 1 / m.cube_inertia (factors 1.0f)
+    float link_damp;         // 1 - hsub * m.link_angular_damping
+    float cube_damp_l, cube_damp_a;      // 1 - hsub * m.cube_linear_damping, 1 - hsub * m.cube_angular_damping
+    FdInvariants fd;         // the constant terms of the mass matrix (tf_device_math.h: finger_dynamics)
+    float tip_floor_db[3][6];            // finger f, fingertip-floor rows: x and y of the row directions (0, 0, 1), t1, t2 in the finger's base frame (dir_world_to_base; z is the literal)
 };
+
+// A member of the parameter block fetched where it is used: behind an index the optimiser cannot see through (a zero in a scalar register) the scalar
+// load cannot be hoisted out of the substep loop, where its value would hold an SGPR - or a spill lane - through every sweep (a register-allocation aid
+// like IN_FLIGHT4; the bits are the same).  The index, not the pointer, is opaque: a pointer that went through an asm statement counts as captured, and
+// every store of the kernel would then be taken to clobber the parameter block (its loads would leave the scalar cache).
+template <class T> DEV const T* fetch_here(const T* p) { int z = 0; asm volatile("" : "+s"(z)); return p + z; }
 
 // what changes every launch travels by value; everything else is read through a pointer to constant
 // device memory so that the ~200 scalars of DevParams are fetched (scalar cache) where they are used

@@ -107,6 +107,39 @@ struct Ctx {
     bool valid;
 };
 
+// The lane's indices formed anew behind the substep loop (128-register kernels): v_mbcnt gives the lane from nothing, the role and the wavefront's first
+// env are scalars.  What the post phase needs of tid, lane and the env index then does not live through the substeps - where it had no register and sat in
+// spill slots, each reload a round trip behind the stores of the last substep.  The zero the optimiser cannot see through keeps the new values from being
+// merged with the old ones (a register-allocation aid like IN_FLIGHT4; the same numbers).
+DEV const Ctx& ctx_again(const DevParams& P, const Ctx& cx, Ctx& out) {
+    unsigned z = 0u;
+    asm volatile("" : "+s"(z));
+    const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, z));
+    const int i_raw = cx.wave_first + lane;
+    out = cx;
+    out.lane = lane;
+    out.tid = (cx.role << 6) | lane;
+    out.i = (i_raw < P.N) ? i_raw : (P.N - 1);
+    return out;
+}
+
+// Behind the substeps of a role (CTX_AGAIN) and as the first statement of every block that follows (CTX_AGAIN_HERE): cx, lane and gid of the block are the
+// ones formed anew.  The units of the 128-register kernels only (-DTF_WIDE=0): the preprocessor, not a template argument, so that the 256-register and helper
+// units see the text they always saw - a declaration more or less in a role moves instructions in their code.
+#if defined(TF_WIDE) && TF_WIDE == 0
+#define CTX_AGAIN() constexpr bool AGAIN = (MODE & M_SIM) != 0; Ctx cx_new_; const Ctx& cx_post_ = AGAIN ? ctx_again(P, cx, cx_new_) : cx; \
+                    const int lane_role_ = lane; const uint32_t gid_role_ = gid; (void)lane_role_; (void)gid_role_
+#define CTX_AGAIN_HERE() const Ctx& cx = cx_post_; const int lane = AGAIN ? cx.lane : lane_role_; const uint32_t gid = AGAIN ? (uint32_t)(P.env_id_offset + cx.i) : gid_role_; (void)lane; (void)gid
+#define LANE_AGAIN() (AGAIN ? cx_post_.lane : lane)
+// the record's 1 / cube_inertia: the host's quotient, fetched where it is used (without domain randomisation; the division in front of the loop is then dead)
+#define INV_I_HERE() const float inv_I_top_ = inv_I; const float inv_I = DR ? inv_I_top_ : *fetch_here(&P.inv_cube_inertia)
+#else
+#define INV_I_HERE() (void)0
+#define CTX_AGAIN() (void)0
+#define CTX_AGAIN_HERE() (void)0
+#define LANE_AGAIN() lane
+#endif
+
 #define ST_RSRC() __builtin_amdgcn_make_buffer_rsrc((void*)P.state, 0, TF_STATE_ROWS * P.N * 4, 0x00020000)
 #define LDST(row) __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ST_RSRC(), (unsigned)cx.i * 4u, (row) * P.N * 4, 0))
 #define STST(row, val) do { if (cx.valid) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (float)(val)), ST_RSRC(), (unsigned)cx.i * 4u, (row) * P.N * 4, 0); } while (0)
@@ -660,7 +693,7 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
             {
                 float M[6], bias[3], rhs[3], acc[3];
                 fk_setup(m, q, k);
-                finger_dynamics(m, k, qd, P.grav, M, bias);
+                finger_dynamics<!DR && !WIDE>(m, k, qd, P.grav, M, bias, (!DR && !WIDE) ? fetch_here(&P.fd) : nullptr);      // (128-register kernels without domain randomisation: the constant terms of M are the host's)
 #pragma unroll
                 for (int j = 0; j < 6; ++j) M[j] = M[j] * dr[4];
 #pragma unroll
@@ -669,7 +702,7 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
 #pragma unroll
                 for (int j = 0; j < 3; ++j) rhs[j] = tau[j] - bias[j];
                 sym3_mul(k.Minv, rhs, acc);
-                const float damp = 1.0f - h * m.link_angular_damping;
+                const float damp = (DR || WIDE) ? 1.0f - h * m.link_angular_damping : *fetch_here(&P.link_damp);
 #pragma unroll
                 for (int j = 0; j < 3; ++j) vq[j] = FMA(h, acc[j], qd[j]) * damp;
                 if (!WIDE && m.ff_middle_pairs != 0) {      // how fast this finger's distal and middle link can move at all: the gate of the middle-distal rows (tf_contact.h: ff_gate)
@@ -967,6 +1000,7 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
                     fc_live = true;
 #pragma unroll
                     for (int j = 0; j < 9; ++j) { fcJ[j] = J[j]; LD(rb + R_DIR + j) = dir[j]; LD(rb + R_RXD + j) = rxd[j]; }
+                    INV_I_HERE();
 #pragma unroll
                     for (int d = 0; d < 3; ++d) LD(L_VQFF + 3 * f + d) = f_rcp2(FMA(dot3(&rxd[3 * d], &rxd[3 * d]), inv_I, Dd[d] + inv_m));
                     LD(rb + R_A + 0) = FMA(dot3(&rxd[0], &rxd[3]), inv_I, dot3(&J[0], &W[3]));
@@ -1021,7 +1055,7 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
                         float Pw[3] = {FMA(-m.cap_radius, dir[0], Bw[0]), FMA(-m.cap_radius, dir[1], Bw[1]), FMA(-m.cap_radius, dir[2], Bw[2])};
                         float Pb[3], Dd[3], Jt[9], Wt[9];
                         world_to_base(yw, Pw, Pb);
-                        finger_jac(yw, k, 3, Pb, dir, Jt, Wt, Dd);
+                        finger_jac(yw, k, 3, Pb, dir, Jt, Wt, Dd, (t == 0 && !DR && !WIDE) ? fetch_here(&P.tip_floor_db[f][0]) : nullptr);      // (floor: the directions are literals, their base-frame images the host's)
                         float vn0 = dot3(&Jt[0], vq);
                         if (contact_live(m, gp_, vn0, h)) {
                             c.active = true;
@@ -1219,11 +1253,13 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
         }
     }
     STAMP(30);
+    CTX_AGAIN();
     // =================================================================================================================
     // post: fingertip state, observation slots of this finger
     // =================================================================================================================
     bool f_guarded = false;                                    // NaN guard of the env (set in the post phase; read by the presampler below)
     if (MODE & M_POST) {
+        CTX_AGAIN_HERE();
         FK pk;
         float tips[13];
         fk_setup(m, q, pk);
@@ -1350,6 +1386,7 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
     }
     // ---- state rows of this finger ----
     if (MODE & (M_RESETS | M_SIM | M_POST)) {
+        CTX_AGAIN_HERE();
 #pragma unroll
         for (int j = 0; j < 3; ++j) { STST(TF_S_Q + 3 * f + j, q[j]); STST(TF_S_QD + 3 * f + j, qd[j]); }
     }
@@ -1357,6 +1394,7 @@ DEV void finger_role(const DevParams& P, const StepArgs& sa, const float* __rest
     // the cube wavefront still evaluates rewards and statistics - one third each: finger 0 the object pose and the tag, finger 1 the goal position,
     // finger 2 the goal orientation and angular velocity (include/trifinger.h: TF_S_NEXT_*; the cube role's reset block loads them) ----
     if (PRESAMPLE) {
+        CTX_AGAIN_HERE();
         const int steps_now = (rflag ? 0 : fl_steps) + 1;                                        // what the cube role writes to steps[] at the end of this step
         const bool will_reset = f_guarded || (P.episode_length > 0 && steps_now >= P.episode_length);    // = reset_buf after this step
         if (__builtin_expect(__builtin_amdgcn_ballot_w64(will_reset) != 0ull, 0)) {
@@ -1880,7 +1918,7 @@ DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restri
             const float* dr = drs;
             const float cube_mass = m.cube_mass * dr[0];
             const float cube_inertia = m.cube_inertia * dr[0] * dr[1] * dr[1];
-            const float inv_m = (DR || WIDE) ? 1.0f / cube_mass : P.inv_cube_mass, inv_I = 1.0f / cube_inertia;      // (128-register kernels without domain randomisation: the mass is the model's - the host's quotient, the same bits)
+            const float inv_m = (DR || WIDE) ? 1.0f / cube_mass : P.inv_cube_mass, inv_I = (DR || WIDE) ? 1.0f / cube_inertia : P.inv_cube_inertia;      // (128-register kernels without domain randomisation: mass and inertia are the model's - the host's quotients, the same bits)
             const float fr1 = dr[TF_DR_FRICTION_ROBOT] - 1.0f, fo1 = dr[TF_DR_FRICTION_OBJECT] - 1.0f, fs1 = dr[TF_DR_FRICTION_STAGE] - 1.0f;
             const float mu_fc = (m.mu_finger_cube * dr[2]) * (EXT ? pair_factor(m.mu_robot, fr1, m.mu_object, fo1) : 1.0f);
             const float mu_cf = (m.mu_cube_floor * dr[2]) * (EXT ? pair_factor(m.mu_object, fo1, m.mu_floor, fs1) : 1.0f);
@@ -1908,7 +1946,7 @@ DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restri
                     for (int k = 0; k < 3; ++k) wb[k] = FMA(h, tq[k] / m.box_inertia[k], wb[k]);
                     mat3_mul(R, wb, wf);
                 }
-                float dl = 1.0f - h * m.cube_linear_damping, da = 1.0f - h * m.cube_angular_damping;
+                float dl = (DR || WIDE) ? 1.0f - h * m.cube_linear_damping : P.cube_damp_l, da = (DR || WIDE) ? 1.0f - h * m.cube_angular_damping : P.cube_damp_a;
 #pragma unroll
                 for (int j = 0; j < 3; ++j) {
                     v[j] = FMA(h, P.grav[j], cv[j]) * dl;
@@ -2596,18 +2634,21 @@ DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restri
         __builtin_amdgcn_s_setprio(0);
     }
     STAMP(30);
+    CTX_AGAIN();
     // =================================================================================================================
     // post: observations of the object and the goal, rewards, termination, statistics
     // =================================================================================================================
     StatsTicket tk;
     tk.mine = 0ull; tk.old = 0ull;
     if (MODE & (M_POST | M_FINISH)) {     // the flag buffers as the reset logic left them (cold through the physics: re-read)
+        CTX_AGAIN_HERE();
         c_reset = P.reset_buf[(unsigned)cx.i] != 0;
         c_goal_reset = P.goal_reset_buf[(unsigned)cx.i] != 0;
         c_successes = P.successes[(unsigned)cx.i] != 0;
         c_steps = (int)P.steps[(unsigned)cx.i];
     }
     if (MODE & M_POST) {
+        CTX_AGAIN_HERE();
         float gp[3], gq[4], prev_obj[7];                        // cold through the physics: re-read from their rows
 #pragma unroll
         for (int j = 0; j < 3; ++j) gp[j] = LDST(TF_S_GOAL_P + j);
@@ -2751,12 +2792,14 @@ DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restri
     // ---- state rows of the cube role; the moving goal advances AFTER the step's observations and rewards used its pose
     // (trifinger_env.py:500-559: __update_goal_movement_post comes last) ----
     if (MODE & (M_RESETS | M_SIM | M_POST)) {
+        CTX_AGAIN_HERE();
 #pragma unroll
         for (int j = 0; j < 3; ++j) { STST(TF_S_CUBE_P + j, cp[j]); STST(TF_S_CUBE_V + j, cv[j]); STST(TF_S_CUBE_W + j, cw[j]); }
 #pragma unroll
         for (int j = 0; j < 4; ++j) STST(TF_S_CUBE_Q + j, cq[j]);
     }
     if (MODE & (M_RESETS | M_SIM)) {
+        CTX_AGAIN_HERE();
 #pragma unroll
         for (int j = 0; j < 12; ++j) STST(TF_S_LAM_CF + j, lam_cf[j]);
         STST(TF_S_CF_FACE, cf_face); STST(TF_S_CW_FACE, cw_face);
@@ -2766,6 +2809,7 @@ DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restri
         }
     }
     if ((MODE & M_POST) && P.goal_rotation_activate) {
+        CTX_AGAIN_HERE();
         float gq2[4], gw2[3];
 #pragma unroll
         for (int j = 0; j < 4; ++j) gq2[j] = LDST(TF_S_GOAL_Q + j);
@@ -2778,6 +2822,7 @@ DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restri
     }
     STAMP(38);
     if (MODE & M_FINISH) {                                      // env_base.py:391-399
+        CTX_AGAIN_HERE();
         if (cx.valid) {
             int sN = c_steps + 1;
             P.steps[(unsigned)cx.i] = (int64_t)sN;
@@ -2787,7 +2832,7 @@ DEV void cube_role(const DevParams& P, const StepArgs& sa, const float* __restri
         }
     }
     STAMP(39);
-    if (MODE & M_POST) stats_end(P, lane, tk);
+    if (MODE & M_POST) stats_end(P, LANE_AGAIN(), tk);
     STAMP(35);
     STAMPV(40, __builtin_amdgcn_s_getreg((31 << 11) | 4));      // HW_REG_HW_ID
     STAMPV(41, __builtin_amdgcn_s_getreg((31 << 11) | 20));     // HW_REG_XCC_ID

@@ -366,6 +366,67 @@ static void build_tables(const TfConfig* c, int A, float* tab, int* obs_dim, int
     }
 }
 
+// The launch-invariant subexpressions of the 128-register kernels without domain randomisation (tf_params.h), formed on P.m and P.hsub with the fp32
+// operations of the kernel lines they replace, in their order: fmaf where the kernel has FMA, one IEEE division where it divides (-ffp-contract=off
+// holds for this unit too).  volatile keeps every intermediate a rounded float whatever the host compiler would like to do with the expression.
+static float host_rsqrt(float x) {                 // f_rsqrt (tf_device_math.h)
+    uint32_t xb, yb;
+    memcpy(&xb, &x, 4);
+    yb = 0x5F375A86u - (xb >> 1);
+    float y;
+    memcpy(&y, &yb, 4);
+    const float h = 0.5f * x;
+    for (int it = 0; it < 3; ++it) { volatile float yy = y * y; y = y * fmaf(-h, yy, 1.5f); }
+    return y;
+}
+static void host_cross3(const float a[3], const float b[3], float o[3]) {      // cross3
+    volatile float p0 = a[2] * b[1], p1 = a[0] * b[2], p2 = a[1] * b[0];
+    o[0] = fmaf(a[1], b[2], -p0);
+    o[1] = fmaf(a[2], b[0], -p1);
+    o[2] = fmaf(a[0], b[1], -p2);
+}
+static void host_tangent_basis(const float n[3], float t1[3], float t2[3]) {    // tangent_basis
+    if (fabsf(n[2]) < 0.9f) {
+        volatile float p = n[1] * n[1];
+        const float inv = host_rsqrt(fmaf(n[0], n[0], p));
+        t1[0] = -n[1] * inv; t1[1] = n[0] * inv; t1[2] = 0.0f;
+    } else {
+        volatile float p = n[2] * n[2];
+        const float inv = host_rsqrt(fmaf(n[1], n[1], p));
+        t1[0] = 0.0f; t1[1] = -n[2] * inv; t1[2] = n[1] * inv;
+    }
+    host_cross3(n, t1, t2);
+}
+static void fill_invariants(DevParams& P) {
+    const DevModel& m = P.m;
+    const float h = P.hsub;
+    P.inv_cube_inertia = 1.0f / m.cube_inertia;
+    { volatile float t = h * m.link_angular_damping; P.link_damp = 1.0f - t; }
+    { volatile float t = h * m.cube_linear_damping; P.cube_damp_l = 1.0f - t; }
+    { volatile float t = h * m.cube_angular_damping; P.cube_damp_a = 1.0f - t; }
+    // finger_dynamics: c2x = p2[0] + b[0], c3x = p2[0] + e2[0] with e2[0] = d23[0] + e3[0]; the link-1 term of M[0]; m2 * c2x, m3 * c3x; I2[0] + I3[0]
+    const float* c1 = m.link_com[0];
+    volatile float e2x = m.j3_origin[0] + m.link_com[2][0];
+    P.fd.c2x = m.j2_origin[0] + m.link_com[1][0];
+    P.fd.c3x = m.j2_origin[0] + e2x;
+    { volatile float zz = c1[2] * c1[2]; volatile float s = fmaf(c1[0], c1[0], zz); P.fd.m1c1 = m.link_mass[0] * s; }
+    P.fd.m2c2x = m.link_mass[1] * P.fd.c2x;
+    P.fd.m3c3x = m.link_mass[2] * P.fd.c3x;
+    P.fd.i23 = m.link_inertia[1][0] + m.link_inertia[2][0];
+    // fingertip-floor rows: directions (0, 0, 1), t1, t2 of tangent_basis, turned into each finger's base frame (dir_world_to_base: x and y)
+    float dir[9] = {0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    host_tangent_basis(&dir[0], &dir[3], &dir[6]);
+    for (int f = 0; f < 3; ++f) {
+        const float c = m.base_yaw_cos[f], s = m.base_yaw_sin[f];
+        for (int d = 0; d < 3; ++d) {
+            const float* w = &dir[3 * d];
+            volatile float p0 = s * w[1], p1 = s * w[0];
+            P.tip_floor_db[f][2 * d] = fmaf(c, w[0], p0);
+            P.tip_floor_db[f][2 * d + 1] = fmaf(c, w[1], -p1);
+        }
+    }
+}
+
 int tf_create(const TfConfig* cfg, tf_handle* out) {
     if (!cfg || !out) return TF_ERR_INVALID_ARG;
     if (cfg->api_version != TF_API_VERSION || cfg->num_envs <= 0) return TF_ERR_INVALID_ARG;
@@ -450,6 +511,7 @@ int tf_create(const TfConfig* cfg, tf_handle* out) {
         for (int it = 0; it < 3; ++it) r = fmaf(r, fmaf(-x, r, 1.0f), r);
         P.ffm_inv_j = r;
     }
+    fill_invariants(P);
     {   // link-speed gate of the middle-distal rows (tf_contact.h: ff_link_speeds): model constants, rounded up
         // (tools/experiments/ff_gate_census.patch restates these lines and ff_link_speeds in C for the census on the oracle: change them together)
         const TfModel& cm = cfg->model;

@@ -11,7 +11,9 @@ with a linear scan over the instruction stream.  It prints, per region between t
     load it sits, and the source line of that load,
   - chains load -> wait -> load -> wait (dependent round trips),
 and for the whole kernel the loops that hold barriers with any vector-memory or scratch instruction inside them, the
-spill / scratch figures of the metadata, and the summary counts tests/test_isa_memory_waits.py puts caps on.
+scratch reloads in those loops that fetch what was stored in front of the loop (and whether that value was formed from
+scalar registers and literals only: a constant of the launch parked in a spill slot), the spill / scratch figures of the
+metadata, and the summary counts the tests/test_isa_*.py put caps on.
 
     python tools/isa_waits.py [--unit 0_0] [--kernel SUBSTR] [--full] [--no-min] [--asm FILE] [--keep FILE] [--json] [--quiet]
 
@@ -333,14 +335,134 @@ def max_run(chain):
     return best if best >= 2 else 0
 
 
+def loop_code(ins, lp):
+    """the instructions of a loop of find_loops, in text order"""
+    leaders = {0}
+    for i in ins:
+        if i.labels:
+            leaders.add(i.idx)
+        if i.op.startswith(("s_cbranch", "s_branch")) or i.op == "s_endpgm":
+            leaders.add(i.idx + 1)
+    starts = sorted(x for x in leaders if x < len(ins))
+    out = []
+    for b in sorted(lp["blocks"]):
+        out += ins[starts[b]:(starts[b + 1] if b + 1 < len(starts) else len(ins))]
+    return out
+
+
+def _regs(tok):
+    """registers an operand names: ("v", {numbers}) / ("s", ...) / None for literals, inline constants, vcc, exec, off, modifiers"""
+    tok = tok.strip().lstrip("-|").rstrip("|")
+    m = re.match(r"^([vsa])(\d+)$", tok)
+    if m:
+        return m.group(1), {int(m.group(2))}
+    m = re.match(r"^([vsa])\[(\d+):(\d+)\]$", tok)
+    if m:
+        return m.group(1), set(range(int(m.group(2)), int(m.group(3)) + 1))
+    return None
+
+
+def _operands(text):
+    body = text.split(None, 1)[1] if " " in text else ""
+    return [t for t in re.split(r",\s*(?![^\[]*\])", body) if t]
+
+
+def scratch_slot(i):
+    """(first byte, bytes) of the scratch slot a scratch_load / scratch_store touches"""
+    m = re.search(r"offset:(\d+)", i.text)
+    w = re.search(r"dwordx(\d)", i.op)
+    return (int(m.group(1)) if m else 0), 4 * (int(w.group(1)) if w else 1)
+
+
+ACCUMULATING = ("v_fmac", "v_mac", "v_pk_fmac", "v_dot")      # the destination is a source too
+MAX_TRACE = 600
+
+
+def wave_uniform(ins, at, reg, depth=0):
+    """Is VGPR `reg`, as instruction `at` reads it, formed from scalar registers and literals only?  A backward walk over the text (like the rest of this
+    tool it follows the text, not the control flow): the nearest earlier instruction that writes the register decides - a vector-ALU instruction whose sources
+    are SGPRs, literals or VGPRs that are themselves uniform.  Anything else (a load, a lane instruction, a select, no definition inside the basic block) counts
+    as per lane."""
+    if depth > 12:
+        return False
+    for k in range(at - 1, max(at - MAX_TRACE, -1), -1):
+        i = ins[k]
+        if ins[k + 1].labels or re.search(r"\bexec\b", i.text.split(",")[0]) or i.op.startswith(("s_cbranch", "s_branch")):
+            return False                                     # the walk stays inside one basic block with one EXEC mask: a write further up may have been a partial one
+        ops = _operands(i.text)
+        if not ops or not i.op.startswith("v_"):
+            d = _regs(ops[0]) if ops else None
+            if d and d[0] == "v" and reg in d[1] and not i.op.startswith(("scratch_store", "global_store", "buffer_store", "flat_store", "ds_write")):
+                return False                                 # written by a load
+            continue
+        d = _regs(ops[0])
+        if not (d and d[0] == "v" and reg in d[1]):
+            continue
+        if i.op.startswith(("v_cndmask", "v_mbcnt", "v_writelane", "v_readlane", "v_readfirstlane", "v_permlane", "v_mov_b32_dpp", "v_div_fmas", "v_accvgpr")) and not i.op.startswith("v_div_fmas"):
+            return False
+        srcs = ops[1:]
+        if i.op.startswith("v_div_scale"):                   # two destinations: the value and a scalar mask
+            srcs = ops[2:]
+        if i.op.startswith(ACCUMULATING):
+            srcs = srcs + [ops[0]]
+        for t in srcs:
+            r = _regs(t)
+            if r is None or r[0] == "s":
+                continue
+            if r[0] != "v" or not all(wave_uniform(ins, k, x, depth + 1) for x in r[1]):
+                return False
+        return True
+    return False
+
+
+def loop_reloads(ins, lp):
+    """every scratch reload inside loop lp whose slot is stored in front of the loop: the store, and whether the stored value is wave-uniform"""
+    code = loop_code(ins, lp)
+    inside = {i.idx for i in code}
+    first = min(inside)
+    out = []
+    for ld in code:
+        if ld.kind != "sload":
+            continue
+        lo, n = scratch_slot(ld)
+        stores = []
+        for st in ins[:first]:
+            if st.kind == "sstore" and st.idx not in inside:
+                slo, sn = scratch_slot(st)
+                if slo < lo + n and lo < slo + sn:
+                    stores.append(st)
+        if not stores or any(st.kind == "sstore" and scratch_slot(st)[0] < lo + n and lo < sum(scratch_slot(st)) for st in code):
+            continue                                         # stored inside the loop (or nowhere in front of it): not a value parked in front of the loop
+        st = stores[-1]                                      # the last store in front of the loop is the one the loop finds
+        r = _regs(_operands(st.text)[1])
+        uniform = bool(r) and r[0] == "v" and all(wave_uniform(ins, st.idx, x) for x in r[1])
+        out.append(dict(load=ld, store=st, slot=lo, bytes=n, uniform=uniform))
+    return out
+
+
+def barrier_loop_reloads(ins, loops):
+    """loop_reloads of every loop that holds barriers (an inner loop's reloads are its outer loop's too: counted once, by instruction)"""
+    seen, out = set(), []
+    for lp in loops:
+        for r in loop_reloads(ins, lp):
+            if r["load"].idx not in seen:
+                seen.add(r["load"].idx)
+                out.append(dict(r, loop=lp["label"]))
+    return out
+
+
 def run(unit="0_0", kernel=HEADLINE, dev_min=True, asm=None, keep=None):
     if unit.startswith("d") and kernel.startswith("k_envI"):      # the d0_* and d2_* units (domain randomisation as a run-time flag): the same kernels, named k_env_dr
         kernel = "k_env_dr" + kernel[len("k_env"):]
     text = open(asm).read() if asm else compile_unit(unit, dev_min, keep)
     name, ins, meta = extract_kernel(text, kernel)
     waits, single, chains, counts, loops = analyse(ins)
-    return dict(name=name, ins=ins, meta=meta, waits=waits, single=single, chains=chains, counts=counts, loops=loops,
-                summary=summary(name, ins, meta, waits, single, chains, loops))
+    reloads = barrier_loop_reloads(ins, loops)
+    s = summary(name, ins, meta, waits, single, chains, loops)
+    s["barrier_loop_scratch_max"] = max([len(lp["scratch"]) for lp in loops], default=0)      # most scratch instructions in one loop that holds barriers
+    s["loop_reloads_of_preloop_stores"] = len(reloads)                                       # scratch reloads in such loops of values stored in front of the loop
+    s["loop_reloads_of_preloop_uniform"] = sum(r["uniform"] for r in reloads)                # ... of values formed from scalar registers and literals only
+    return dict(name=name, ins=ins, meta=meta, waits=waits, single=single, chains=chains, counts=counts, loops=loops, reloads=reloads, summary=s)
 
 
 def main():
@@ -392,6 +514,10 @@ def main():
             if lp["innermost"]:
                 for x in lp["vmem"] + lp["scratch"]:
                     print("        @%d %s   %s" % (x.idx, x.text, x.loc))
+        print("\nscratch reloads inside loops that hold barriers of values stored in front of the loop (uniform: formed from scalar registers and literals only):")
+        for x in r["reloads"]:
+            print("    slot %3d (%d B) %-8s stored @%d %s, reloaded @%d %s in %s" % (x["slot"], x["bytes"], "uniform" if x["uniform"] else "per lane",
+                  x["store"].idx, x["store"].loc, x["load"].idx, x["load"].loc, x["loop"]))
     print("\nsummary")
     for k, v in s.items():
         if k != "kernel":
