@@ -25,6 +25,9 @@
 // tfp_ppo_loss_sym (include/trifinger_ppo_symmetry.h; `symmetry_augmentation`) is the same kernel once more with a row count of its own for the KL statistic
 // (KLR): the rows i >= kl_rows add nothing to it and its divisor is kl_rows - the augmented rows of a minibatch train, the statistic that drives the adaptive
 // learning rate reads the original rows alone.  With kl_rows == B every bit is that of the entry point (old_v, weighted) selects.
+// tfp_ppo_loss_diag / tfp_clip_adam_diag (include/trifinger_ppo_diag.h; `diagnostics`) are the DIAG instantiations of the objective and of k_clip_adam: they
+// form no quantity of the loss, of a gradient or of the update differently and count, on the side, what the header's record names - predicates per wavefront
+// by ballot and population count, integer wave reductions, the four wavefronts through LDS, at most one 64-bit integer atomic per block and slot.
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include <stdint.h>
@@ -32,6 +35,7 @@
 #include "../../include/trifinger_ppo_value.h"       // declares the value-side entry points (and trifinger_ppo.h): a definition that drifts fails here
 #include "../../include/trifinger_ppo_episode.h"     // ... and the episode-end entry points
 #include "../../include/trifinger_ppo_symmetry.h"    // ... and the objective with a KL row count
+#include "../../include/trifinger_ppo_diag.h"        // ... and the objective and the optimiser with the diagnostics record
 
 #define MAX_A 18
 
@@ -41,19 +45,43 @@ __device__ __forceinline__ float wave_sum(float x) {
     return x;
 }
 
+// integer wave reductions of the diagnostics record (DIAG instantiations only)
+__device__ __forceinline__ long long wave_sum_ll(long long x) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+    return x;
+}
+__device__ __forceinline__ int wave_sum_i(int x) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+    return x;
+}
+__device__ __forceinline__ unsigned wave_max_u(unsigned x) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { const unsigned y = (unsigned)__shfl_xor((int)x, off, 64); x = y > x ? y : x; }
+    return x;
+}
+__device__ __forceinline__ unsigned wave_min_u(unsigned x) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { const unsigned y = (unsigned)__shfl_xor((int)x, off, 64); x = y < x ? y : x; }
+    return x;
+}
+#define DIAG_OBJ_SLOTS 9                 // slots 0-8 of the record belong to the objective
+#define DIAG_INF_BITS 0x7F800000u        // TFP_DIAG_RATIO_MIN_CLEAR
+
 // d_logstd and the loss are sums over the blocks.  They are accumulated in accumulators of the library that are ZERO between launches and handed to the
 // caller's buffers by the block that finishes last (a ticket), which also clears them again: the caller's outputs need no launch that zeroes them first.
 // One objective at a time per device (the trainer's single stream); results as before up to the order of the atomic sums.
 __device__ float g_loss_acc[24];
 __device__ unsigned g_loss_ticket;
-template <int A, bool VCLIP, bool WGT, bool KLR = false>
+template <int A, bool VCLIP, bool WGT, bool KLR = false, bool DIAG = false>
 __global__ void __launch_bounds__(256) k_ppo_loss(const float* __restrict__ mu, const float* __restrict__ log_std, const float* __restrict__ act,
                                                   const float* __restrict__ old_nlp, const float* __restrict__ adv,
                                                   const float* __restrict__ old_mu, const float* __restrict__ v,
                                                   const float* __restrict__ ret, int B, float e_clip, float v_coef, float ent_coef,
                                                   float bounds_coef, float* __restrict__ d_mu, float* __restrict__ d_v,
                                                   float* __restrict__ d_logstd, float* __restrict__ loss_out, float* __restrict__ stats,
-                                                  const float* __restrict__ old_v, int kl_rows) {
+                                                  const float* __restrict__ old_v, int kl_rows, long long* __restrict__ diag) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const bool valid = i < B;
     const float invB = 1.0f / (float)B;
@@ -64,6 +92,11 @@ __global__ void __launch_bounds__(256) k_ppo_loss(const float* __restrict__ mu, 
     float dls[A];
 #pragma unroll
     for (int a = 0; a < A; ++a) dls[a] = 0.0f;
+    // DIAG: what this row adds to the record (include/trifinger_ppo_diag.h); a row that is not live adds nothing
+    [[maybe_unused]] bool dg_row = false, dg_clip = false, dg_zero = false, dg_vclip = false, dg_nonf = false;
+    [[maybe_unused]] int dg_mu = 0;
+    [[maybe_unused]] long long dg_k3 = 0;
+    [[maybe_unused]] unsigned dg_hi = 0u, dg_lo = DIAG_INF_BITS;
     if (valid) {
         float m[A], z[A], nlp = 0.0f;
 #pragma unroll
@@ -88,6 +121,7 @@ __global__ void __launch_bounds__(256) k_ppo_loss(const float* __restrict__ mu, 
         const float g_nlp = g_ratio * (-ratio) * invB;            // d loss / d nlp_i
         const float dv_ = v[i] - ret[i];
         c_term = dv_ * dv_;
+        [[maybe_unused]] bool v_clipped = false;
         if constexpr (VCLIP) {
             // the unclipped branch inside the range (both agree there) or when it is the larger one - the selection of the surrogate above
             const float vo = old_v[i], dlt = v[i] - vo;
@@ -96,6 +130,7 @@ __global__ void __launch_bounds__(256) k_ppo_loss(const float* __restrict__ mu, 
             const float g_v = unclipped ? v_coef * 2.0f * dv_ * invB : 0.0f;
             if constexpr (WGT) d_v[i] = g_v * wi; else d_v[i] = g_v;
             c_term = unclipped ? c_term : lc;
+            if constexpr (DIAG) v_clipped = !unclipped;
         } else {
             const float g_v = v_coef * 2.0f * dv_ * invB;
             if constexpr (WGT) d_v[i] = g_v * wi; else d_v[i] = g_v;
@@ -112,6 +147,25 @@ __global__ void __launch_bounds__(256) k_ppo_loss(const float* __restrict__ mu, 
         }
         if constexpr (WGT) { a_term *= wi; c_term *= wi; b_term *= wi; kl_term *= wi; }
         if constexpr (KLR) { if (i >= kl_rows) kl_term = 0.0f; }
+        if constexpr (DIAG) {
+            // the kernel's own locals, read and not formed again: ratio, inside, s1 > s2, unclipped, m[a]
+            const float l = old_nlp[i] - nlp;
+            bool live = true;
+            if constexpr (WGT) live = wi != 0.0f;
+            if constexpr (KLR) live = live && i < kl_rows;
+            const bool fin = isfinite(l) && isfinite(ratio);
+            dg_nonf = live && !fin;
+            dg_row = live && fin;
+            if (dg_row) {
+                dg_clip = ratio < 1.0f - e_clip || ratio > 1.0f + e_clip;
+                dg_zero = !(inside || s1 > s2);
+                dg_vclip = v_clipped;
+#pragma unroll
+                for (int a = 0; a < A; ++a) dg_mu += (m[a] > 1.1f || m[a] < -1.1f) ? 1 : 0;
+                dg_k3 = llrintf(fminf(expm1f(l) - l, TFP_DIAG_K3_MAX) * TFP_DIAG_K3_SCALE);
+                dg_hi = dg_lo = __float_as_uint(ratio);
+            }
+        }
     }
     // reductions: wave shuffles, then the four waves of the block through LDS, ONE atomic per block and quantity (atomics on
     // the same address serialise at ~100 ns each: 128 waves on 14 addresses cost 13 us, 32 blocks cost 3)
@@ -127,7 +181,37 @@ __global__ void __launch_bounds__(256) k_ppo_loss(const float* __restrict__ mu, 
     const float sa = wave_sum(a_term) * invB, sc = wave_sum(c_term) * invB, sb = wave_sum(b_term) * invB;
     const float sk = wave_sum(kl_term) * (KLR ? 1.0f / (float)kl_rows : invB);
     if (lane == 0) { red[wave][A] = sa; red[wave][A + 1] = sc; red[wave][A + 2] = sb; red[wave][A + 3] = sk; }
+    __shared__ long long dred[DIAG ? 4 : 1][DIAG_OBJ_SLOTS];               // referenced by the DIAG instantiations alone
+    if constexpr (DIAG) {
+        const long long c_row = __popcll(__ballot(dg_row)), c_clip = __popcll(__ballot(dg_clip)), c_zero = __popcll(__ballot(dg_zero));
+        const long long c_vclip = __popcll(__ballot(dg_vclip)), c_nonf = __popcll(__ballot(dg_nonf));
+        const long long c_mu = wave_sum_i(dg_mu), c_k3 = wave_sum_ll(dg_k3);
+        const unsigned r_hi = wave_max_u(dg_hi), r_lo = wave_min_u(dg_lo);
+        if (lane == 0) {
+            long long* w = dred[wave];
+            w[TFP_DIAG_ROWS] = c_row; w[TFP_DIAG_CLIPPED] = c_clip; w[TFP_DIAG_ZERO_GRAD] = c_zero; w[TFP_DIAG_VCLIPPED] = c_vclip; w[TFP_DIAG_MU_OUT] = c_mu;
+            w[TFP_DIAG_NONFINITE] = c_nonf; w[TFP_DIAG_K3_SUM] = c_k3; w[TFP_DIAG_RATIO_MAX] = r_hi; w[TFP_DIAG_RATIO_MIN] = r_lo;
+        }
+    }
     __syncthreads();
+    if constexpr (DIAG) {
+        // the block's share of the record: wave 1, one thread per slot (wave 0 issues the float atomics below), at most ONE atomic each, none for a zero
+        const int q = (int)threadIdx.x - 64;
+        if (q >= 0 && q < DIAG_OBJ_SLOTS) {
+            unsigned long long* dst = reinterpret_cast<unsigned long long*>(diag) + q;
+            const long long x0 = dred[0][q], x1 = dred[1][q], x2 = dred[2][q], x3 = dred[3][q];
+            if (q == TFP_DIAG_RATIO_MAX) {
+                const long long a = x0 > x1 ? x0 : x1, b = x2 > x3 ? x2 : x3, t = a > b ? a : b;
+                if (t != 0) atomicMax(dst, (unsigned long long)t);
+            } else if (q == TFP_DIAG_RATIO_MIN) {
+                const long long a = x0 < x1 ? x0 : x1, b = x2 < x3 ? x2 : x3, t = a < b ? a : b;
+                if (t != (long long)DIAG_INF_BITS) atomicMin(dst, (unsigned long long)t);
+            } else {
+                const long long t = (x0 + x1) + (x2 + x3);
+                if (t != 0) atomicAdd(dst, (unsigned long long)t);
+            }
+        }
+    }
     if (threadIdx.x < A + 4) {
         const int q = threadIdx.x;
         const float t = (red[0][q] + red[1][q]) + (red[2][q] + red[3][q]);
@@ -204,16 +288,32 @@ __global__ void __launch_bounds__(256) k_grad_sqnorms(const float* __restrict__ 
 }
 // torch.nn.utils.clip_grad_norm_: g *= min(1, max_norm / (||g|| + 1e-6)) per group; then torch.optim.Adam (no weight decay, no
 // amsgrad): m = b1 m + (1 - b1) g, v = b2 v + (1 - b2) g^2, p -= (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+// DIAG (include/trifinger_ppo_diag.h): block 0 thread q < 2 files its group's pre-truncation norm and whether the step truncated it into slots 10-15 of the
+// record, thread 0 the step into STEPS - one writer per slot, plain loads and stores; nothing of the update is formed differently
+template <bool DIAG = false>
 __global__ void __launch_bounds__(256) k_clip_adam(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, int n0, int n1, float* __restrict__ sq,
                                                    float* __restrict__ step, const float* __restrict__ lr, float max0, float max1,
-                                                   float b1, float b2, float eps) {
+                                                   float b1, float b2, float eps, long long* __restrict__ diag) {
     const float t = step[0];                                    // this step (written by k_grad_sqnorms, stable during this launch)
     const int par = (int)t & 1;
     const float bc1 = 1.0f - powf(b1, t), bc2s = sqrtf(1.0f - powf(b2, t));
     const float c0 = fminf(max0 / (sqrtf(sq[2 * par]) + 1e-6f), 1.0f), c1 = fminf(max1 / (sqrtf(sq[2 * par + 1]) + 1e-6f), 1.0f);
     if (blockIdx.x == 0 && threadIdx.x < 2) sq[2 * (1 - par) + threadIdx.x] = 0.0f;      // the other half: the next step sums into it (nobody touches it now)
     if (blockIdx.x == 0 && threadIdx.x == 0) step[1] = t;
+    if constexpr (DIAG) {
+        if (blockIdx.x == 0 && threadIdx.x < 2) {
+            const int q = threadIdx.x;
+            if (q == 0) diag[TFP_DIAG_STEPS] += 1;
+            if (q == 0 || n0 < n1) {                                  // one group without a central value network: slots 11, 13 and 15 stay 0
+                const float nb = fminf(sqrtf(sq[2 * par + q]), TFP_DIAG_GN_MAX);
+                diag[TFP_DIAG_TRUNC_A + q] += ((q ? c1 : c0) < 1.0f) ? 1 : 0;
+                diag[TFP_DIAG_GN_A_SUM + q] += llrintf(nb * TFP_DIAG_GN_SCALE);
+                const long long bits = (long long)__float_as_uint(nb);
+                if (bits > diag[TFP_DIAG_GN_A_MAX + q]) diag[TFP_DIAG_GN_A_MAX + q] = bits;
+            }
+        }
+    }
     const float s0 = lr[0] / bc1, s1 = lr[1] / bc1;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n1; i += gridDim.x * blockDim.x) {
         const bool g0 = i < n0;
@@ -238,18 +338,20 @@ int tfp_api_version(void) { return 3; }
 static int launch_ppo_loss(bool ok, const float* mu, const float* log_std, const float* act, const float* old_nlp, const float* adv, const float* old_mu,
                            const float* v, const float* ret, const float* old_v, bool weighted, int32_t B, int32_t A, float e_clip, float v_coef,
                            float ent_coef, float bounds_coef, float* d_mu, float* d_v, float* d_logstd, float* loss_out, float* stats, void* stream,
-                           int32_t kl_rows = 0) {
+                           int32_t kl_rows = 0, long long* diag = nullptr) {
     if (!ok || B <= 0 || (A != 9 && A != 18) || kl_rows < 0 || kl_rows > B) return -1;
     hipStream_t s = (hipStream_t)stream;
     dim3 grid((B + 255) / 256), block(256);
-#define LOSS(A_, V_, W_, K_) hipLaunchKernelGGL((k_ppo_loss<A_, V_, W_, K_>), grid, block, 0, s, mu, log_std, act, old_nlp, adv, old_mu, v, ret, B, e_clip, v_coef, \
-                                                ent_coef, bounds_coef, d_mu, d_v, d_logstd, loss_out, stats, old_v, kl_rows)
-#define LOSS_K(V_, W_, K_) do { if (A == 9) LOSS(9, V_, W_, K_); else LOSS(18, V_, W_, K_); } while (0)
+#define LOSS(A_, V_, W_, K_, D_) hipLaunchKernelGGL((k_ppo_loss<A_, V_, W_, K_, D_>), grid, block, 0, s, mu, log_std, act, old_nlp, adv, old_mu, v, ret, B, e_clip, \
+                                                    v_coef, ent_coef, bounds_coef, d_mu, d_v, d_logstd, loss_out, stats, old_v, kl_rows, diag)
+#define LOSS_D(A_, V_, W_, K_) do { if (diag) LOSS(A_, V_, W_, K_, true); else LOSS(A_, V_, W_, K_, false); } while (0)
+#define LOSS_K(V_, W_, K_) do { if (A == 9) LOSS_D(9, V_, W_, K_); else LOSS_D(18, V_, W_, K_); } while (0)
 #define LOSS_A(V_, W_) do { if (kl_rows > 0) LOSS_K(V_, W_, true); else LOSS_K(V_, W_, false); } while (0)
     if (!weighted) { if (!old_v) LOSS_A(false, false); else LOSS_A(true, false); }
     else { if (!old_v) LOSS_A(false, true); else LOSS_A(true, true); }
 #undef LOSS_A
 #undef LOSS_K
+#undef LOSS_D
 #undef LOSS
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
@@ -295,6 +397,16 @@ int tfp_ppo_loss_sym(const float* mu, const float* log_std, const float* act, co
                            d_logstd, loss_out, stats, stream, kl_rows);
 }
 
+// include/trifinger_ppo_diag.h: tfp_ppo_loss_sym's cases and kl_rows == 0 (every row: no KLR instantiation, the KL divisor is B) with the diagnostics
+// record - the compile-time variant DIAG of the same kernel: its accumulators, its ticket, its one-call-at-a-time contract
+int tfp_ppo_loss_diag(const float* mu, const float* log_std, const float* act, const float* old_nlp, const float* adv, const float* old_mu,
+                      const float* v, const float* ret, const float* old_v, int32_t weighted, int32_t kl_rows, int32_t B, int32_t A, float e_clip, float v_coef,
+                      float ent_coef, float bounds_coef, float* d_mu, float* d_v, float* d_logstd, float* loss_out, float* stats, void* stream, long long* diag) {
+    const bool ok = diag && ((uintptr_t)diag & 7) == 0 && (!weighted || (adv && ((uintptr_t)adv & 7) == 0));
+    return launch_ppo_loss(ok, mu, log_std, act, old_nlp, adv, old_mu, v, ret, old_v, weighted != 0, B, A, e_clip, v_coef, ent_coef, bounds_coef, d_mu, d_v,
+                           d_logstd, loss_out, stats, stream, kl_rows, diag);
+}
+
 // the zero state of tfp_ppo_loss's accumulators (after a launch that failed or was aborted; a completed launch leaves them clean itself)
 int tfp_reset_state(void* stream) {
     hipLaunchKernelGGL(k_reset_loss_state, dim3(1), dim3(64), 0, (hipStream_t)stream);
@@ -303,14 +415,27 @@ int tfp_reset_state(void* stream) {
 
 // One optimisation step over flat buffers: sq [4] is scratch (all zero before the first step; the launches keep the half of the next step zero), step [2]
 // = (this step, completed steps) and lr [2] live on the device (graph capture).
-int tfp_clip_adam(float* p, const float* g, float* m, float* v, int32_t n0, int32_t n1, float* sq, float* step, const float* lr,
-                  float max_norm0, float max_norm1, float beta1, float beta2, float eps, void* stream) {
+}  // extern "C"
+static int launch_clip_adam(float* p, const float* g, float* m, float* v, int32_t n0, int32_t n1, float* sq, float* step, const float* lr,
+                            float max_norm0, float max_norm1, float beta1, float beta2, float eps, void* stream, long long* diag) {
     if (n1 <= 0 || n0 < 0 || n0 > n1) return -1;
     hipStream_t s = (hipStream_t)stream;
     const int blocks = (n1 + 256 * 4 - 1) / (256 * 4);
     hipLaunchKernelGGL(k_grad_sqnorms, dim3(blocks), dim3(256), 0, s, g, n0, n1, sq, step);
-    hipLaunchKernelGGL(k_clip_adam, dim3(blocks), dim3(256), 0, s, p, g, m, v, n0, n1, sq, step, lr, max_norm0, max_norm1, beta1, beta2, eps);
+    if (diag) hipLaunchKernelGGL(k_clip_adam<true>, dim3(blocks), dim3(256), 0, s, p, g, m, v, n0, n1, sq, step, lr, max_norm0, max_norm1, beta1, beta2, eps, diag);
+    else hipLaunchKernelGGL(k_clip_adam<false>, dim3(blocks), dim3(256), 0, s, p, g, m, v, n0, n1, sq, step, lr, max_norm0, max_norm1, beta1, beta2, eps, diag);
     return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+extern "C" {
+int tfp_clip_adam(float* p, const float* g, float* m, float* v, int32_t n0, int32_t n1, float* sq, float* step, const float* lr,
+                  float max_norm0, float max_norm1, float beta1, float beta2, float eps, void* stream) {
+    return launch_clip_adam(p, g, m, v, n0, n1, sq, step, lr, max_norm0, max_norm1, beta1, beta2, eps, stream, nullptr);
+}
+// include/trifinger_ppo_diag.h: the same two launches, k_clip_adam as its DIAG variant
+int tfp_clip_adam_diag(float* p, const float* g, float* m, float* v, int32_t n0, int32_t n1, float* sq, float* step, const float* lr,
+                       float max_norm0, float max_norm1, float beta1, float beta2, float eps, void* stream, long long* diag) {
+    if (!diag || ((uintptr_t)diag & 7) != 0) return -1;
+    return launch_clip_adam(p, g, m, v, n0, n1, sq, step, lr, max_norm0, max_norm1, beta1, beta2, eps, stream, diag);
 }
 
 }  // extern "C"

@@ -101,6 +101,23 @@ A in {9, 18}; an engine with `dr_enable` and a non-zero `dr_base_pos` or `dr_sta
 trifinger_ppo_symmetry.h - the augmenting gather writes the three images in the ONE gather launch (`ppo_kernels.gather_rows_sym`), the objective takes
 the KL row count (`tfp_ppo_loss_sym`); the step keeps its launch count on three times the rows.  With the key off no table is built and every launch, buffer
 and statistic is what it was.
+Training diagnostics (`params.config.diagnostics`, the project's own key; off by default, and off every launch, buffer, statistic and log line is what it
+was).  THE RECORD is int64 [16] on the device (include/trifinger_ppo_diag.h; `D_*` below): integers and fixed-point sums, so its bits do not depend on the
+order of the workgroups or of the ranks.  Every minibatch step adds to it: the objective slots 0-8 over its LIVE rows (w_i != 0 with `episode_ends`, the
+original B rows with `symmetry_augmentation`; a row with a non-finite log-ratio or ratio counts in NONFINITE alone) - ROWS, CLIPPED (ratio outside 1 +- e_clip),
+ZERO_GRAD (the surrogate's zero-gradient branch), VCLIPPED (the value term's clipped branch), MU_OUT (entries of mu beyond +-1.1), K3_SUM
+(round(min(expm1(l) - l, 64) * 2^28), l = old_nlp - nlp), RATIO_MAX / RATIO_MIN (bit patterns) -, the optimiser slots 9-15 - STEPS, and per group TRUNC (its
+coefficient max_norm / (norm + 1e-6) is < 1), GN_SUM (round(min(norm, 2^16) * 2^24)), GN_MAX, norm the pre-truncation gradient norm.  `diag_objective_statement`
+and `diag_optimiser_statement` ARE the specification: float32 torch with the kernel's predicates in the kernel's order, what the torch path runs; on the GPU
+the same two launches run as their DIAG instantiations (`tfp_ppo_loss_diag`, `tfp_clip_adam_diag`) - no quantity of the loss, of a gradient or of the update
+is formed differently, no launch and no host sync is added to the minibatch loop.  `update()` takes and clears the record once per epoch - with a process
+group slots 0-6 through ONE SUM all-reduce and (RATIO_MAX, -RATIO_MIN) through ONE MAX all-reduce, both counted in `n_diag_allreduce`; the norms are those of
+the exchanged gradient, the same on every rank - and reports, a key whose divisor is 0 being absent: `clip_frac`, `zero_grad_frac`, `value_clip_frac` (with a
+clipped value term), `mu_out_frac` = MU_OUT / (ROWS A), `approx_kl` = K3_SUM / 2^28 / ROWS, `ratio_max`, `ratio_min`, `nonfinite_rows`, `grad_norm` (the mean
+over the steps), `grad_norm_max`, `grad_trunc_frac` and the same three with suffix `_value` for a central value network; and once per epoch in torch,
+rank-local like `symmetry_gap`: `explained_variance` = 1 - Var(ret - val) / Var(ret) over the rollout's samples with w = 1 in reward units (ret - val is the
+advantage estimate as GAE filed it; population variances; absent when Var(ret) = 0), `entropy` = sum_a (log sigma_a + 0.5 + 0.5 log 2 pi), `sigma_mean`.
+`last_diag` keeps the epoch's record.  Checkpoints do not carry it.
 
 This is host-side training glue, NOT part of the measured hot path.  On a GPU the minibatch step runs on the hand-written kernels of
 csrc/ppo_kernels.hip (leibnizgym_amd/ppo_kernels.py): one gather launch, the Linear / ELU layers on fp32 MFMA, the objective with all
@@ -169,6 +186,7 @@ class PPOConfig:
     games_to_track: int = 100         # params.config.games_to_track (RL-Games' key): the episodes the reported window holds at least, once that many have ended
     score_to_win: float = float("inf")    # params.config.score_to_win (RL-Games' key): train() stops when episode_return exceeds it; needs track_episodes
     symmetry_augmentation: bool = False   # params.config.symmetry_augmentation: every minibatch with its two images under the robot's 120-degree turn (module docstring)
+    diagnostics: bool = False         # params.config.diagnostics: clip fraction, approx_kl, gradient norms, explained variance in the statistics (module docstring)
 
     def __post_init__(self):
         if self.value_bootstrap and not self.episode_ends:
@@ -208,7 +226,8 @@ class PPOConfig:
                   lr_schedule=lr_schedule_name(c.get("lr_schedule", "adaptive")),
                   episode_ends=bool(c.get("episode_ends", False)), value_bootstrap=bool(c.get("value_bootstrap", False)),
                   track_episodes=bool(c.get("track_episodes", False)), games_to_track=int(c.get("games_to_track", 100)),
-                  score_to_win=float(c.get("score_to_win", float("inf"))), symmetry_augmentation=bool(c.get("symmetry_augmentation", False)))
+                  score_to_win=float(c.get("score_to_win", float("inf"))), symmetry_augmentation=bool(c.get("symmetry_augmentation", False)),
+                  diagnostics=bool(c.get("diagnostics", False)))
         # without a central value network the critic takes the actor's keys
         kw.update(value_activation=kw["activation"], value_d2rl=kw["d2rl"], value_truncate_grads=kw["truncate_grads"])
         if cv:
@@ -499,6 +518,119 @@ def masked_advantage_norm(adv, w):
     return w * (adv - mean) / (std + 1e-8)
 
 
+# ---- training diagnostics (`params.config.diagnostics`; include/trifinger_ppo_diag.h has the record, the module docstring the keys) ----------------------
+DIAG_N = 16
+(D_ROWS, D_CLIPPED, D_ZERO_GRAD, D_VCLIPPED, D_MU_OUT, D_NONFINITE, D_K3_SUM, D_RATIO_MAX, D_RATIO_MIN, D_STEPS, D_TRUNC_A, D_TRUNC_V, D_GN_A_SUM, D_GN_V_SUM,
+ D_GN_A_MAX, D_GN_V_MAX) = range(DIAG_N)
+DIAG_RATIO_MIN_CLEAR = 0x7F800000                # the bit pattern of +inf: the cleared state of RATIO_MIN
+DIAG_K3_SCALE, DIAG_K3_MAX, DIAG_GN_SCALE, DIAG_GN_MAX = 2.0 ** 28, 64.0, 2.0 ** 24, 2.0 ** 16
+
+
+def new_diag_record(device):
+    """a cleared record: int64 [DIAG_N], every slot 0 but RATIO_MIN"""
+    rec = torch.zeros(DIAG_N, dtype=torch.int64, device=device)
+    rec[D_RATIO_MIN] = DIAG_RATIO_MIN_CLEAR
+    return rec
+
+
+def _float_bits(x):
+    """the bit pattern of a float32 tensor as int64 (of a non-negative float: an integer that orders as the float does)"""
+    return x.float().contiguous().view(torch.int32).to(torch.int64)
+
+
+def diag_objective_statement(l, ratio, adv, mu, e_clip, v=None, ret=None, old_v=None, w=None, kl_rows=None):
+    """slots 0-8 of the record for ONE launch of the objective - the SPECIFICATION of what tfp_ppo_loss_diag adds, with the kernel's predicates in the
+    kernel's order, on the tensors `_mb_backward` has: l = old_nlp - nlp [B], ratio = exp(l) [B], adv [B], mu [B, A], and with a clipped value term v, ret,
+    old_v [B]; w [B] with `episode_ends`, kl_rows with `symmetry_augmentation`.  float32 in, int64 [DIAG_N] out (slots 9-15 zero, RATIO_MIN in its
+    cleared state when no row is live); sums and masks only - no boolean indexing, no host sync.
+    A row is LIVE when w_i != 0 (where w is given) and i < kl_rows (where given); a live row with a non-finite l or ratio counts in NONFINITE alone."""
+    e = torch.as_tensor(e_clip, dtype=ratio.dtype, device=ratio.device)
+    one = torch.ones((), dtype=ratio.dtype, device=ratio.device)
+    lo, hi = one - e, one + e
+    live = torch.ones_like(ratio, dtype=torch.bool)
+    if w is not None:
+        live = live & (w != 0)
+    if kl_rows is not None:
+        live = live & (torch.arange(ratio.numel(), device=ratio.device) < int(kl_rows))
+    fin = torch.isfinite(l) & torch.isfinite(ratio)
+    row, nonf = live & fin, live & ~fin
+    s1, s2 = -adv * ratio, -adv * torch.minimum(torch.maximum(ratio, lo), hi)
+    inside = (ratio >= lo) & (ratio <= hi)
+    clipped = (ratio < lo) | (ratio > hi)
+    zero = ~(inside | (s1 > s2))
+    if old_v is not None:
+        dlt = v - old_v
+        lu, lc = (v - ret) ** 2, ((old_v + torch.minimum(torch.maximum(dlt, -e), e)) - ret) ** 2
+        vclipped = ~(((dlt >= -e) & (dlt <= e)) | (lu >= lc))
+    else:
+        vclipped = torch.zeros_like(row)
+    mu_out = ((mu > 1.1) | (mu < -1.1)).sum(-1)
+    k3 = torch.round(torch.clamp(torch.expm1(l) - l, max=DIAG_K3_MAX) * DIAG_K3_SCALE)
+    k3 = torch.where(row, k3, torch.zeros_like(k3)).to(torch.int64)          # a non-finite value never reaches the integer conversion
+    bits = _float_bits(torch.where(row, ratio, torch.zeros_like(ratio)))
+    cnt = lambda p: (p & row).sum()                                           # noqa: E731
+    zero64 = torch.zeros((), dtype=torch.int64, device=ratio.device)
+    return torch.stack([row.sum(), cnt(clipped), cnt(zero), cnt(vclipped), torch.where(row, mu_out, torch.zeros_like(mu_out)).sum(), nonf.sum(), k3.sum(),
+                        bits.max(), torch.where(row, bits, torch.full_like(bits, DIAG_RATIO_MIN_CLEAR)).min()] + [zero64] * (DIAG_N - 9)).to(torch.int64)
+
+
+def total_grad_norm(params):
+    """the 2-norm of the gradients of `params` as torch.nn.utils.clip_grad_norm_ forms and returns it (for an optimiser that does not truncate)"""
+    return torch.linalg.vector_norm(torch.stack([torch.linalg.vector_norm(p.grad) for p in params if p.grad is not None]))
+
+
+def diag_optimiser_statement(norms, max_norms):
+    """slots 9-15 of the record for ONE optimiser step - the SPECIFICATION of what tfp_clip_adam_diag adds.  `norms`: the pre-truncation gradient norm per
+    optimiser group (one or two float32 scalars: what clip_grad_norm_ returns), `max_norms`: the group's max_norm, inf where it does not truncate.  A group is
+    TRUNCATED when its coefficient max_norm / (norm + 1e-6) is < 1; the norm enters the sum as round(fmin(norm, 2^16) * 2^24) and the maximum by its bit
+    pattern.  int64 [DIAG_N], slots 0-8 zero (RATIO_MIN too: `diag_merge` takes the minimum of slot 8 from objective statements alone)."""
+    out = torch.zeros(DIAG_N, dtype=torch.int64, device=norms[0].device)
+    out[D_STEPS] = 1
+    for q, (nrm, mx) in enumerate(zip(norms, max_norms)):
+        nrm = nrm.detach().float()
+        coef = torch.as_tensor(float(mx), dtype=torch.float32, device=nrm.device) / (nrm + 1e-6)
+        nb = torch.fmin(nrm, torch.as_tensor(DIAG_GN_MAX, dtype=torch.float32, device=nrm.device))
+        out[D_TRUNC_A + q] = (coef < 1.0).to(torch.int64)
+        out[D_GN_A_SUM + q] = torch.round(nb * DIAG_GN_SCALE).to(torch.int64)
+        out[D_GN_A_MAX + q] = _float_bits(nb)
+    return out
+
+
+def diag_merge(rec, add, objective):
+    """accumulate one statement into the record, in place, as the kernels do: sums add, maxima take the larger, RATIO_MIN the smaller"""
+    if objective:
+        rec[:D_RATIO_MAX] += add[:D_RATIO_MAX]
+        rec[D_RATIO_MAX] = torch.maximum(rec[D_RATIO_MAX], add[D_RATIO_MAX])
+        rec[D_RATIO_MIN] = torch.minimum(rec[D_RATIO_MIN], add[D_RATIO_MIN])
+    else:
+        rec[D_STEPS:D_GN_A_MAX] += add[D_STEPS:D_GN_A_MAX]
+        rec[D_GN_A_MAX:] = torch.maximum(rec[D_GN_A_MAX:], add[D_GN_A_MAX:])
+
+
+def _bits_float(b):
+    import struct
+    return struct.unpack("<f", struct.pack("<I", int(b) & 0xFFFFFFFF))[0]
+
+
+def diagnostic_stats(vec, act_dim, value_clip, central):
+    """the record of an epoch (a list of DIAG_N integers) as the statistics `update()` reports; a key whose divisor is 0 is absent (no NaN goes into a log)"""
+    out = {"nonfinite_rows": int(vec[D_NONFINITE])}
+    rows, steps = int(vec[D_ROWS]), int(vec[D_STEPS])
+    if rows > 0:
+        out["clip_frac"], out["zero_grad_frac"] = vec[D_CLIPPED] / rows, vec[D_ZERO_GRAD] / rows
+        if value_clip:
+            out["value_clip_frac"] = vec[D_VCLIPPED] / rows
+        out["mu_out_frac"] = vec[D_MU_OUT] / (rows * int(act_dim))
+        out["approx_kl"] = vec[D_K3_SUM] / DIAG_K3_SCALE / rows
+        out["ratio_max"], out["ratio_min"] = _bits_float(vec[D_RATIO_MAX]), _bits_float(vec[D_RATIO_MIN])
+    if steps > 0:
+        for q, sfx in enumerate(("", "_value") if central else ("",)):
+            out["grad_norm" + sfx] = vec[D_GN_A_SUM + q] / DIAG_GN_SCALE / steps
+            out["grad_norm_max" + sfx] = _bits_float(vec[D_GN_A_MAX + q])
+            out["grad_trunc_frac" + sfx] = vec[D_TRUNC_A + q] / steps
+    return out
+
+
 class ActorCritic(nn.Module):
     obs_norm = None            # InputNorm of `obs` / of `states` (plain attributes, not modules: the model's state_dict keeps its keys); set by the trainer
     state_norm = None
@@ -688,6 +820,11 @@ class PPOTrainer:
         # `symmetry_augmentation`: the tables of the map, built ONCE for this env's widths (the refusals: module docstring).  Off: none of it exists
         self.sym = self._symmetry_tables(obs_dim, state_dim, act_dim, fk) if c.symmetry_augmentation else None
         self._sym_mu = None                                  # the last minibatch's mu [3B, A] (a reference, no launch): `symmetry_gap` is formed from it once per epoch
+        # `diagnostics`: the record (int64 [DIAG_N] on the device), which the objective and the optimiser of every minibatch step add to and `update()` takes
+        # and clears once per epoch.  Off: none of it exists
+        self.diag = new_diag_record(self.device) if c.diagnostics else None
+        self.n_diag_allreduce = 0
+        self.last_diag = None                                # the last epoch's record as `update()` read it (a list of DIAG_N integers; reduced over the ranks)
         self.frames = 0
         self.epoch = 0
         self.last_info = {}
@@ -1140,6 +1277,10 @@ class PPOTrainer:
                 kl = wmean(kl_i)
             acc["kl"] += kl
             acc["loss"] += loss.detach(); acc["a_loss"] += a_loss.detach(); acc["c_loss"] += c_loss.detach()
+            if self.diag is not None:              # the torch statement of what tfp_ppo_loss_diag counts
+                vk = dict(v=v, ret=d["ret"][idx], old_v=d["old_v"][idx]) if self.clip_v else {}
+                diag_merge(self.diag, diag_objective_statement(d["old_nlp"][idx] - nlp, ratio, a, mu, c.e_clip, w=w, kl_rows=B if self.sym is not None else None,
+                                                               **vk), objective=True)
 
     def _sym_minibatch(self, d, idx):
         """the 3B minibatch of `symmetry_augmentation` in plain torch: rows [k B, (k + 1) B) = G^k of obs / states, P^k of act and old_mu, the rest repeated"""
@@ -1191,6 +1332,8 @@ class PPOTrainer:
             if self.ends:                                  # the gathered array is (adv_i, w_i): the weighted instantiation of the objective
                 kw["adv_w"] = g.pop("adv")
             kw.update(kl_rows)
+            if self.diag is not None:                      # the DIAG instantiation of the same launch adds to the record
+                kw["diag"] = self.diag
             if self.sym is not None:
                 self._sym_mu = mu
             _, d_mu, d_v, _ = pk.ppo_loss_and_grads(mu, self.net.log_std, v, g["act"], g["old_nlp"], g.get("adv"), g["ret"], g["old_mu"], acc["_fused"], c.e_clip,
@@ -1210,15 +1353,18 @@ class PPOTrainer:
 
     def _mb_apply(self, gathered=False):
         if self.flat_opt is not None:
-            self.flat_opt.step(gathered)
+            self.flat_opt.step(gathered, **({"diag": self.diag} if self.diag is not None else {}))
             return
-        if self.net.central:                   # truncate_grads of each optimiser on its own network
-            if self.trunc[0]:
-                nn.utils.clip_grad_norm_(self.net.actor_parameters(), self.cfg.grad_norm, foreach=True)
-            if self.trunc[1]:
-                nn.utils.clip_grad_norm_(self.net.critic_parameters(), self.cfg.value_grad_norm, foreach=True)
-        elif self.trunc[0]:
-            nn.utils.clip_grad_norm_(self.net.parameters(), self.cfg.grad_norm, foreach=True)
+        # (parameters, max_norm, truncates) per optimiser: truncate_grads of each on its own network
+        if self.net.central:
+            groups = [(self.net.actor_parameters(), self.cfg.grad_norm, self.trunc[0]), (self.net.critic_parameters(), self.cfg.value_grad_norm, self.trunc[1])]
+        else:
+            groups = [(list(self.net.parameters()), self.cfg.grad_norm, self.trunc[0])]
+        norms = [nn.utils.clip_grad_norm_(ps, mx, foreach=True) if on else None for ps, mx, on in groups]
+        if self.diag is not None:              # the torch statement of what tfp_clip_adam_diag files: the pre-truncation norms, clip_grad_norm_'s return value
+            with torch.no_grad():
+                norms = [nrm if nrm is not None else total_grad_norm(ps) for nrm, (ps, _, _) in zip(norms, groups)]
+                diag_merge(self.diag, diag_optimiser_statement(norms, [mx if on else float("inf") for _, mx, on in groups]), objective=False)
         self.opt.step()
 
     def _flatten_grads(self, out=None):
@@ -1263,6 +1409,12 @@ class PPOTrainer:
                 self.tracker.merge(self.group)
                 self.n_track_allreduce += 1
             track_vec = self.tracker.take()
+        if self.diag is not None:                  # once per epoch in torch, rank-local like symmetry_gap: the rollout's samples with w = 1, in reward units.
+            # ret = adv + val (GAE), so ret - val is the advantage estimate as filed: [Var(ret - val), Var(ret)] (population), read below
+            wv = w if self.ends else torch.ones_like(adv)
+            err, rets, sw = flat(buf["adv"]), flat(buf["ret"]), wv.sum()
+            pvar = lambda x: (wv * (x - (wv * x).sum() / sw) ** 2).sum() / sw  # noqa: E731
+            ev_pair = torch.stack([pvar(err), pvar(rets)])
         total = T * n
         mb = max(1, total // c.minibatches)
         dev = src["obs"].device
@@ -1313,7 +1465,32 @@ class PPOTrainer:
             stats.update(self._track_stats(track_vec.tolist()))
         if self.sym is not None and self._sym_mu is not None:
             stats["symmetry_gap"] = float(self._symmetry_gap())
+        if self.diag is not None:
+            stats.update(self._diag_stats(ev_pair))
         return stats
+
+    @torch.no_grad()
+    def _diag_stats(self, ev_pair):
+        """`diagnostics`: take the epoch's record and clear it; with a process group slots 0-6 through ONE SUM all-reduce and (RATIO_MAX, -RATIO_MIN) through
+        ONE MAX all-reduce (`n_diag_allreduce` counts both; the gradient norms are those of the exchanged gradient, the same on every rank, and stay), then
+        the keys of the module docstring - the record's, and explained_variance / entropy / sigma_mean of this rank in torch"""
+        vec = self.diag.clone()
+        self.diag.copy_(new_diag_record(self.device))
+        if self.dist_on:
+            sums = vec[:D_RATIO_MAX].clone()
+            ext = torch.stack([vec[D_RATIO_MAX], -vec[D_RATIO_MIN]])
+            self.dist.all_reduce(sums, op=self.dist.ReduceOp.SUM, group=self.group)
+            self.dist.all_reduce(ext, op=self.dist.ReduceOp.MAX, group=self.group)
+            self.n_diag_allreduce += 2
+            vec[:D_RATIO_MAX], vec[D_RATIO_MAX], vec[D_RATIO_MIN] = sums, ext[0], -ext[1]
+        ls = self.net.log_std.detach()
+        extra = torch.cat([ev_pair.double(), torch.stack([(ls + 0.5 + 0.5 * math.log(2 * math.pi)).sum(), ls.exp().mean()]).double()]).tolist()
+        self.last_diag = vec.tolist()
+        out = diagnostic_stats(self.last_diag, ls.numel(), self.clip_v, self.net.central)
+        if extra[1] > 0.0:                         # absent when the returns do not vary
+            out["explained_variance"] = 1.0 - extra[0] / extra[1]
+        out["entropy"], out["sigma_mean"] = extra[2], extra[3]
+        return out
 
     def _track_stats(self, vec):
         """file the epoch's vector (a list of integers, the same on every rank) and return the episode keys of the statistics: the window's means and rates

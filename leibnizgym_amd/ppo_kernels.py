@@ -51,6 +51,8 @@ _ARGTYPES = {
     "tfp_rollout_track": [_P, _P], "tfp_record_step": [_P, _P],
     # symmetry augmentation (include/trifinger_ppo_symmetry.h: csrc/ppo_symmetry.hip and the KL-row variant of the objective)
     "tfp_gather_rows_sym": [_P] * 7 + [_I, _P, _I, _P], "tfp_ppo_loss_sym": [_P] * 9 + [_I] * 4 + [_R] * 4 + [_P] * 6,
+    # training diagnostics (include/trifinger_ppo_diag.h: the DIAG variants of the objective and of the optimiser, the record behind their arguments)
+    "tfp_ppo_loss_diag": [_P] * 9 + [_I] * 4 + [_R] * 4 + [_P] * 7, "tfp_clip_adam_diag": [_P] * 4 + [_I, _I] + [_P] * 3 + [_R] * 5 + [_P, _P],
 }
 
 
@@ -95,15 +97,31 @@ class _FusedPPOLoss(torch.autograd.Function):
 _LOSS_ENTRY = {(False, False): "tfp_ppo_loss", (True, False): "tfp_ppo_loss_vclip", (False, True): "tfp_ppo_loss_w", (True, True): "tfp_ppo_loss_vclip_w"}
 
 
+DIAG_N, DIAG_RATIO_MIN, DIAG_RATIO_MIN_CLEAR = 16, 8, 0x7F800000        # include/trifinger_ppo_diag.h: the record, and the one slot whose cleared state is not 0
+
+
+def new_diag(device):
+    """a cleared diagnostics record: int64 [DIAG_N] on the device"""
+    rec = torch.zeros(DIAG_N, dtype=torch.int64, device=device)
+    rec[DIAG_RATIO_MIN] = DIAG_RATIO_MIN_CLEAR
+    return rec
+
+
+def _diag_ok(diag, like):
+    return diag.dtype == torch.int64 and diag.is_contiguous() and diag.numel() == DIAG_N and diag.device == like.device
+
+
 def ppo_loss_and_grads(mu, log_std, v, act, old_nlp, adv, ret, old_mu, stats, e_clip, v_coef, ent_coef, bounds_coef, d_ls_out=None, old_v=None, adv_w=None,
-                       kl_rows=None):
+                       kl_rows=None, diag=None):
     """(loss, d loss / d mu, d loss / d v, d loss / d log_std) straight from the kernel - for a caller that starts the backward pass at
     the network outputs itself (`torch.autograd.backward((mu, v), (d_mu, d_v))`), without a loss node multiplying them by one.
     `old_v` [B] (the value recorded in the rollout): the value term is clipped around it with the surrogate's `e_clip` (tfp_ppo_loss_vclip: `clip_value`).
     `adv_w` [B, 2] = (adv_i, w_i) interleaved (`episode_ends`; `adv` is then None): every per-sample term and gradient times w_i, the divisor stays B
     (tfp_ppo_loss_w / tfp_ppo_loss_vclip_w, include/trifinger_ppo_episode.h).
     `kl_rows` (`symmetry_augmentation`; 1 .. B): the KL statistic sums over the first kl_rows rows alone and is divided by kl_rows, everything else is
-    untouched (tfp_ppo_loss_sym, include/trifinger_ppo_symmetry.h: ONE entry point for the four cases above; with kl_rows == B their bits)"""
+    untouched (tfp_ppo_loss_sym, include/trifinger_ppo_symmetry.h: ONE entry point for the four cases above; with kl_rows == B their bits).
+    `diag` (`diagnostics`; int64 [DIAG_N] on the device, `new_diag`): the launch is tfp_ppo_loss_diag (include/trifinger_ppo_diag.h: ONE entry point for
+    all of the above) and adds what it saw to slots 0-8 of the record; every output is what it is without the record"""
     lib = load()
     mu, v = mu.contiguous(), v.contiguous()
     B, A = mu.shape
@@ -115,9 +133,17 @@ def ppo_loss_and_grads(mu, log_std, v, act, old_nlp, adv, ret, old_mu, stats, e_
     d_mu, d_v = torch.empty_like(mu), torch.empty_like(v)
     out = torch.empty(A + 1, device=mu.device, dtype=torch.float32)      # d_logstd [A] and the loss
     d_ls, loss = (out[:A] if d_ls_out is None else d_ls_out), out[A]      # d_ls_out: e.g. the parameter's slot of a flat gradient buffer
+    if kl_rows is not None and not 1 <= int(kl_rows) <= B:
+        raise ValueError(f"kl_rows = {kl_rows}: the KL statistic needs between 1 and B = {B} rows")
+    if diag is not None:
+        assert _diag_ok(diag, mu), "the diagnostics record is int64 [16], contiguous, on the device of the minibatch"
+        _chk(lib.tfp_ppo_loss_diag(mu.data_ptr(), log_std.data_ptr(), act.data_ptr(), old_nlp.data_ptr(), adv.data_ptr(), old_mu.data_ptr(), v.data_ptr(),
+                                   ret.data_ptr(), old_v.data_ptr() if old_v is not None else None, 1 if adv_w is not None else 0,
+                                   int(kl_rows) if kl_rows is not None else 0, B, A, float(e_clip), float(v_coef), float(ent_coef), float(bounds_coef),
+                                   d_mu.data_ptr(), d_v.data_ptr(), d_ls.data_ptr(), loss.data_ptr(), stats.data_ptr(), _stream(mu), diag.data_ptr()),
+             "tfp_ppo_loss_diag")
+        return loss, d_mu, d_v, d_ls
     if kl_rows is not None:
-        if not 1 <= int(kl_rows) <= B:
-            raise ValueError(f"kl_rows = {kl_rows}: the KL statistic needs between 1 and B = {B} rows")
         _chk(lib.tfp_ppo_loss_sym(mu.data_ptr(), log_std.data_ptr(), act.data_ptr(), old_nlp.data_ptr(), adv.data_ptr(), old_mu.data_ptr(), v.data_ptr(),
                                   ret.data_ptr(), old_v.data_ptr() if old_v is not None else None, 1 if adv_w is not None else 0, int(kl_rows), B, A,
                                   float(e_clip), float(v_coef), float(ent_coef), float(bounds_coef), d_mu.data_ptr(), d_v.data_ptr(), d_ls.data_ptr(),
@@ -197,9 +223,16 @@ class FlatClipAdam:
             torch._foreach_copy_(dst, src)
         return self.flat_g
 
-    def step(self, gathered=False):
+    def step(self, gathered=False, diag=None):
+        """`diag` (int64 [DIAG_N] on the device): tfp_clip_adam_diag - the same two launches, slots 9-15 of the record updated on the side"""
         if not gathered:
             self.gather_grads()
+        if diag is not None:
+            assert _diag_ok(diag, self.flat_p), "the diagnostics record is int64 [16], contiguous, on the optimiser's device"
+            _chk(load().tfp_clip_adam_diag(self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.n0, self.n1,
+                                           self.sq.data_ptr(), self.step_count.data_ptr(), self.lr.data_ptr(), self.max_norms[0], self.max_norms[1],
+                                           self.betas[0], self.betas[1], self.eps, _stream(self.flat_p), diag.data_ptr()), "tfp_clip_adam_diag")
+            return
         _chk(load().tfp_clip_adam(self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.n0, self.n1,
                                   self.sq.data_ptr(), self.step_count.data_ptr(), self.lr.data_ptr(), self.max_norms[0], self.max_norms[1],
                                   self.betas[0], self.betas[1], self.eps, _stream(self.flat_p)), "tfp_clip_adam")

@@ -232,6 +232,25 @@ def episode_line(st):
     return f"  episode return {st['episode_return']:.3f} length {st['episode_length']:.1f} success {st['success_rate']:.3f} ({st['episodes']} episodes)"
 
 
+# the keys `params.config.diagnostics` adds to an epoch's statistics (leibnizgym_amd/ppo.py: diagnostic_stats and PPOTrainer._diag_stats), in log order
+DIAGNOSTIC_KEYS = ("clip_frac", "zero_grad_frac", "value_clip_frac", "mu_out_frac", "approx_kl", "ratio_max", "ratio_min", "nonfinite_rows", "grad_norm",
+                   "grad_norm_max", "grad_trunc_frac", "grad_norm_value", "grad_norm_max_value", "grad_trunc_frac_value", "explained_variance", "entropy",
+                   "sigma_mean")
+
+
+def diagnostic_scalars(st):
+    """(tag, value, step) of the training diagnostics of an epoch (`diagnostics`): diagnostics/<key> over frames for every key the epoch reports - a key
+    whose divisor was 0 is absent from the statistics and from the log; nothing with the key off"""
+    return [(f"diagnostics/{k}", st[k], st["frames"]) for k in DIAGNOSTIC_KEYS if k in st]
+
+
+def diagnostic_line(st):
+    """what the printed line of an epoch gains with `diagnostics`: clip_frac, approx_kl, explained_variance and grad_norm, each where the epoch reports it"""
+    parts = [f"{name} {st[k]:{fmt}}" for name, k, fmt in (("clip", "clip_frac", ".3f"), ("approx_kl", "approx_kl", ".5f"), ("ev", "explained_variance", ".3f"),
+                                                         ("grad norm", "grad_norm", ".3f")) if k in st]
+    return ("  " + " ".join(parts)) if parts else ""
+
+
 # ---- the in-repo runner behind RL-Games' Runner interface ------------------------------------------------------------------
 class NativeRunner:
     """`load(rlg) / reset() / run(args)` like `rl_games.torch_runner.Runner`, driving leibnizgym_amd.ppo.PPOTrainer on the
@@ -290,14 +309,14 @@ class NativeRunner:
             total_time = time.perf_counter() - t0
             for k in ("loss", "a_loss", "c_loss", "kl", "lr", "mean_reward"):
                 self.writer.add_scalar(f"losses/{k}" if k.endswith("loss") else f"info/{k}", st[k], st["frames"])
-            for tag, value, step in episode_scalars(st, total_time):
+            for tag, value, step in episode_scalars(st, total_time) + diagnostic_scalars(st):
                 self.writer.add_scalar(tag, value, step)
             if self.observer is not None:
                 self.observer.process_infos([[], tr.last_info], [])
                 self.observer.after_print_stats(st["frames"], st["epoch"], total_time)
             if conf_print:
                 print(f"epoch {st['epoch']:5d} frames {st['frames']:11d} reward/step {st['mean_reward']:9.3f} kl {st['kl']:.4f} "
-                      f"lr {st['lr']:.2e}  {st['frames'] / total_time:.3e} frames/s{episode_line(st)}", flush=True)
+                      f"lr {st['lr']:.2e}  {st['frames'] / total_time:.3e} frames/s{episode_line(st)}{diagnostic_line(st)}", flush=True)
         conf_print = bool(self.params["params"]["config"].get("print_stats", True))
         stats = tr.train(cfg.max_epochs, log, checkpoint_dir=os.path.join(args.get("logdir") or ".", "nn"))
         self.writer.close()

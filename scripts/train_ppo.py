@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """End-to-end PPO on the native TriFinger env (BASELINE config 5: difficulty 4, 8192 envs per GPU).
 
-    python scripts/train_ppo.py gym=trifinger_difficulty_4 args.num_envs=8192 [epochs=20] [args.checkpoint=run/nn/trifinger.pth] [save_dir=run/nn] [--symmetry]
+    python scripts/train_ppo.py gym=trifinger_difficulty_4 args.num_envs=8192 [epochs=20] [args.checkpoint=run/nn/trifinger.pth] [save_dir=run/nn] [--symmetry] [--diagnostics]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 scripts/train_ppo.py ...
 
 One process per GPU; envs are sharded (no data-path collective), gradients are averaged with one fused RCCL
 all-reduce per minibatch.  Uses RL-Games' hyper-parameters of resources/config/rlg/asymm.yaml (leibnizgym_amd/ppo.py).
---symmetry: rlg.params.config.symmetry_augmentation=True - every minibatch with its two images under the robot's 120-degree turn (leibnizgym_amd/symmetry.py)."""
+--symmetry: rlg.params.config.symmetry_augmentation=True - every minibatch with its two images under the robot's 120-degree turn (leibnizgym_amd/symmetry.py).
+--diagnostics: rlg.params.config.diagnostics=True - clip fraction, approx_kl, explained variance and gradient norm on the epoch line (leibnizgym_amd/ppo.py)."""
 import os
 import sys
 import time
@@ -18,7 +19,7 @@ import torch  # noqa: E402
 from leibnizgym_amd.config import compose  # noqa: E402
 from leibnizgym_amd.envs import TrifingerEnv  # noqa: E402
 from leibnizgym_amd.ppo import PPOConfig, PPOTrainer  # noqa: E402
-from leibnizgym_amd.utils.rlg_train import RlGamesGpuEnvAdapter, episode_line  # noqa: E402
+from leibnizgym_amd.utils.rlg_train import RlGamesGpuEnvAdapter, diagnostic_line, episode_line  # noqa: E402
 from leibnizgym_amd.wrappers import VecTaskPython  # noqa: E402
 
 
@@ -32,6 +33,8 @@ def main(argv):
             save_dir = a.split("=", 1)[1]
         elif a == "--symmetry":
             rest.append("rlg.params.config.symmetry_augmentation=True")
+        elif a == "--diagnostics":
+            rest.append("rlg.params.config.diagnostics=True")
         else:
             rest.append(a)
     cfg = compose(rest)
@@ -76,7 +79,7 @@ def main(argv):
             print(f"epoch {st['epoch']:4d} frames {st['frames'] * world:10d} reward/step {st['mean_reward']:9.3f} "
                   f"kl {st['kl']:.4f} lr {st['lr']:.2e} loss {st['loss']:.4f}  {st['frames'] * world / (now - t0):.3e} frames/s "
                   f"since start, {steady:.3e} over the last {min(len(marks) - 1, 10)} epochs{episode_line(st)}"
-                  + (f" symmetry gap {st['symmetry_gap']:.4f}" if "symmetry_gap" in st else ""), flush=True)
+                  + (f" symmetry gap {st['symmetry_gap']:.4f}" if "symmetry_gap" in st else "") + diagnostic_line(st), flush=True)
     tr.train(epochs, log, checkpoint_dir=save_dir if rank == 0 else None)
     if world > 1 or launched:
         if rank == 0:
