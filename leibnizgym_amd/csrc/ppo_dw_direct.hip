@@ -27,6 +27,7 @@
 #include <stdint.h>
 #include <string.h>
 #include "../../include/trifinger_ppo.h"
+#include "../../include/trifinger_ppo_mixed.h"
 
 typedef float w4 __attribute__((ext_vector_type(4)));
 typedef unsigned u4 __attribute__((ext_vector_type(4)));
@@ -92,8 +93,61 @@ __device__ __forceinline__ void dw_loop(__amdgpu_buffer_rsrc_t ra, __amdgpu_buff
     }
 }
 
-// three workgroups per CU at 8 chunks x 93 full blocks = 744 workgroups: no CU carries a fourth (the launch ends with its most loaded CU)
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) k_dw_direct(const DwArgs a) {
+// The K loop with bf16 OPERANDS (include/trifinger_ppo_mixed.h: tfp_gemm_tn_partials_direct_bf16) on v_mfma_f32_16x16x32_bf16: the interleaved-tile trick
+// over 8 rows per lane.  Lane (lr, kk) loads operand[k0 + 8 kk + j][c0 + 4 lr .. + 3], j = 0..7 (la / lb: bytes per operand row); register q of those eight
+// dwordx4 is the 8-k fragment of tile q, packed with v_cvt_pk_bf16_f32 (round to nearest even): 16 MFMAs per 32-k step.  The bias column keeps summing the
+// UN-ROUNDED fp32 dZ.  The next step's 16 dwordx4 are in flight while a step's MFMAs run on its packed copy (64 + 32 registers beside the 64 accumulators).  TINY: one plain A tile, eight dword loads, 4 MFMAs per step.
+#define DW_DEPTH_BF 1
+typedef __bf16 h8 __attribute__((ext_vector_type(8)));
+typedef float w8 __attribute__((ext_vector_type(8)));
+template <bool ONES, bool TINY>
+__device__ __forceinline__ void dw_loop_bf16(__amdgpu_buffer_rsrc_t ra, __amdgpu_buffer_rsrc_t rb, unsigned va, unsigned vb, unsigned oa, unsigned ob, unsigned la,
+                                             unsigned lb, w4 (&acc)[4][4], w4& asum) {
+    w4 fa[DW_DEPTH_BF][8], fb[DW_DEPTH_BF][8];
+    auto load = [&](int d) __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            if (TINY) fa[d][j][0] = dw_load1(ra, va, oa + (unsigned)j * la); else fa[d][j] = dw_load4(ra, va, oa + (unsigned)j * la);
+            fb[d][j] = dw_load4(rb, vb, ob + (unsigned)j * lb);
+        }
+        oa += 32u * la; ob += 32u * lb;
+    };
+#pragma unroll
+    for (int d = 0; d < DW_DEPTH_BF; ++d) load(d);
+#pragma unroll 1
+    for (int t = 0; t < DW_WROWS / 32; t += DW_DEPTH_BF) {
+#pragma unroll
+        for (int d = 0; d < DW_DEPTH_BF; ++d) {
+            h8 x[4], y[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                if (q < (TINY ? 1 : 4))
+                    x[q] = __builtin_convertvector(w8{fa[d][0][q], fa[d][1][q], fa[d][2][q], fa[d][3][q], fa[d][4][q], fa[d][5][q], fa[d][6][q], fa[d][7][q]}, h8);
+                y[q] = __builtin_convertvector(w8{fb[d][0][q], fb[d][1][q], fb[d][2][q], fb[d][3][q], fb[d][4][q], fb[d][5][q], fb[d][6][q], fb[d][7][q]}, h8);
+            }
+            if (ONES) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) { if (TINY) asum[0] += fa[d][j][0]; else asum += fa[d][j]; }
+            }
+            load(d);                                               // step t + d + DW_DEPTH_BF (past the wavefront's piece: loaded, never used)
+#pragma unroll
+            for (int r = 0; r < (TINY ? 1 : 4); ++r) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) acc[r][q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x[r], y[q], acc[r][q], 0, 0, 0);
+            }
+            // the order of a step: the raw fragments are packed (and summed), their registers take the next step's 16 loads at once, then the 16 MFMAs run
+            // on the packed copies while those loads are in flight
+            __builtin_amdgcn_sched_group_barrier(0x020, 16, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, TINY ? 4 : 16, 0);
+        }
+    }
+}
+
+// three workgroups per CU at 8 chunks x 93 full blocks = 744 workgroups: no CU carries a fourth (the launch ends with its most loaded CU).
+// BF: bf16 operands, the loop above - a step of raw fp32 fragments in flight and a packed one are 96 registers beside the 64 accumulators: 168 in all, three
+// wavefronts per SIMD; the fp32 instantiation is the kernel as it was
+template <bool BF>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, BF ? 3 : 4))) k_dw_direct(const DwArgs a) {
     extern __shared__ __attribute__((aligned(16))) float red_[];   // [2][64 * DW_LP]: 34.8 KB
     float (*red)[64 * DW_LP] = (float (*)[64 * DW_LP])red_;
     // Workgroups go to the 8 XCDs round-robin in launch order and each XCD has its own 4 MB L2: every block of ONE chunk is sent to one XCD, so that the
@@ -111,7 +165,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))
     const bool tiny = N1 <= 16;                                    // uniform
     const __amdgpu_buffer_rsrc_t ra = dw_rsrc(P.A, (unsigned)rows * (unsigned)N1 * 4u), rb = dw_rsrc(P.B, (unsigned)rows * (unsigned)N2 * 4u);
     // lane part of the addresses: row kk of the step, columns c0 + 4 lr .. + 3 (tiny: column lr of dZ); the step's first row rides in the scalar offset
-    const unsigned va = 4u * (unsigned)(kk * N1 + (tiny ? min(lr, N1 - 1) : a0 + 4 * lr)), vb = 4u * (unsigned)(kk * N2 + b0 + 4 * lr);
+    unsigned va, vb;
+    if constexpr (BF) {                                            // the lane's first row of a step is 8 kk
+        va = 4u * (unsigned)(8 * kk * N1 + (tiny ? min(lr, N1 - 1) : a0 + 4 * lr)); vb = 4u * (unsigned)(8 * kk * N2 + b0 + 4 * lr);
+    } else {
+        va = 4u * (unsigned)(kk * N1 + (tiny ? min(lr, N1 - 1) : a0 + 4 * lr)); vb = 4u * (unsigned)(kk * N2 + b0 + 4 * lr);
+    }
     const unsigned sa = 16u * (unsigned)N1, sb = 16u * (unsigned)N2;               // bytes per step (4 rows)
     const bool has_ones = b0 <= N2 && N2 < b0 + 64;                // uniform: output column N2 (the bias gradient) lies in this block
     w4 acc[4][4];
@@ -122,7 +181,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))
     }
     w4 asum = w4{0.0f, 0.0f, 0.0f, 0.0f};
     const unsigned oa = (unsigned)krow0 * (unsigned)N1 * 4u, ob = (unsigned)krow0 * (unsigned)N2 * 4u;
-    if (krow0 < rows) {
+    if constexpr (BF) {
+        if (krow0 < rows) {
+            const unsigned la = 4u * (unsigned)N1, lb = 4u * (unsigned)N2;
+            if (tiny) { if (has_ones) dw_loop_bf16<true, true>(ra, rb, va, vb, oa, ob, la, lb, acc, asum); else dw_loop_bf16<false, true>(ra, rb, va, vb, oa, ob, la, lb, acc, asum); }
+            else { if (has_ones) dw_loop_bf16<true, false>(ra, rb, va, vb, oa, ob, la, lb, acc, asum); else dw_loop_bf16<false, false>(ra, rb, va, vb, oa, ob, la, lb, acc, asum); }
+        }
+    } else if (krow0 < rows) {
         if (tiny) { if (has_ones) dw_loop<true, true>(ra, rb, va, vb, oa, ob, sa, sb, acc, asum); else dw_loop<false, true>(ra, rb, va, vb, oa, ob, sa, sb, acc, asum); }
         else { if (has_ones) dw_loop<true, false>(ra, rb, va, vb, oa, ob, sa, sb, acc, asum); else dw_loop<false, false>(ra, rb, va, vb, oa, ob, sa, sb, acc, asum); }
     }
@@ -191,8 +256,8 @@ extern "C" {
 // tfp_sum_partials_multi, splits = ceil(rows / 1024)).  A[p] = dZ [rows, N1], B[p] = X [rows, N2], row-major.  -4: more than 160 blocks of 64 x 64
 // (the caller uses tfp_gemm_tn_partials_group).
 int tfp_gemm_tn_partials_direct_chunk(void) { return DW_CHUNK; }
-int tfp_gemm_tn_partials_direct(const void* const* A, const void* const* B, void* const* part, const int32_t* rows, const int32_t* N1, const int32_t* N2,
-                                int32_t n, void* stream) {
+static int dw_launch(const void* const* A, const void* const* B, void* const* part, const int32_t* rows, const int32_t* N1, const int32_t* N2, int32_t n,
+                     void* stream, bool bf16) {
     if (n <= 0 || n > DW_MAXP) return -1;
     DwArgs a; memset(&a, 0, sizeof(a));
     int nt = 0, maxrows = 0;
@@ -219,13 +284,24 @@ int tfp_gemm_tn_partials_direct(const void* const* A, const void* const* B, void
     a.ntasks = nt;
     a.nchunks = (maxrows + DW_CHUNK - 1) / DW_CHUNK;
     const size_t lds = sizeof(float) * 2 * 64 * DW_LP;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)k_dw_direct, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -2;
-        attr_set = true;
+    static bool attr_set[2] = {false, false};
+    if (!attr_set[bf16 ? 1 : 0]) {
+        const void* f = bf16 ? (const void*)k_dw_direct<true> : (const void*)k_dw_direct<false>;
+        if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -2;
+        attr_set[bf16 ? 1 : 0] = true;
     }
-    hipLaunchKernelGGL(k_dw_direct, dim3((unsigned)(nt * a.nchunks)), dim3(256), lds, (hipStream_t)stream, a);
+    if (bf16) hipLaunchKernelGGL(k_dw_direct<true>, dim3((unsigned)(nt * a.nchunks)), dim3(256), lds, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(k_dw_direct<false>, dim3((unsigned)(nt * a.nchunks)), dim3(256), lds, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+int tfp_gemm_tn_partials_direct(const void* const* A, const void* const* B, void* const* part, const int32_t* rows, const int32_t* N1, const int32_t* N2,
+                                int32_t n, void* stream) {
+    return dw_launch(A, B, part, rows, N1, N2, n, stream, false);
+}
+// the same slabs from bf16 operands (include/trifinger_ppo_mixed.h): [bf16r(A)^T bf16r(B) | column sums of the un-rounded A]
+int tfp_gemm_tn_partials_direct_bf16(const void* const* A, const void* const* B, void* const* part, const int32_t* rows, const int32_t* N1, const int32_t* N2,
+                                     int32_t n, void* stream) {
+    return dw_launch(A, B, part, rows, N1, N2, n, stream, true);
 }
 
 }  // extern "C"

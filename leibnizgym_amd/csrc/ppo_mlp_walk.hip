@@ -38,12 +38,17 @@
 // memory as these wide rows (the weight gradients stay plain products on them; rows of 441 / 513 floats miss StreamOut's dwordx4 path and leave at the layer
 // boundary).  The backward chain reads W with that leading dimension and N = dim[l], and the saved output with a row stride of its own.  The forward operands
 // of a d2rl walk are 110 KB at the trainer's shapes: that call may take the whole CU's LDS, one workgroup per CU.
+//
+// bf16 operands (BF; include/trifinger_ppo_mixed.h: tfp_net_forward_bf16 / tfp_net_backward_bf16, `mixed_precision`) is one more compile-time variant of the
+// extended walk: walk_layer_bf16 below stands where walk_layer stands, everything else - staging, statistics, d2rl (not declined: LDS stays fp32, so the
+// budget is the fp32 form's), epilogues, StreamOut - is the same code.  The fp32 kernels keep their code and their argument blocks.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
 #include "../../include/trifinger_ppo.h"
 #include "../../include/trifinger_ppo_norm.h"
 #include "../../include/trifinger_ppo_net.h"
+#include "../../include/trifinger_ppo_mixed.h"
 
 typedef float w4 __attribute__((ext_vector_type(4)));
 typedef float w4u __attribute__((ext_vector_type(4), aligned(4)));      // a dwordx4 load needs dword alignment only (rows of 41 / 113 floats)
@@ -320,12 +325,136 @@ __device__ __forceinline__ void walk_layer(const float* Xs, int px, const float*
     }
 }
 
+// The same layer with bf16 OPERANDS (include/trifinger_ppo_mixed.h; the BF variant of the extended walk): acc += bf16r(X) . bf16r(op(W)), the products exact
+// and the sums in fp32 on v_mfma_f32_16x16x32_bf16.  LDS and the weights stay fp32: a lane assembles the 8-k fragments of a 32-k step from the very
+// fragments the fp32 form reads in two of its 16-k steps ("halves") - element j of lane (lr, kk) is k = k0 + 16 (j / 4) + 4 kk + j % 4 for BOTH operands
+// (the order of the k inside a step is free as long as both use the same one) - and packs them with v_cvt_pk_bf16_f32 (round to nearest even) in registers.
+// So the A fragment is two ds_read_b128 at columns k0 + 4 kk and k0 + 16 + 4 kk, conflict-free on the 16 q + 4 pitch like the fp32 form's (8 CONSECUTIVE
+// k per lane, columns k0 + 8 kk and + 4, would be 2-way on every pitch in use), and the B fragment is two dwordx4 (forward) or eight dword loads (backward:
+// rows k0 + 4 kk + s and k0 + 16 + 4 kk + s).  The C/D layout is that of the 16 x 16 fp32 form: epilogues, StreamOut and pitches are shared.
+// K = 16 n16 halves.  A half past ceil16(K) is zero in both operands (registers); the forward half that holds the end of a row of K % 4 != 0 floats
+// (41, 113) is loaded element by element with clamped k, against A values the staging zeroed; everything else is the uniform loader of the fp32 form.
+typedef __bf16 h8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ h8 pack_bf16(const w4& lo, const w4& hi) {
+    return __builtin_convertvector(__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7), h8);
+}
+template <int NCT, bool KMAJ, bool SO, class EpiLoad>
+__device__ __forceinline__ void walk_layer_bf16(const float* Xs, int px, const float* __restrict__ W, int ldw, int K, int N, int ct0, int nct, StreamOut& so,
+                                                w4 (&acc)[2][NCT], EpiLoad&& epi_load) {
+    const int lane = threadIdx.x & 63, lr = lane & 15, kk = lane >> 4;
+    const __amdgpu_buffer_rsrc_t rw = make_rsrc(W, (unsigned)(KMAJ ? K * ldw : N * ldw) * 4u);
+    unsigned boff[NCT];
+#pragma unroll
+    for (int j = 0; j < NCT; ++j) {
+        const int n = min((ct0 + min(j, nct - 1)) * 16 + lr, N - 1);
+        boff[j] = 4u * (KMAJ ? (unsigned)(n + 4 * kk * ldw) : (unsigned)(n * ldw + 4 * kk));
+    }
+    const float* xa = Xs + lr * px + 4 * kk;
+    const bool ragged = !KMAJ && (K & 3) != 0;
+    const int n16 = (K + 15) >> 4, nuni = ragged ? n16 - 1 : n16;  // halves in all; halves the uniform loader serves
+    const int nfull = nuni >> 1, rem = n16 - 2 * nfull;             // 32-k steps of two uniform halves; halves of the last step (0: there is none)
+    const bool lo_ragged = ragged && rem == 1, hi_there = rem == 2; // the last step: (ragged | zero), (uniform | zero) or (uniform | ragged)
+    auto loadb16 = [&](int h, int j, w4& b) __attribute__((always_inline)) {
+        const int k0 = 16 * h;
+        if (KMAJ) {
+            const unsigned s0 = (unsigned)(k0 * ldw) * 4u, sl = (unsigned)ldw * 4u;
+            b = w4{buf_load1(rw, boff[j], s0), buf_load1(rw, boff[j], s0 + sl), buf_load1(rw, boff[j], s0 + 2u * sl), buf_load1(rw, boff[j], s0 + 3u * sl)};
+        } else {
+            b = buf_load4(rw, boff[j], (unsigned)k0 * 4u);
+        }
+    };
+    auto loadb_ragged = [&](int h, int j, w4& b) __attribute__((always_inline)) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int k = min(16 * h + 4 * kk + s, K - 1);         // k >= K: a copy of the row's last element, against an A value that is zero
+            b[s] = buf_load1(rw, boff[j] + 4u * (unsigned)(k - 4 * kk), 0u);
+        }
+    };
+    auto loada16 = [&](int h, w4 (&a)[2]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) a[i] = *(const w4*)(xa + i * 16 * px + 16 * h);
+    };
+    const w4 zero4 = w4{0.0f, 0.0f, 0.0f, 0.0f};
+    auto tail_a = [&](w4 (&a)[2][2]) __attribute__((always_inline)) {
+        loada16(2 * nfull, a[0]);
+        if (hi_there) loada16(2 * nfull + 1, a[1]); else { a[1][0] = zero4; a[1][1] = zero4; }
+    };
+    auto tail_b = [&](int j, w4 (&b)[2]) __attribute__((always_inline)) {
+        if (lo_ragged) loadb_ragged(2 * nfull, j, b[0]); else loadb16(2 * nfull, j, b[0]);
+        if (hi_there) loadb_ragged(2 * nfull + 1, j, b[1]); else b[1] = zero4;
+    };
+    auto pack_a = [&](const w4 (&a)[2][2], h8 (&pa)[2]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) pa[i] = pack_bf16(a[0][i], a[1][i]);
+    };
+    auto mma_tile = [&](const h8 (&pa)[2], const w4 (&b)[2], int j) __attribute__((always_inline)) {
+        const h8 pb = pack_bf16(b[0], b[1]);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa[i], pb, acc[i][j], 0, 0, 0);
+    };
+    w4 a[2][2], an[2][2], b[NCT][2];                                // [half][row tile], [tile][half]
+    h8 pa[2];
+    if (nfull == 0) {                                               // K <= 16, or K <= 32 and ragged: the last step alone
+        tail_a(a);
+#pragma unroll
+        for (int j = 0; j < NCT; ++j) tail_b(j, b[j]);
+        if (SO) so.flush();
+        pack_a(a, pa);
+#pragma unroll
+        for (int j = 0; j < NCT; ++j) { mma_tile(pa, b[j], j); epi_load(j); }
+        return;
+    }
+    loada16(0, a[0]); loada16(1, a[1]);
+#pragma unroll
+    for (int j = 0; j < NCT; ++j) { loadb16(0, j, b[j][0]); loadb16(1, j, b[j][1]); }
+    for (int t = 0; t + 1 < nfull; ++t) {
+        w4 sv;
+        if (SO) sv = so.read();
+        loada16(2 * t + 2, an[0]); loada16(2 * t + 3, an[1]);
+        pack_a(a, pa);
+#pragma unroll
+        for (int j = 0; j < NCT; ++j) {
+            mma_tile(pa, b[j], j);
+            loadb16(2 * t + 2, j, b[j][0]); loadb16(2 * t + 3, j, b[j][1]);
+        }
+        if (SO) so.write(sv);
+        // the pinned order of a step, restated for this form: the 4 LDS reads of the next A fragments (5 with a stream-out), then per column tile its
+        // 2 MFMAs followed by the loads of its next B fragment (2 dwordx4 forward, 8 dwords backward); the packing goes where its MFMAs need it
+        __builtin_amdgcn_sched_group_barrier(0x100, SO ? 5 : 4, 0);
+#pragma unroll
+        for (int j = 0; j < NCT; ++j) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+            __builtin_amdgcn_sched_group_barrier(0x020, KMAJ ? 8 : 2, 0);
+        }
+#pragma unroll
+        for (int h = 0; h < 2; ++h) { a[h][0] = an[h][0]; a[h][1] = an[h][1]; }
+    }
+    if (rem) {
+        tail_a(an);
+        pack_a(a, pa);
+#pragma unroll
+        for (int j = 0; j < NCT; ++j) {
+            mma_tile(pa, b[j], j);
+            tail_b(j, b[j]);
+        }
+        if (SO) so.flush();
+        pack_a(an, pa);
+#pragma unroll
+        for (int j = 0; j < NCT; ++j) { mma_tile(pa, b[j], j); epi_load(j); }
+    } else {
+        if (SO) so.flush();
+        pack_a(a, pa);
+#pragma unroll
+        for (int j = 0; j < NCT; ++j) { mma_tile(pa, b[j], j); epi_load(j); }
+    }
+}
+
 // layer + epilogue for a wavefront with NCT column tiles.  Ys: LDS output [32][py] or nullptr (last product).  G: memory output [M, N], written here only
 // for the last product (the others leave through StreamOut during the next step).
 //   BWD = false: v = acc + bias, ELU when act;  BWD = true: v = acc * elu'(E[row, col]) when E (the saved output of the layer this is the dZ of)
 //   EXT (the extended walk, include/trifinger_ppo_net.h): `act` is an activation code, forwards and backwards; ldw / lde are the leading dimensions of W and E
 //   (the plain walk passes BWD ? N : K and N); xcols: the columns of Ys behind N belong to the row block's input (d2rl) and are not written here.
-template <int NCT, bool BWD, bool SO, bool EXT>
+template <int NCT, bool BWD, bool SO, bool EXT, bool BF = false>
 __device__ __forceinline__ void walk_run(const float* Xs, int px, const float* __restrict__ W, int ldw, int K, int N, const float* __restrict__ bias, int act,
                                          const float* __restrict__ E, int lde, bool xcols, float* Ys, int py, float* __restrict__ G, int row0, int M, int ct0,
                                          int nct, StreamOut& so, int stamp) {
@@ -378,7 +507,8 @@ __device__ __forceinline__ void walk_run(const float* Xs, int px, const float* _
         for (int j = 0; j < NCT; ++j) asm volatile("" : "+v"(acc[i][j]));       // the zeroing instructions stay in front of ...
     }
     asm volatile("s_nop 7" ::: "memory");                          // ... the wait states before the first MFMA reads an accumulator as srcC
-    walk_layer<NCT, BWD, SO>(Xs, px, W, ldw, K, N, ct0, nct, so, acc, epi_load);
+    if constexpr (BF) walk_layer_bf16<NCT, BWD, SO>(Xs, px, W, ldw, K, N, ct0, nct, so, acc, epi_load);
+    else walk_layer<NCT, BWD, SO>(Xs, px, W, ldw, K, N, ct0, nct, so, acc, epi_load);
     walk_mfma_drain<NCT>(acc);
     WSTAMP(2 + 3 * stamp);
     if (EXT) {
@@ -459,7 +589,7 @@ __device__ __forceinline__ void walk_run(const float* Xs, int px, const float* _
 
 // this wavefront's share of a layer: all 32 rows and a quarter of the 16-column tiles (the first `nct_all % 4` wavefronts take one more); the tile count
 // selects the instantiation with exactly that many accumulator columns
-template <bool BWD, bool EXT>
+template <bool BWD, bool EXT, bool BF = false>
 __device__ __forceinline__ void walk_dispatch(const float* Xs, int px, const float* __restrict__ W, int ldw, int K, int N, const float* __restrict__ bias,
                                               int act, const float* __restrict__ E, int lde, bool xcols, float* Ys, int py, float* __restrict__ G, int row0,
                                               int M, StreamOut& so, bool has_so, int stamp) {
@@ -467,8 +597,8 @@ __device__ __forceinline__ void walk_dispatch(const float* Xs, int px, const flo
     const int nct_all = (N + 15) >> 4, base = nct_all >> 2, rem = nct_all & 3;
     const int nct = base + (wave < rem ? 1 : 0), ct0 = wave * base + min(wave, rem);
     if (nct <= 0) { if (has_so) so.flush(); return; }
-#define WALK_CASE(n_) do { if (has_so) walk_run<n_, BWD, true, EXT>(Xs, px, W, ldw, K, N, bias, act, E, lde, xcols, Ys, py, G, row0, M, ct0, nct, so, stamp); \
-                           else walk_run<n_, BWD, false, EXT>(Xs, px, W, ldw, K, N, bias, act, E, lde, xcols, Ys, py, G, row0, M, ct0, nct, so, stamp); } while (0)
+#define WALK_CASE(n_) do { if (has_so) walk_run<n_, BWD, true, EXT, BF>(Xs, px, W, ldw, K, N, bias, act, E, lde, xcols, Ys, py, G, row0, M, ct0, nct, so, stamp); \
+                           else walk_run<n_, BWD, false, EXT, BF>(Xs, px, W, ldw, K, N, bias, act, E, lde, xcols, Ys, py, G, row0, M, ct0, nct, so, stamp); } while (0)
     switch (nct) {
         case 1: WALK_CASE(1); break;
         case 2: WALK_CASE(2); break;
@@ -498,7 +628,7 @@ template <bool NORM> struct walk_args<NORM, true> { typedef WalkArgsExt type; };
 // two workgroups of four wavefronts per CU: two wavefronts per SIMD, 256 registers each.  NORM (forward only): the staged input passes through a.nm.
 // EXT forward is always NORM (a network without statistics has mean NULL); with the wide rows of a d2rl network its LDS may exceed half a CU's: then one
 // workgroup per CU runs, with the same code.
-template <bool BWD, bool NORM = false, bool EXT = false>
+template <bool BWD, bool NORM = false, bool EXT = false, bool BF = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) k_mlp_walk(const typename walk_args<NORM, EXT>::type a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int ni = (int)blockIdx.x / a.blocks_per_net;
@@ -599,7 +729,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
         float* G = BWD ? net.y[l - 1] : net.y[l];
         const int act = BWD ? (EXT ? net.act[l - 1] : 0) : net.act[l];
         const float* bias = BWD ? nullptr : net.b[l];
-        walk_dispatch<BWD, EXT>(cur, px, net.W[l], ldw, K, N, bias, act, E, lde, xcols, Ys, py, G, row0, a.M, so, has_so, s);
+        walk_dispatch<BWD, EXT, BF>(cur, px, net.W[l], ldw, K, N, bias, act, E, lde, xcols, Ys, py, G, row0, a.M, so, has_so, s);
         WSTAMP(3 + 3 * s);
         if (!lastp) __syncthreads();
         WSTAMP(4 + 3 * s);
@@ -718,7 +848,7 @@ static int net_setup(const TfpNet* nets, int32_t n_nets, bool bwd, bool shapes_o
     }
     return 0;
 }
-static int net_launch(const TfpNet* nets, int32_t n_nets, int32_t M, bool bwd, void* stream, bool shapes_only) {
+static int net_launch(const TfpNet* nets, int32_t n_nets, int32_t M, bool bwd, void* stream, bool shapes_only, bool bf16 = false) {
     if (M <= 0) return -1;
     WalkArgsExt a; bool d2rl = false;
     int rc = net_setup(nets, n_nets, bwd, shapes_only, a, &d2rl);
@@ -728,21 +858,31 @@ static int net_launch(const TfpNet* nets, int32_t n_nets, int32_t M, bool bwd, v
     size_t lds = 0;
     rc = walk_prepare(a, M, bwd, &lds, a.kin, limit, shapes_only);
     if (rc || shapes_only) return rc;
-    static bool attr_set[2] = {false, false};
-    const void* f = bwd ? (const void*)k_mlp_walk<true, false, true> : (const void*)k_mlp_walk<false, true, true>;
-    if (!attr_set[bwd ? 1 : 0]) {
+    // (bf16: the BF instantiations of the same kernel - LDS, limits and argument block are those of the fp32 form, d2rl included)
+    static bool attr_set[4] = {false, false, false, false};
+    const int which = (bf16 ? 2 : 0) + (bwd ? 1 : 0);
+    const void* f = bf16 ? (bwd ? (const void*)k_mlp_walk<true, false, true, true> : (const void*)k_mlp_walk<false, true, true, true>)
+                         : (bwd ? (const void*)k_mlp_walk<true, false, true> : (const void*)k_mlp_walk<false, true, true>);
+    if (!attr_set[which]) {
         if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bwd ? 80 * 1024 : 160 * 1024) != hipSuccess) return -2;
-        attr_set[bwd ? 1 : 0] = true;
+        attr_set[which] = true;
     }
     const dim3 grid(a.blocks_per_net * n_nets), block(256);
     hipStream_t s = (hipStream_t)stream;
-    if (bwd) hipLaunchKernelGGL((k_mlp_walk<true, false, true>), grid, block, lds, s, a);
+    if (bf16) {
+        if (bwd) hipLaunchKernelGGL((k_mlp_walk<true, false, true, true>), grid, block, lds, s, a);
+        else hipLaunchKernelGGL((k_mlp_walk<false, true, true, true>), grid, block, lds, s, a);
+    } else if (bwd) hipLaunchKernelGGL((k_mlp_walk<true, false, true>), grid, block, lds, s, a);
     else hipLaunchKernelGGL((k_mlp_walk<false, true, true>), grid, block, lds, s, a);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 int tfp_net_forward(const TfpNet* nets, int32_t n_nets, int32_t M, void* stream) { return net_launch(nets, n_nets, M, false, stream, false); }
 int tfp_net_backward(const TfpNet* nets, int32_t n_nets, int32_t M, void* stream) { return net_launch(nets, n_nets, M, true, stream, false); }
 int tfp_net_fits(const TfpNet* nets, int32_t n_nets, int32_t backward) { return net_launch(nets, n_nets, 1, backward != 0, nullptr, true); }
+// ---- `mixed_precision` (include/trifinger_ppo_mixed.h): the same walk with bf16 operands on v_mfma_f32_16x16x32_bf16 ----
+int tfp_net_forward_bf16(const TfpNet* nets, int32_t n_nets, int32_t M, void* stream) { return net_launch(nets, n_nets, M, false, stream, false, true); }
+int tfp_net_backward_bf16(const TfpNet* nets, int32_t n_nets, int32_t M, void* stream) { return net_launch(nets, n_nets, M, true, stream, false, true); }
+int tfp_net_fits_bf16(const TfpNet* nets, int32_t n_nets, int32_t backward) { return net_launch(nets, n_nets, 1, backward != 0, nullptr, true, true); }
 
 #ifdef WALK_TIMING
 int tfp_walk_debug_read(unsigned long long* out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_walk_t), sizeof(unsigned long long) * 128) == hipSuccess ? 0 : -3; }

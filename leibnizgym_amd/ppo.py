@@ -118,6 +118,20 @@ over the steps), `grad_norm_max`, `grad_trunc_frac` and the same three with suff
 rank-local like `symmetry_gap`: `explained_variance` = 1 - Var(ret - val) / Var(ret) over the rollout's samples with w = 1 in reward units (ret - val is the
 advantage estimate as GAE filed it; population variances; absent when Var(ret) = 0), `entropy` = sum_a (log sigma_a + 0.5 + 0.5 log 2 pi), `sigma_mean`.
 `last_diag` keeps the epoch's record.  Checkpoints do not carry it.
+Mixed precision (`params.config.mixed_precision`, RL-Games' key; off by default, and off every launch, buffer, statistic and bit is what it was).  With
+bf16r(t) = t.to(bfloat16).to(float32) (round to nearest even) every Linear of both networks - hidden layers, the mu head, the value head - becomes
+    forward   y  = bf16r(x) @ bf16r(W).T + b           products accumulated in fp32, the bias added in fp32
+    backward  gx = bf16r(gy) @ bf16r(W);   gW = bf16r(gy).T @ bf16r(x);   gb = gy.sum(0)   (the un-rounded gy)
+with the rounding straight-through for autograd: `_MixedLinear` IS the specification - what the CPU path and `fused_kernels=False` run and what the kernels
+are held to.  Everything else stays fp32 and unchanged: master weights, biases and log_std; activations and their derivatives from the saved output; the
+saved layer outputs and dZ in memory; input normalisation (formed in fp32, then rounded as the operand); the [h | x] operand of d2rl (rounded elementwise);
+the objective, GAE, the records and Adam; checkpoints (the same keys: they move freely between on and off); the gradient exchange (fp32).  The rollout
+forward, `act()`, `play()` and `evaluate()` use the same arithmetic as the update - otherwise the probability ratio of the first minibatch would not be 1.
+Deliberately NOT RL-Games: it autocasts to fp16 under a gradient scaler; this build rounds to bf16, which has fp32's range, and needs no scaler (DESIGN.md
+section 6).  On the GPU: include/trifinger_ppo_mixed.h - the network walk and the direct weight-gradient kernel with bf16 operands on
+v_mfma_f32_16x16x32_bf16, packed in registers at the fragment (memory and LDS stay fp32).  There is no per-layer bf16 tier: shapes the bf16 walk declines put
+the trainer on the torch statement, said once (`_fused_refusal`); a weight-gradient group the direct kernel declines at run time is formed as torch products of
+the rounded operands.  ppo_kernels.n_calls counts the launches per entry point.
 
 This is host-side training glue, NOT part of the measured hot path.  On a GPU the minibatch step runs on the hand-written kernels of
 csrc/ppo_kernels.hip (leibnizgym_amd/ppo_kernels.py): one gather launch, the Linear / ELU layers on fp32 MFMA, the objective with all
@@ -187,6 +201,7 @@ class PPOConfig:
     score_to_win: float = float("inf")    # params.config.score_to_win (RL-Games' key): train() stops when episode_return exceeds it; needs track_episodes
     symmetry_augmentation: bool = False   # params.config.symmetry_augmentation: every minibatch with its two images under the robot's 120-degree turn (module docstring)
     diagnostics: bool = False         # params.config.diagnostics: clip fraction, approx_kl, gradient norms, explained variance in the statistics (module docstring)
+    mixed_precision: bool = False     # params.config.mixed_precision (RL-Games' key): every Linear's products take bf16 operands, fp32 sums (module docstring)
 
     def __post_init__(self):
         if self.value_bootstrap and not self.episode_ends:
@@ -227,7 +242,7 @@ class PPOConfig:
                   episode_ends=bool(c.get("episode_ends", False)), value_bootstrap=bool(c.get("value_bootstrap", False)),
                   track_episodes=bool(c.get("track_episodes", False)), games_to_track=int(c.get("games_to_track", 100)),
                   score_to_win=float(c.get("score_to_win", float("inf"))), symmetry_augmentation=bool(c.get("symmetry_augmentation", False)),
-                  diagnostics=bool(c.get("diagnostics", False)))
+                  diagnostics=bool(c.get("diagnostics", False)), mixed_precision=bool(c.get("mixed_precision", False)))
         # without a central value network the critic takes the actor's keys
         kw.update(value_activation=kw["activation"], value_d2rl=kw["d2rl"], value_truncate_grads=kw["truncate_grads"])
         if cv:
@@ -270,8 +285,37 @@ class _SplitKLinear(torch.autograd.Function):
         return gx, gw, gy.sum(0)
 
 
+def bf16r(t):
+    """t rounded to bfloat16 (round to nearest even) and read back in its own type (float32 in the trainer; a float64 reference stays float64)"""
+    return t.to(torch.bfloat16).to(t.dtype)
+
+
+class _MixedLinear(torch.autograd.Function):
+    """`mixed_precision`, THE STATEMENT of a Linear with bf16 operands (module docstring; include/trifinger_ppo_mixed.h): y = bf16r(x) bf16r(W)^T + b with the
+    products accumulated in fp32 and the bias added in fp32; gx = bf16r(gy) bf16r(W), gW = bf16r(gy)^T bf16r(x), gb = the column sums of the UN-ROUNDED gy.
+    The rounding is straight-through: no derivative of bf16r appears.  x may carry leading dimensions; they are rows."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        xr, wr = bf16r(x), bf16r(w)
+        ctx.save_for_backward(xr, wr)
+        return torch.matmul(xr, wr.t()) + b
+
+    @staticmethod
+    def backward(ctx, gy):
+        xr, wr = ctx.saved_tensors
+        gr = bf16r(gy)
+        gx = torch.matmul(gr, wr) if ctx.needs_input_grad[0] else None
+        g2, x2 = gr.reshape(-1, gr.shape[-1]), xr.reshape(-1, xr.shape[-1])
+        return gx, g2.t() @ x2, gy.reshape(-1, gy.shape[-1]).sum(0)
+
+
 class SplitKLinear(nn.Linear):
+    mixed = False              # `mixed_precision`: the layer is _MixedLinear (set by ActorCritic, a plain attribute: the state_dict keeps its keys)
+
     def forward(self, x):
+        if self.mixed:
+            return _MixedLinear.apply(x, self.weight, self.bias)
         if x.dim() == 2 and x.is_cuda and torch.is_grad_enabled():
             return _SplitKLinear.apply(x, self.weight, self.bias)
         return super().forward(x)
@@ -308,12 +352,13 @@ class FusedMLP(nn.Sequential):
     a plain product)."""
     mfma = False
     d2rl = False
+    mixed = False              # `mixed_precision`: the Linear layers are _MixedLinear; on the hand-written path the walk with bf16 operands runs the network
 
     def layer_list(self):
         """[(weight, bias, act, grad_out)] of the Linear layers (a ppo_kernels.LayerList: it carries `d2rl`), act = the activation code behind the layer"""
         from .ppo_kernels import LayerList
         mods, out = list(self), LayerList()
-        out.d2rl = self.d2rl
+        out.d2rl, out.mixed = self.d2rl, self.mixed
         other = False
         for i, m in enumerate(mods):
             if isinstance(m, nn.Linear):
@@ -324,8 +369,8 @@ class FusedMLP(nn.Sequential):
         return out
 
     def forward(self, x):
-        if not (self.mfma and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32):
-            return super().forward(x)
+        if self.mixed or not (self.mfma and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32):
+            return super().forward(x)                               # (mixed: the torch statement - the per-layer kernels are fp32, there is no bf16 tier of them)
         from .ppo_kernels import mfma_linear
         mods = list(self)
         i = 0
@@ -644,6 +689,13 @@ class ActorCritic(nn.Module):
         self.actor = mlp(obs_dim, units, act_dim, a_act, a_d2rl)
         self.critic = mlp(state_dim if state_dim > 0 else obs_dim, units, 1, c_act, c_d2rl)
         self.log_std = nn.Parameter(torch.zeros(act_dim))          # sigma_init const 0, fixed_sigma
+        self.mixed = bool(cfg is not None and cfg.mixed_precision)
+        if self.mixed:                                              # `mixed_precision`: every Linear of both networks, the heads included
+            for net in (self.actor, self.critic):
+                net.mixed = True
+                for m in net:
+                    if isinstance(m, nn.Linear):
+                        m.mixed = True
         if cfg is not None:
             self.init_like_rl_games(cfg)
 
@@ -676,7 +728,8 @@ class ActorCritic(nn.Module):
         (FusedMLP.forward: the per-layer kernels, or torch) behind InputNorm.normalize"""
         recs = [self.obs_norm if n == "actor" else self.critic_norm() for n in nets]
         mods, x = [getattr(self, n) for n in nets], xs[0]
-        if runner and all(m.mfma for m in mods) and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and all(x.dim() == 2 for x in xs):
+        # (`mixed_precision`: every call without autograd takes that ONE call - the walk with bf16 operands is the only kernel tier of the mode)
+        if (runner or self.mixed) and all(m.mfma for m in mods) and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and all(x.dim() == 2 for x in xs):
             from . import ppo_kernels as pk
             ys = pk.forward_nets([(x.contiguous(), m.layer_list()) for x, m in zip(xs, mods)], store_hidden=False,
                                  norms=[r.stats() if r is not None else None for r in recs])
@@ -871,6 +924,9 @@ class PPOTrainer:
         if (pk.needs_net_walk(la) or pk.needs_net_walk(lc)) and not (pk.net_fits([la, lc], False) and pk.net_fits([la, lc], True)):
             return ("network.mlp.activation / d2rl: the network walk declines these shapes (a layer wider than 416 or rows beyond the LDS of a CU) and the "
                     "per-layer kernels know ELU only")
+        if self.cfg.mixed_precision and not (pk.net_fits([la, lc], False, mixed=True) and pk.net_fits([la, lc], True, mixed=True)):
+            return ("params.config.mixed_precision: the network walk with bf16 operands declines these shapes (more than 4 layers, a layer wider than 416 or "
+                    "rows beyond the LDS of a CU) and there is no per-layer bf16 tier")
         return None
 
     def _set_actor_lr(self, lr):

@@ -53,7 +53,22 @@ _ARGTYPES = {
     "tfp_gather_rows_sym": [_P] * 7 + [_I, _P, _I, _P], "tfp_ppo_loss_sym": [_P] * 9 + [_I] * 4 + [_R] * 4 + [_P] * 6,
     # training diagnostics (include/trifinger_ppo_diag.h: the DIAG variants of the objective and of the optimiser, the record behind their arguments)
     "tfp_ppo_loss_diag": [_P] * 9 + [_I] * 4 + [_R] * 4 + [_P] * 7, "tfp_clip_adam_diag": [_P] * 4 + [_I, _I] + [_P] * 3 + [_R] * 5 + [_P, _P],
+    # `mixed_precision` (include/trifinger_ppo_mixed.h: the walk and the direct weight-gradient kernel with bf16 operands)
+    "tfp_net_forward_bf16": _WALK, "tfp_net_backward_bf16": _WALK, "tfp_net_fits_bf16": [_P, _I, _I], "tfp_gemm_tn_partials_direct_bf16": [_P] * 6 + [_I, _P],
 }
+# launches per entry point of the three product kernels - the walk forwards and backwards, the direct weight gradients - since import: which tier ran a
+# network (the tests of `mixed_precision` read them: the bf16 names advance, the fp32 walk's do not); `n_mixed_dw_torch`: weight-gradient groups the direct
+# bf16 kernel declined, formed as torch products of the rounded operands
+n_calls = {}
+
+
+def _count(name):
+    n_calls[name] = n_calls.get(name, 0) + 1
+
+
+def bf16r(t):
+    """t rounded to bfloat16 (round to nearest even) and read back in its own type: the operand rounding of `mixed_precision` (ppo._MixedLinear)"""
+    return t.to(torch.bfloat16).to(t.dtype)
 
 
 def load():
@@ -675,11 +690,12 @@ def gemm_tn_bias_group(as_, bs, ys, outs, chunk=256):
     return True
 
 
-def gemm_tn_bias_direct(as_, bs, outs):
+def gemm_tn_bias_direct(as_, bs, outs, mixed=False):
     """the chunk slabs of up to 8 weight / bias gradients [a.T @ b | a.sum(0)] in ONE launch of the direct kernel (csrc/ppo_dw_direct.hip: 64 x 64 blocks,
     operands straight from memory), their sums deferred to flush_partial_sums().  a: dZ [rows, N1] (plain: no activation factor), b: [rows, N2].
-    Returns False when the call does not fit (nothing is queued then)."""
+    Returns False when the call does not fit (nothing is queued then).  `mixed`: tfp_gemm_tn_partials_direct_bf16 - [bf16r(a).T @ bf16r(b) | a.sum(0)]."""
     n = len(as_)
+    name = "tfp_gemm_tn_partials_direct_bf16" if mixed else "tfp_gemm_tn_partials_direct"
     as_ = [a if a.is_contiguous() else a.contiguous() for a in as_]
     bs = [b if b.is_contiguous() else b.contiguous() for b in bs]
     rows = [a.shape[0] for a in as_]
@@ -688,10 +704,11 @@ def gemm_tn_bias_direct(as_, bs, outs):
     chunk = load().tfp_gemm_tn_partials_direct_chunk()          # rows per slab of the build
     splits = [(r + chunk - 1) // chunk for r in rows]
     parts = [torch.empty(sp * a1 * (b2 + 1), device=as_[0].device, dtype=torch.float32) for sp, a1, b2 in zip(splits, n1, n2)]
-    rc = load().tfp_gemm_tn_partials_direct(_vp(as_), _vp(bs), _vp(parts), _ip(rows), _ip(n1), _ip(n2), n, _stream(as_[0]))
+    rc = getattr(load(), name)(_vp(as_), _vp(bs), _vp(parts), _ip(rows), _ip(n1), _ip(n2), n, _stream(as_[0]))
     if rc == -4:
         return False
-    _chk(rc, "tfp_gemm_tn_partials_direct")
+    _chk(rc, name)
+    _count(name)
     for k in range(n):
         _PENDING_SUMS.append((parts[k], outs[k][0], outs[k][1], splits[k], n1[k], n2[k]))
     return True
@@ -773,9 +790,11 @@ class LayerList(list):
     """[(weight, bias, act, grad_out)] of a network's Linear layers, act an activation code.  `d2rl`: the input x is concatenated behind every hidden
     output but the last - weight l is [out, in + D0] for 1 <= l <= len - 2 - and the walk keeps / expects the hidden outputs of those layers as the wide
     rows [h | x] (include/trifinger_ppo_net.h).  `ext`: what needs_net_walk() answers, when the builder of the list already knows it (None: computed per call;
-    the trainer's lists carry it so that a minibatch step does not walk the layers again)"""
+    the trainer's lists carry it so that a minibatch step does not walk the layers again).  `mixed`: `mixed_precision` - every product of the network takes
+    bf16 operands (include/trifinger_ppo_mixed.h); forward_nets / backward_nets read the mode from here"""
     d2rl = False
     ext = None
+    mixed = False
 
 
 def _d2rl(layers):
@@ -824,13 +843,14 @@ def _walk_blocks(nets, ext, norms=None, check=False):
 
 # the walk's entry point by (direction, extended, statistics given).  The plain kernels keep their own argument block and entry points on purpose: their
 # timing is what DESIGN.md section 9 item 1 rests on
+_WALK_ENTRY_MIXED = {"forward": "tfp_net_forward_bf16", "backward": "tfp_net_backward_bf16"}      # `mixed_precision`: the extended block, whatever the network
 _WALK_ENTRY = {("forward", False, False): "tfp_mlp_forward", ("forward", False, True): "tfp_mlp_forward_norm", ("forward", True, False): "tfp_net_forward",
                ("forward", True, True): "tfp_net_forward", ("backward", False, False): "tfp_mlp_backward", ("backward", True, False): "tfp_net_backward"}
 
 
-def _walk_launch(direction, nets, ext, norms, M, stream):
-    """ONE launch of the walk over `nets` (as _walk_blocks takes them); False when the kernel declines the shapes"""
-    name = _WALK_ENTRY[direction, bool(ext), norms is not None]
+def _walk_launch(direction, nets, ext, norms, M, stream, mixed=False):
+    """ONE launch of the walk over `nets` (as _walk_blocks takes them); False when the kernel declines the shapes.  `mixed`: the bf16 entry point (ext is True)"""
+    name = _WALK_ENTRY_MIXED[direction] if mixed else _WALK_ENTRY[direction, bool(ext), norms is not None]
     args = [C.cast(_walk_blocks(nets, ext, norms, check=ext and direction == "forward"), C.c_void_p)]
     if norms is not None and not ext:                               # the plain walk takes the statistics as a block of their own
         nm = (TfpNorm * len(nets))()
@@ -842,18 +862,21 @@ def _walk_launch(direction, nets, ext, norms, M, stream):
     if rc == -4:
         return False
     _chk(rc, name)
+    _count(name)
     return True
 
 
-def net_fits(layer_lists, backward=False):
-    """whether the SHAPES of one or two networks (LayerLists; activation codes 0 .. 6) fit the network walk in the given direction: tfp_net_fits, no launch"""
+def net_fits(layer_lists, backward=False, mixed=False):
+    """whether the SHAPES of one or two networks (LayerLists; activation codes 0 .. 6) fit the network walk in the given direction: tfp_net_fits
+    (`mixed`: tfp_net_fits_bf16), no launch"""
     if not (0 < len(layer_lists) <= 2) or any(not (0 < len(l) <= WALK_MAXL) or any(not (0 <= int(e[2]) <= 6) for e in l) for l in layer_lists):
         return False
     arr = _walk_blocks([(None, layers, None, None) for layers in layer_lists], True, check=True)
-    rc = load().tfp_net_fits(C.cast(arr, C.c_void_p), len(layer_lists), 1 if backward else 0)
+    name = "tfp_net_fits_bf16" if mixed else "tfp_net_fits"
+    rc = getattr(load(), name)(C.cast(arr, C.c_void_p), len(layer_lists), 1 if backward else 0)
     if rc == -4:
         return False
-    _chk(rc, "tfp_net_fits")
+    _chk(rc, name)
     return True
 
 
@@ -862,17 +885,19 @@ def _walkable(nets):
             and all(x.dim() == 2 and x.is_contiguous() and x.shape[0] == nets[0][0].shape[0] for x, _ in nets))
 
 
-def mlp_walk_forward(nets, store_hidden=True, norms=None, ext=None):
+def mlp_walk_forward(nets, store_hidden=True, norms=None, ext=None, mixed=False):
     """nets: [(x, layers)] for one or two Linear / ELU stacks over the same rows (`layers` as in mlp_forward).  ONE launch; returns the list of layer
     outputs per network (hidden outputs None with store_hidden = False: the rollout needs the network outputs only), or None when the shapes do not
     fit the walk (the caller then runs the layers one by one).  `norms`: None, or per network None / (mean_f, inv_std_f, clip): that network reads
     clamp((x - mean_f) * inv_std_f, -clip, clip), formed while the rows are staged (tfp_mlp_forward_norm) - the bits of the plain walk on normalize_rows(x).
     A network with another activation than ELU / none or with d2rl (`layers` a LayerList) takes the call to tfp_net_forward (`ext` = True forces that entry
-    point, which for plain networks returns the same bits); of a d2rl network the outputs of the layers 0 .. len - 3 come back as the wide rows [h | x]."""
+    point, which for plain networks returns the same bits); of a d2rl network the outputs of the layers 0 .. len - 3 come back as the wide rows [h | x].
+    `mixed`: tfp_net_forward_bf16 - every product with bf16 operands, everything else as the extended entry point."""
     if not _walkable(nets):
         return None
     if ext is None:
         ext = any(needs_net_walk(layers) for _, layers in nets)
+    ext = bool(ext or mixed)
     if norms is not None and not any(e is not None for e in norms):
         norms = None
     if norms is not None and not (len(norms) == len(nets) and all(e is None or _norm_ok(e, x.shape[1], x.device) for e, (x, _) in zip(norms, nets))):
@@ -881,16 +906,17 @@ def mlp_walk_forward(nets, store_hidden=True, norms=None, ext=None):
     outs = [[torch.empty(M, _out_width(layers, l) if ext else w.shape[0], device=x.device, dtype=torch.float32)
              if (store_hidden or l == len(layers) - 1) else None for l, (w, _, _, _) in enumerate(layers)] for x, layers in nets]
     blocks = [(x, layers, ys, None) for (x, layers), ys in zip(nets, outs)]
-    return outs if _walk_launch("forward", blocks, ext, norms, M, _stream(nets[0][0])) else None
+    return outs if _walk_launch("forward", blocks, ext, norms, M, _stream(nets[0][0]), mixed) else None
 
 
-def mlp_walk_backward(nets, ext=None):
+def mlp_walk_backward(nets, ext=None, mixed=False):
     """nets: [(gy, ys, layers)]: gy = gradient of the network output, ys = the layer outputs the forward kept.  ONE launch for the whole input-gradient
     chain; returns per network the list dz with dz[l] = gradient of layer l's pre-activation (dz[-1] is gy itself), or None when the shapes do not fit."""
     if not (0 < len(nets) <= 2) or any(len(layers) > WALK_MAXL or any(y is None for y in ys) for _, ys, layers in nets):
         return None
     if ext is None:
         ext = any(needs_net_walk(layers) for _, _, layers in nets)
+    ext = bool(ext or mixed)
     M = nets[0][0].shape[0]
     outs, blocks = [], []
     for gy, ys, layers in nets:
@@ -902,7 +928,7 @@ def mlp_walk_backward(nets, ext=None):
         dz = [torch.empty(M, layers[l][0].shape[0], device=gy.device, dtype=torch.float32) if ext else torch.empty_like(ys[l]) for l in range(len(layers) - 1)]
         blocks.append((gy, layers, dz, ys[:len(layers) - 1]))
         outs.append(dz + [gy])
-    return outs if _walk_launch("backward", blocks, ext, None, M, _stream(nets[0][0])) else None
+    return outs if _walk_launch("backward", blocks, ext, None, M, _stream(nets[0][0]), mixed) else None
 
 
 USE_WALK = True       # tools / tests switch it off to time or check the per-layer launches
@@ -912,19 +938,36 @@ USE_WALK = True       # tools / tests switch it off to time or check the per-lay
 _WALK_ONLY = "a network with an activation other than ELU or with d2rl runs on the network walk only, and the walk declined these shapes"
 
 
+_MIXED_ONLY = ("mixed_precision: a network with bf16 operands runs on the network walk only (there is no per-layer bf16 tier), and the walk declined these "
+               "shapes or is switched off")
+
+
+def _mixed_of(layer_lists):
+    return any(bool(getattr(layers, "mixed", False)) for layers in layer_lists)
+
+
 def _pairable(la, lc):
     return len(la) == len(lc) and all(a[2] == c[2] for a, c in zip(la, lc))
 
 
-def forward_nets(nets, store_hidden=True, norms=None):
+def forward_nets(nets, store_hidden=True, norms=None, mixed=None):
     """the forward of one or two networks [(x, layers)] over the same rows; returns the list of layer outputs per network.  In this order: ONE launch on the
     network walk (any activation code, d2rl: LayerLists); a network that needs the walk and was declined raises - the per-layer launches are ELU / none
     stacks and are never applied to a network that asked for something else (the trainer asks net_fits() once and runs such a network on torch); else the
     per-layer tier - two Linear / ELU stacks of the same depth and activations one grouped launch per layer (4 launches instead of 8 for the trainer's
     MLPs), anything else layer by layer.  `norms`: per network None or (mean_f, inv_std_f, clip): the inputs are RAW and normalised on the way in - inside
-    the walk, or by one normalize_rows launch per network in front of the per-layer tier."""
+    the walk, or by one normalize_rows launch per network in front of the per-layer tier.  `mixed` (None: what the LayerLists say): `mixed_precision` - ONE
+    launch of the walk with bf16 operands (tfp_net_forward_bf16) or a RuntimeError: there is no per-layer bf16 tier, the trainer asks net_fits(mixed=True)
+    once and runs a network the walk declines on the torch statement."""
     if norms is not None and not any(e is not None for e in norms):
         norms = None
+    if mixed is None:
+        mixed = _mixed_of([layers for _, layers in nets])
+    if mixed:
+        out = mlp_walk_forward(nets, store_hidden, norms, mixed=True) if USE_WALK else None
+        if out is None:
+            raise RuntimeError(_MIXED_ONLY)
+        return out
     if USE_WALK:
         out = mlp_walk_forward(nets, store_hidden, norms)
         if out is not None:
@@ -952,12 +995,20 @@ def mlp_forward_pair(xa, la, xc, lc, store_hidden=True, norms=None):
     return ya, yc
 
 
-def _weight_grads(gys, inps, ys, outs, direct=False, grouped=True):
+def _weight_grads(gys, inps, ys, outs, direct=False, grouped=True, mixed=False):
     """the tail of a backward pass: the weight / bias gradient products (gy or dZ, layer input, grad_out) of the parallel lists, eight per launch - the
     direct kernel (`direct`: every dZ is plain) -> one grouped launch -> one by one.  ys: None, or per product the ELU output whose derivative the operand
-    load forms.  Chunk sums deferred: flush_partial_sums()"""
+    load forms.  Chunk sums deferred: flush_partial_sums().  `mixed`: the direct kernel with bf16 operands (every dZ is plain), and for a group it declines
+    at run time the torch products of the rounded operands, written at once: gw = bf16r(gy).T @ bf16r(x), gb = gy.sum(0)"""
     for i in range(0, len(gys), 8):
         sl = slice(i, i + 8)
+        if mixed:
+            if not (USE_DIRECT_DW and gemm_tn_bias_direct(gys[sl], inps[sl], outs[sl], mixed=True)):
+                _count("n_mixed_dw_torch")
+                for gy, x, (gw, gb) in zip(gys[sl], inps[sl], outs[sl]):
+                    torch.matmul(bf16r(gy).t(), bf16r(x), out=gw)
+                    torch.sum(gy, 0, out=gb)
+            continue
         if direct and USE_DIRECT_DW and gemm_tn_bias_direct(gys[sl], inps[sl], outs[sl]):
             continue
         if not (grouped and gemm_tn_bias_group(gys[sl], inps[sl], ys[sl] if ys is not None else None, outs[sl])):
@@ -992,19 +1043,26 @@ def _backward_per_layer(nets):
         _weight_grads(g, inps, ys if has_elu else None, outs, grouped=pair)
 
 
-def backward_nets(nets, walk=True):
+def backward_nets(nets, walk=True, mixed=None):
     """gradients of every layer's weight and bias of one or two networks [(x, ys, gy, layers)] into the layers' `grad_out` buffers, given the gradient
     `gy` of each network output; the input gradient of the first layer is not formed.  The counterpart of forward_nets, same order: the walk - ONE launch
     for every dZ, then all weight / bias gradients of the step as plain products dZ_l^T [input_l | 1] -, the refusal, the per-layer tier (5 launches
-    instead of 14 for the trainer's MLPs).  Chunk sums deferred: call flush_partial_sums() afterwards."""
+    instead of 14 for the trainer's MLPs).  Chunk sums deferred: call flush_partial_sums() afterwards.  `mixed` (None: what the LayerLists say): the walk
+    and the direct weight gradients with bf16 operands, or a RuntimeError (no per-layer bf16 tier)."""
+    if mixed is None:
+        mixed = _mixed_of([layers for _, _, _, layers in nets])
+    if mixed and not (walk and USE_WALK):
+        raise RuntimeError(_MIXED_ONLY)
     if walk and USE_WALK:
-        dz = mlp_walk_backward([(gy, ys, layers) for _, ys, gy, layers in nets])
+        dz = mlp_walk_backward([(gy, ys, layers) for _, ys, gy, layers in nets], mixed=mixed)
+        if dz is None and mixed:
+            raise RuntimeError(_MIXED_ONLY)
         if dz is not None:
             gys, inps, outs = [], [], []
             for (x, ys, _, layers), d in zip(nets, dz):
                 for k in range(len(layers) - 1, -1, -1):
                     gys.append(d[k]); inps.append(ys[k - 1] if k > 0 else x); outs.append(layers[k][3])
-            _weight_grads(gys, inps, None, outs, direct=True)
+            _weight_grads(gys, inps, None, outs, direct=True, mixed=mixed)
             return
     if any(needs_net_walk(layers) for _, _, _, layers in nets):
         raise RuntimeError(_WALK_ONLY)

@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
 """End-to-end PPO on the native TriFinger env (BASELINE config 5: difficulty 4, 8192 envs per GPU).
 
-    python scripts/train_ppo.py gym=trifinger_difficulty_4 args.num_envs=8192 [epochs=20] [args.checkpoint=run/nn/trifinger.pth] [save_dir=run/nn] [--symmetry] [--diagnostics]
+    python scripts/train_ppo.py gym=trifinger_difficulty_4 args.num_envs=8192 [epochs=20] [args.checkpoint=run/nn/trifinger.pth] [save_dir=run/nn] [--symmetry] [--diagnostics] [--mixed-precision]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 scripts/train_ppo.py ...
 
 One process per GPU; envs are sharded (no data-path collective), gradients are averaged with one fused RCCL
 all-reduce per minibatch.  Uses RL-Games' hyper-parameters of resources/config/rlg/asymm.yaml (leibnizgym_amd/ppo.py).
 --symmetry: rlg.params.config.symmetry_augmentation=True - every minibatch with its two images under the robot's 120-degree turn (leibnizgym_amd/symmetry.py).
---diagnostics: rlg.params.config.diagnostics=True - clip fraction, approx_kl, explained variance and gradient norm on the epoch line (leibnizgym_amd/ppo.py)."""
+--diagnostics: rlg.params.config.diagnostics=True - clip fraction, approx_kl, explained variance and gradient norm on the epoch line (leibnizgym_amd/ppo.py).
+--mixed-precision: rlg.params.config.mixed_precision=True - every Linear's products take bf16 operands with fp32 sums (leibnizgym_amd/ppo.py: _MixedLinear)."""
 import os
 import sys
 import time
@@ -35,6 +36,8 @@ def main(argv):
             rest.append("rlg.params.config.symmetry_augmentation=True")
         elif a == "--diagnostics":
             rest.append("rlg.params.config.diagnostics=True")
+        elif a == "--mixed-precision":
+            rest.append("rlg.params.config.mixed_precision=True")
         else:
             rest.append(a)
     cfg = compose(rest)
