@@ -47,7 +47,8 @@ int tfp_linear_fwd(const float* A, const float* W, const float* bias, float* C, 
 int tfp_gemm_nn(const float* A, const float* Y, const float* B, float* C, int32_t M, int32_t N, int32_t K, void* stream);
 /* ... the same product leaving as the dZ of the layer BELOW: C[M, N] = (dZ . B) * elu'(Yout[M, N]) with Yout that layer's ELU output (NULL: no factor).
  * A backward walk that chains these (A = the dZ the call above produced, Y = NULL) multiplies every activation gradient once, where the product is
- * stored, instead of in the operand loads of the two products that consume it; same bits.  N % 4 == 0 needs Yout 16-byte aligned. */
+ * stored, instead of in the operand loads of the two products that consume it; same bits.  N % 4 == 0 needs Yout 16-byte aligned (-1 otherwise); C itself
+ * may lie at any float boundary - its four-float stores are global accesses, which need dword alignment only. */
 int tfp_gemm_nn_dz(const float* A, const float* Y, const float* B, const float* Yout, float* C, int32_t M, int32_t N, int32_t K, void* stream);
 
 /* Weight and bias gradient: gw[N1, N2] = dZ^T B, gb[N1] = column sums of dZ, for dZ[rows, N1] (as above), B[rows, N2].

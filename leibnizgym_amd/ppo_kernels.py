@@ -885,14 +885,15 @@ def _walkable(nets):
             and all(x.dim() == 2 and x.is_contiguous() and x.shape[0] == nets[0][0].shape[0] for x, _ in nets))
 
 
-def mlp_walk_forward(nets, store_hidden=True, norms=None, ext=None, mixed=False):
+def mlp_walk_forward(nets, store_hidden=True, norms=None, ext=None, mixed=False, outs=None):
     """nets: [(x, layers)] for one or two Linear / ELU stacks over the same rows (`layers` as in mlp_forward).  ONE launch; returns the list of layer
     outputs per network (hidden outputs None with store_hidden = False: the rollout needs the network outputs only), or None when the shapes do not
     fit the walk (the caller then runs the layers one by one).  `norms`: None, or per network None / (mean_f, inv_std_f, clip): that network reads
     clamp((x - mean_f) * inv_std_f, -clip, clip), formed while the rows are staged (tfp_mlp_forward_norm) - the bits of the plain walk on normalize_rows(x).
     A network with another activation than ELU / none or with d2rl (`layers` a LayerList) takes the call to tfp_net_forward (`ext` = True forces that entry
     point, which for plain networks returns the same bits); of a d2rl network the outputs of the layers 0 .. len - 3 come back as the wide rows [h | x].
-    `mixed`: tfp_net_forward_bf16 - every product with bf16 operands, everything else as the extended entry point."""
+    `mixed`: tfp_net_forward_bf16 - every product with bf16 operands, everything else as the extended entry point.
+    `outs`: preallocated tensors to write instead of new ones, per network one per layer (None where nothing is stored); they are what is returned."""
     if not _walkable(nets):
         return None
     if ext is None:
@@ -903,29 +904,45 @@ def mlp_walk_forward(nets, store_hidden=True, norms=None, ext=None, mixed=False)
     if norms is not None and not (len(norms) == len(nets) and all(e is None or _norm_ok(e, x.shape[1], x.device) for e, (x, _) in zip(norms, nets))):
         return None
     M = nets[0][0].shape[0]
-    outs = [[torch.empty(M, _out_width(layers, l) if ext else w.shape[0], device=x.device, dtype=torch.float32)
-             if (store_hidden or l == len(layers) - 1) else None for l, (w, _, _, _) in enumerate(layers)] for x, layers in nets]
+    shapes = [[(M, _out_width(layers, l) if ext else w.shape[0]) if (store_hidden or l == len(layers) - 1) else None for l, (w, _, _, _) in enumerate(layers)]
+              for _, layers in nets]
+    if outs is None:
+        outs = [[None if sh is None else torch.empty(sh, device=x.device, dtype=torch.float32) for sh in net] for net, (x, _) in zip(shapes, nets)]
+    elif len(outs) != len(nets) or any(len(o) != len(net) or any((t is None) != (sh is None) or (t is not None and (
+            t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != sh or t.device != x.device)) for t, sh in zip(o, net))
+            for o, net, (x, _) in zip(outs, shapes, nets)):
+        raise ValueError(f"outs: per network one contiguous float32 tensor per stored layer output, shapes {shapes}, on the device of the input")
     blocks = [(x, layers, ys, None) for (x, layers), ys in zip(nets, outs)]
     return outs if _walk_launch("forward", blocks, ext, norms, M, _stream(nets[0][0]), mixed) else None
 
 
-def mlp_walk_backward(nets, ext=None, mixed=False):
+def mlp_walk_backward(nets, ext=None, mixed=False, outs=None):
     """nets: [(gy, ys, layers)]: gy = gradient of the network output, ys = the layer outputs the forward kept.  ONE launch for the whole input-gradient
-    chain; returns per network the list dz with dz[l] = gradient of layer l's pre-activation (dz[-1] is gy itself), or None when the shapes do not fit."""
+    chain; returns per network the list dz with dz[l] = gradient of layer l's pre-activation (dz[-1] is gy itself), or None when the shapes do not fit.
+    `outs`: preallocated dz tensors to write instead of new ones, per network one per layer but the last."""
     if not (0 < len(nets) <= 2) or any(len(layers) > WALK_MAXL or any(y is None for y in ys) for _, ys, layers in nets):
         return None
     if ext is None:
         ext = any(needs_net_walk(layers) for _, _, layers in nets)
     ext = bool(ext or mixed)
     M = nets[0][0].shape[0]
-    outs, blocks = [], []
-    for gy, ys, layers in nets:
+    given, outs, blocks = outs, [], []
+    if given is not None and len(given) != len(nets):
+        raise ValueError("outs: one list of dz tensors per network")
+    for ni, (gy, ys, layers) in enumerate(nets):
         gy = gy if gy.is_contiguous() else gy.contiguous()
         for l in range(len(layers) - 1 if ext else 0):               # dZ covers the hidden part only; ys[l] may be the wide rows [h | x]
             if tuple(ys[l].shape) != (M, _out_width(layers, l)) or not ys[l].is_contiguous():
                 raise ValueError(f"saved output of layer {l}: {tuple(ys[l].shape)}, contiguous {ys[l].is_contiguous()}; the walk stored and reads "
                                  f"({M}, {_out_width(layers, l)}) contiguous")
-        dz = [torch.empty(M, layers[l][0].shape[0], device=gy.device, dtype=torch.float32) if ext else torch.empty_like(ys[l]) for l in range(len(layers) - 1)]
+        shapes = [(M, layers[l][0].shape[0]) if ext else tuple(ys[l].shape) for l in range(len(layers) - 1)]
+        if given is None:
+            dz = [torch.empty(sh, device=gy.device, dtype=torch.float32) if ext else torch.empty_like(ys[l]) for l, sh in enumerate(shapes)]
+        else:
+            dz = list(given[ni])
+            if len(dz) != len(shapes) or any(d.dtype != torch.float32 or not d.is_contiguous() or tuple(d.shape) != sh or d.device != gy.device
+                                             for d, sh in zip(dz, shapes)):
+                raise ValueError(f"outs: network {ni} takes contiguous float32 dz tensors of shapes {shapes} on the device of the gradient")
         blocks.append((gy, layers, dz, ys[:len(layers) - 1]))
         outs.append(dz + [gy])
     return outs if _walk_launch("backward", blocks, ext, None, M, _stream(nets[0][0]), mixed) else None

@@ -256,14 +256,15 @@ def matrix_model(lib, family):
     return surface_model(lib, low_ring=True) if surf else lib.default_model()
 
 
-def matrix_engine(lib, device, family, a, asym, variant=None):
-    """one engine of the matrix cell (family, A = `a`, ASYM = `asym`), not yet reset; `variant` is forced and must be accepted"""
+def matrix_engine(lib, device, family, a, asym, variant=None, n=MATRIX_N, episode_length=MATRIX_EPISODE):
+    """one engine of the matrix cell (family, A = `a`, ASYM = `asym`), not yet reset; `variant` is forced and must be accepted; `n`, `episode_length`:
+    the matrix's own unless given (tests/test_guard_bands*.py: smaller populations, shorter episodes)"""
     dr, _, ext = family
     kw = dict(command_mode={9: "torque", 18: "position_impedance"}[a], asymmetric_obs=bool(asym), task_difficulty=4, reward_terms=D4_REWARDS,
               robot_reset="random", dof_pos_stddev=0.6, dof_vel_stddev=0.3, success=MATRIX_SUCCESS, model=matrix_model(lib, family))
     if dr:
         kw["domain_randomization"] = MATRIX_EXT_DR if ext == 1 else MATRIX_BASE_DR
-    eng = TrifingerEngine(make_config(lib, MATRIX_N, seed=MATRIX_SEED, episode_length=MATRIX_EPISODE, **kw), device=device, lib=lib)
+    eng = TrifingerEngine(make_config(lib, n, seed=MATRIX_SEED, episode_length=episode_length, **kw), device=device, lib=lib)
     assert eng.action_dim == a
     if variant is not None:
         eng.kernel_variant = variant
