@@ -2,13 +2,18 @@
 """End-to-end PPO on the native TriFinger env (BASELINE config 5: difficulty 4, 8192 envs per GPU).
 
     python scripts/train_ppo.py gym=trifinger_difficulty_4 args.num_envs=8192 [epochs=20] [args.checkpoint=run/nn/trifinger.pth] [save_dir=run/nn] [--symmetry] [--diagnostics] [--mixed-precision]
+                                 [--fingertip-actions {delta,absolute}]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 scripts/train_ppo.py ...
 
 One process per GPU; envs are sharded (no data-path collective), gradients are averaged with one fused RCCL
 all-reduce per minibatch.  Uses RL-Games' hyper-parameters of resources/config/rlg/asymm.yaml (leibnizgym_amd/ppo.py).
 --symmetry: rlg.params.config.symmetry_augmentation=True - every minibatch with its two images under the robot's 120-degree turn (leibnizgym_amd/symmetry.py).
 --diagnostics: rlg.params.config.diagnostics=True - clip fraction, approx_kl, explained variance and gradient norm on the epoch line (leibnizgym_amd/ppo.py).
---mixed-precision: rlg.params.config.mixed_precision=True - every Linear's products take bf16 operands with fp32 sums (leibnizgym_amd/ppo.py: _MixedLinear)."""
+--mixed-precision: rlg.params.config.mixed_precision=True - every Linear's products take bf16 operands with fp32 sums (leibnizgym_amd/ppo.py: _MixedLinear).
+--fingertip-actions {delta,absolute}: the policy commands the three fingertips (leibnizgym_amd/wrappers/fingertip_action.py); the env is wrapped before the
+trainer sees it, one more launch per env step.  Off by default: every launch is then what it was.  Refused with --symmetry: the symmetry tables permute
+joint actions, a Cartesian command turns as a vector.  With a position-mode config the env's own joint PD law stands behind the joint targets, and at the default
+control step of 20 ms it rings: fingertip commands then train on a ringing plant - use a torque-mode config, or `gym.sim.dt=0.005`."""
 import os
 import sys
 import time
@@ -24,10 +29,13 @@ from leibnizgym_amd.utils.rlg_train import RlGamesGpuEnvAdapter, diagnostic_line
 from leibnizgym_amd.wrappers import VecTaskPython  # noqa: E402
 
 
-def main(argv):
-    epochs, save_dir = 20, None
+def parse_args(argv):
+    """-> (epochs, save_dir, fingertip frame or None, the overrides for `compose`); ValueError for what is refused by name"""
+    epochs, save_dir, fingertip = 20, None, None
     rest = []
-    for a in argv:
+    argv = list(argv)
+    while argv:
+        a = argv.pop(0)
         if a.startswith("epochs="):
             epochs = int(a.split("=", 1)[1])
         elif a.startswith("save_dir="):
@@ -38,8 +46,20 @@ def main(argv):
             rest.append("rlg.params.config.diagnostics=True")
         elif a == "--mixed-precision":
             rest.append("rlg.params.config.mixed_precision=True")
+        elif a == "--fingertip-actions" or a.startswith("--fingertip-actions="):
+            fingertip = a.split("=", 1)[1] if "=" in a else (argv.pop(0) if argv else None)
+            if fingertip not in ("delta", "absolute"):
+                raise ValueError(f"--fingertip-actions: one of delta, absolute, got {fingertip!r}")
         else:
             rest.append(a)
+    if fingertip is not None and any(r.replace(" ", "").lower() == "rlg.params.config.symmetry_augmentation=true" for r in rest):
+        raise ValueError("--fingertip-actions with --symmetry (symmetry_augmentation): the symmetry tables permute joint actions, while a Cartesian fingertip "
+                         "command turns as a vector; a table for it does not exist")
+    return epochs, save_dir, fingertip, rest
+
+
+def main(argv):
+    epochs, save_dir, fingertip, rest = parse_args(argv)
     cfg = compose(rest)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -64,7 +84,11 @@ def main(argv):
     n = cfg["gym"]["num_instances"]                 # envs per GPU
     env = TrifingerEnv(config=cfg["gym"], device=dev, verbose=False, env_id_offset=rank * n,
                        global_num_instances=world * n)
-    adapter = RlGamesGpuEnvAdapter("rlgpu", n, env=VecTaskPython(env, rl_device=dev))
+    vec = VecTaskPython(env, rl_device=dev)
+    if fingertip is not None:
+        from leibnizgym_amd.wrappers.fingertip_action import FingertipActionEnv
+        vec = FingertipActionEnv(vec, frame=fingertip)
+    adapter = RlGamesGpuEnvAdapter("rlgpu", n, env=vec)
     # hyper-parameters from the agent tree (asymm.yaml); minibatch = envs per GPU, as update_cfg sets it
     tr = PPOTrainer(adapter, env.get_obs_dim(), env.get_state_dim(), env.get_action_dim(),
                     PPOConfig.from_rlg(cfg["rlg"], num_envs=n), device=dev)
